@@ -2,7 +2,12 @@
 """Headline benchmark: PathIntegrator on the synthetic ~1M-triangle scene, 1920x1080 @ 64 spp
 (BASELINE.json configs[2]), film tiles sharded across the ranks, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  Everything else the benchmark measures --
+per-kernel times and rooflines from one more frame, serialised; roofline.hbm_regime (the 5 M-triangle scene); live
+rocprofv3 --pmc passes; the record-fetch ceiling; the CPU reference baseline -- runs only with --full.
+--dump-outputs DIR writes the image of the last timed step as DIR/image.npy (float32).
 
 With N > 1 and no launcher around it (WORLD_SIZE unset) the script starts its own N ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`); under
@@ -19,6 +24,7 @@ import argparse
 import json
 import os
 import re
+import shutil
 import socket
 import subprocess
 import sys
@@ -41,6 +47,7 @@ INFINITY_CACHE_BYTES = 256 << 20
 FOG = ('MakeNamedMedium "fog" "string type" "homogeneous" "rgb sigma_a" [ 0.02 0.03 0.04 ] "rgb sigma_s" [ 0.15 0.12 0.1 ] "float g" [ 0.4 ]\n'
        'MediumInterface "" "fog"\n')
 OPTIONAL_PMC = ("GRBM_TA_BUSY", "TCP_PENDING_STALL_CYCLES_sum")
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 EMULATED = os.environ.get("PBRT_EMULATED_DEVICE") == "1"  # tests/emu: the device library compiled for the host (a functional check, never a measurement)
 
 
@@ -266,6 +273,10 @@ def run_workload(ctx, args, steps, warmup, keep_image=False, serial_frame=False)
     ctx.sync()
     elapsed = time.perf_counter() - t0
     cn = gs.counters()
+    image = None
+    if ctx.rank == 0 and keep_image and last is not None:  # final image (outside the timed region): MergeFilmTile per shard + WriteImage arithmetic
+        shards = gather.shards(last) if gather else [(last.film, last.strays, int(last.nstrays.item()))]
+        image = pdist.merge_shards(pkg, scene, gs.tile_count, shards)  # (before the serialised frame, which renders into the same buffer)
     # Per-kernel times (HIP events around every launch) only mean something while kernels do not share the chip.  The timed frames of a
     # one-GPU run overlap each any-hit launch with the next closest-hit launch (PG_OVERLAP_SHADOW=1: +1.2 % Mrays/s,
     # profiles/r04b_bench_overlap*.json); the figures the rooflines are made of come from ONE more frame, serialised, after the timed region.
@@ -300,12 +311,25 @@ def run_workload(ctx, args, steps, warmup, keep_image=False, serial_frame=False)
         per_rank_kernels = [[float(x) for x in t.tolist()] for t in every_k]
     elapsed, rays, samples = (float(x) for x in stats.tolist())
     m = types.SimpleNamespace(elapsed=elapsed, rays=rays, samples=samples, cn=cn, scene=scene, gs=gs, t_parse=t_parse, workdir=workdir, serial=serial,
-                              per_rank_ms=[t / max(1, steps) * 1e3 for t in per_rank], steps=steps, image=None,
+                              per_rank_ms=[t / max(1, steps) * 1e3 for t in per_rank], steps=steps, image=image,
                               per_rank_kernel_ms=[{k[:-3]: round(v, 3) for k, v in zip(kn, row)} for row in per_rank_kernels])
-    if ctx.rank == 0 and keep_image and last is not None:  # final image (outside the timed region): MergeFilmTile per shard + WriteImage arithmetic
-        shards = gather.shards(last) if gather else [(last.film, last.strays, int(last.nstrays.item()))]
-        m.image = pdist.merge_shards(pkg, scene, gs.tile_count, shards)
     return m
+
+
+def dump_outputs(outdir, image):
+    """--dump-outputs: what the last timed step rendered, as a caller of the render receives it -- rank 0's merged (h, w, 3) image -- in
+    float32.  A frame above DUMP_BYTES is written as a fixed sample of its pixels (seed 0), their flat indices in image_pixels.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(outdir, "image.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    n = DUMP_BYTES // 2 // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(outdir, "image.npy"), px[idx])
+    np.save(os.path.join(outdir, "image_pixels.npy"), idx.astype(np.float64))
 
 
 def shading_mode(cn):
@@ -352,7 +376,7 @@ def live_pmc(bench_args, passes, timeout=300):
     for counters in passes:
         d = tempfile.mkdtemp(prefix="pbrt_pmc_", dir="/tmp")
         cmd = [exe, "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__), *bench_args,
-               "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-hbm-regime", "--no-live-pmc", "--no-overlap"]
+               "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-hbm-regime", "--no-live-pmc", "--no-overlap"]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
         except Exception as e:
@@ -557,6 +581,82 @@ def gather_ceiling(m, working_set, pmc_kernels, pmc_src):
         return {"error": str(e)}
 
 
+def full_measurements(ctx, args, m, hbm, workload, ms_per_step):
+    """What --full adds to rank 0's line, after the timed region and with this process's device scenes closed: rooflines and per-kernel
+    times, roofline.hbm_regime, live PMC passes, the record-fetch ceiling, the CPU reference baseline."""
+    # memory-side traffic, L2 hit rates and vector-instruction counts of the hot kernels: measured by this run (child rocprofv3 --pmc
+    # passes over one frame each, after the timed region) unless --no-live-pmc / N > 1 / an emulated device
+    # (this process's device scenes go first: a child pass renders the same workload in a process of its own, and with 100+ GB of
+    # buffers still held here pg_render's k_material lists would not fit there -- it would measure the k_shade<2> fallback instead)
+    if not EMULATED: torch.cuda.empty_cache()
+    live, live_why, live_hbm = None, "--no-live-pmc", None
+    wl_args = ["--workload", args.workload, "--grid", str(args.grid), "--tris", str(args.tris), "--xres", str(args.xres), "--yres", str(args.yres),
+               "--spp", str(args.spp), "--filter", args.filter]
+    if ctx.world == 1 and not ctx.multi and not EMULATED and not args.no_live_pmc:
+        live, live_why = live_pmc(wl_args, (["FETCH_SIZE"], ["WRITE_SIZE"], ["TCC_HIT_sum", "TCC_MISS_sum"], ["SQ_INSTS_VALU", "SQ_THREAD_CYCLES_VALU"],
+                                            ["GRBM_TA_BUSY", "GRBM_GUI_ACTIVE"], ["TCP_PENDING_STALL_CYCLES_sum", "TCP_GATE_EN1_sum"]))
+        if live is None: sys.stderr.write(f"bench: live PMC passes failed ({live_why}); replaying profiles/pmc_traffic.json\n")
+        if hbm is not None and live is not None:
+            a5l = ["--workload", "synthetic", "--grid", str(hbm.args.grid), "--xres", str(args.xres), "--yres", str(args.yres), "--spp", str(args.spp), "--filter", args.filter]
+            live_hbm, why5 = live_pmc(a5l, (["FETCH_SIZE"], ["WRITE_SIZE"], ["TCC_EA0_RDREQ_DRAM_32B_sum"]))
+            if live_hbm is None: sys.stderr.write(f"bench: live PMC passes of the hbm-regime workload failed ({why5})\n")
+    # the frame the per-kernel figures come from: the serialised one where the timed frames overlapped kernels
+    km = m if m.serial is None else types.SimpleNamespace(cn=m.serial.cn, scene=m.scene)
+    ksteps = args.steps if m.serial is None else 1
+    kernels, working_set, bound, peak, pmc_kernels, pmc_src = kernel_rooflines(km, workload, live)
+    gather = gather_ceiling(km, working_set, pmc_kernels, pmc_src)
+    roofline = dict(kernels[0]) if kernels else {"kernel": None, "bound": bound, "achieved": 0.0, "peak": peak, "unit": "GB/s", "frac": 0.0, "traffic": None}
+    roofline["working_set_bytes"] = working_set
+    # every reading of the dominant kernel's rate at the top level: against the L2s' aggregate bandwidth, against the HBM peak (north star's
+    # yardstick; above 1 = the caches serve the gathers), and what the L2s' memory side moved against the HBM peak
+    if kernels:
+        roofline["frac_of_l2"] = roofline["achieved"] / L2_PEAK_GBS
+        roofline["frac_of_hbm_algorithmic"] = roofline["achieved"] / HBM_PEAK_GBS
+        roofline["cache_served"] = bool(roofline["bound"] == "l2")
+        if roofline.get("l2_memory_side"): roofline["l2_memory_side_frac_of_hbm"] = roofline["l2_memory_side"]["frac_of_hbm_peak"]
+    if gather is not None:
+        roofline["gather"] = gather
+    roofline["bound_reason"] = (f"BVH + triangle records {working_set / 2**20:.0f} MiB " +
+                                ("fit the 256 MiB Infinity Cache: gathers are served on-die, L2 bandwidth is the ceiling"
+                                 if bound == "l2" else "exceed the 256 MiB Infinity Cache: gathers reach HBM"))
+    if hbm is not None:
+        hk, hws, hbound, _, _, _ = kernel_rooflines(hbm if hbm.serial is None else types.SimpleNamespace(cn=hbm.serial.cn, scene=hbm.scene), describe(hbm.args, hbm.scene), live_hbm)
+        t = next((k for k in hk if k["kernel"].startswith("k_trace<0>")), None)
+        if t is not None and hbound == "hbm":
+            roofline["hbm_regime"] = {
+                "kernel": t["kernel"], "workload": describe(hbm.args, hbm.scene), "working_set_bytes": hws, "bound": "hbm",
+                "achieved": t["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": t["achieved"] / HBM_PEAK_GBS,
+                "avg_launch_ms": t["avg_launch_ms"], "launches": t["launches"], "algorithmic_bytes_per_launch": t["algorithmic_bytes_per_launch"],
+                "steps": hbm.steps, "ms_per_step": hbm.elapsed / hbm.steps * 1e3, "Mrays_per_s": hbm.rays / hbm.elapsed / 1e6,
+                "note": "timed in THIS run (HIP events per launch); algorithmic bytes (SURVEY 8d) / kernel time / 8 TB/s. Algorithmic bytes count "
+                        "every reference node fetch, also those the L2s serve, so this is the north star's roofline fraction, NOT memory-side "
+                        "traffic: `l2_memory_side` is what the L2s' fabric ports moved for this kernel (FETCH_SIZE x factor + WRITE_SIZE; Infinity-Cache hits included), beside the same 8 TB/s"}
+            for f in ("traffic", "l2_memory_side", "traffic_source"):  # the memory-side companion (weak point of round 3: 0.97 alone reads as HBM utilisation)
+                if t.get(f) is not None: roofline["hbm_regime"][f] = t[f]
+    other_ms = {k: km.cn[k] for k in ("resolve_ms", "generate_ms", "film_ms")}
+    out = {
+        "roofline": roofline,
+        "roofline_kernels": kernels,
+        "kernel_ms_per_step": {**{k["kernel"].split(" ")[0]: k["total_ms"] / ksteps for k in kernels},
+                               **{k[:-3]: v / ksteps for k, v in other_ms.items()}},
+    }
+    if roofline.get("hbm_regime"):  # also at the top level of the line (a parser that keeps only known keys of `roofline` still sees it)
+        out["hbm_regime"] = roofline["hbm_regime"]
+    if live:
+        # the counters of this run's own PMC passes, kernel by kernel (the shading slot's roofline merges k_shade_order + k_material + k_shade<.>)
+        out["pmc_by_kernel"] = {k.replace("void ", "")[:48]: {f: (round(v, 4) if isinstance(v, float) else v) for f, v in e.items()} for k, e in sorted(live.items())
+                                if e.get("fetch_KiB_per_launch", 0) * e.get("launches", 1) > 1e5}
+    if m.serial is not None:
+        out["kernel_times"] = {
+            "from": "ONE extra frame after the timed region with every kernel alone on the chip (pg_scene_set_option PG_OPT_OVERLAP_SHADOW 0): kernel_ms_per_step, roofline and "
+                    "roofline_kernels are that frame's HIP-event times; the timed frames (ms_per_step, value) run each any-hit launch beside the next "
+                    "closest-hit launch, so they are shorter than the sum of the kernels",
+            "serialized_frame_ms": m.serial.ms, "sum_of_kernels_ms": sum(out["kernel_ms_per_step"].values()), "overlapped_frame_ms": ms_per_step}
+    if ctx.world == 1 and not args.no_cpu_baseline and not EMULATED:
+        out["cpu_baseline"] = cpu_baseline(m.workdir, args)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -579,6 +679,12 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="one GPU: do not run any-hit launches beside the next closest-hit launch in the timed frames "
                                                              "(every kernel alone on the chip, as in the serialised frame the rooflines are taken from; what rocprofv3 --stats should profile)")
     ap.add_argument("--out", default=None, help="write the rendered image (PFM) here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step (rank 0's merged frame) as DIR/image.npy, float32 (a fixed, seeded sample of "
+                         "its pixels with DIR/image_pixels.npy when the frame is larger than 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: per-kernel times and rooflines from one more frame, serialised; roofline.hbm_regime; live "
+                         "rocprofv3 --pmc passes; the record-fetch ceiling; the CPU reference baseline (each still off with its --no-* option)")
     args = ap.parse_args()
     dx, dy, dspp = (400, 400, 8) if args.workload == "config0" else (1920, 1080, 64)
     args.xres, args.yres, args.spp = args.xres or dx, args.yres or dy, args.spp or dspp
@@ -588,18 +694,18 @@ def main():
     ctx = Context(args)
     # The any-hit launch of a bounce runs on a second stream beside the next bounce's closest-hit launch: a shard's launches are small
     # and their tails weigh more (one rank of 8: 48.7 instead of 52.9 ms, profiles/r03j_shard_timing.json), and the whole frame on one
-    # GPU gains 1.2 % (profiles/r04b_bench_overlap*.json).  Per-kernel times then overlap, so a one-GPU run takes them -- and its
+    # GPU gains 1.2 % (profiles/r04b_bench_overlap*.json).  Per-kernel times then overlap, so a one-GPU --full run takes them -- and its
     # rooflines -- from one more frame, serialised, after the timed region (run_workload, serial_frame).
     overlap = not args.no_overlap and os.environ.get("PG_OVERLAP_SHADOW", "1") != "0"
     args.overlap = overlap  # (handed to every scene through pg_scene_set_option: the library reads the environment only at scene creation)
     pkg = load_package()
     one_gpu = ctx.world == 1 and not ctx.multi
-    m = run_workload(ctx, args, args.steps, args.warmup, keep_image=bool(args.out), serial_frame=overlap and one_gpu)
+    m = run_workload(ctx, args, args.steps, args.warmup, keep_image=bool(args.out or args.dump_outputs), serial_frame=args.full and overlap and one_gpu)
     # North star: ">= 40 % of the HBM roofline in the BVH-traversal kernel" is a statement about the regime where the BVH does not
-    # fit the 256 MiB Infinity Cache, which config 3 (106 MiB) is not in.  After the headline steps, rank 0 of a 1-GPU run times 3
+    # fit the 256 MiB Infinity Cache, which config 3 (106 MiB) is not in.  After the headline steps, rank 0 of a 1-GPU --full run times 3
     # frames of the same scene at 5 M triangles (535 MiB of records) at the headline's resolution and spp: roofline.hbm_regime.
     hbm = None
-    if ctx.world == 1 and not ctx.multi and not args.no_hbm_regime and not EMULATED and args.workload == "synthetic" and args.grid == 708:
+    if args.full and ctx.world == 1 and not ctx.multi and not args.no_hbm_regime and not EMULATED and args.workload == "synthetic" and args.grid == 708:
         a5 = argparse.Namespace(**vars(args))
         a5.grid = 1582
         m.gs.close()
@@ -612,59 +718,11 @@ def main():
     if ctx.rank == 0:
         if args.out and m.image is not None:
             pkg.write_pfm(args.out, m.image)
+        if args.dump_outputs and m.image is not None:
+            dump_outputs(args.dump_outputs, m.image)
         workload = describe(args, m.scene)
-        # memory-side traffic, L2 hit rates and vector-instruction counts of the hot kernels: measured by this run (child rocprofv3 --pmc
-        # passes over one frame each, after the timed region) unless --no-live-pmc / N > 1 / an emulated device
-        # (this process's device scenes go first: a child pass renders the same workload in a process of its own, and with 100+ GB of
-        # buffers still held here pg_render's k_material lists would not fit there -- it would measure the k_shade<2> fallback instead)
         m.gs.close()
         if hbm is not None: hbm.gs.close()
-        if not EMULATED: torch.cuda.empty_cache()
-        live, live_why, live_hbm = None, "--no-live-pmc", None
-        wl_args = ["--workload", args.workload, "--grid", str(args.grid), "--tris", str(args.tris), "--xres", str(args.xres), "--yres", str(args.yres),
-                   "--spp", str(args.spp), "--filter", args.filter]
-        if ctx.world == 1 and not ctx.multi and not EMULATED and not args.no_live_pmc:
-            live, live_why = live_pmc(wl_args, (["FETCH_SIZE"], ["WRITE_SIZE"], ["TCC_HIT_sum", "TCC_MISS_sum"], ["SQ_INSTS_VALU", "SQ_THREAD_CYCLES_VALU"],
-                                                ["GRBM_TA_BUSY", "GRBM_GUI_ACTIVE"], ["TCP_PENDING_STALL_CYCLES_sum", "TCP_GATE_EN1_sum"]))
-            if live is None: sys.stderr.write(f"bench: live PMC passes failed ({live_why}); replaying profiles/pmc_traffic.json\n")
-            if hbm is not None and live is not None:
-                a5l = ["--workload", "synthetic", "--grid", str(hbm.args.grid), "--xres", str(args.xres), "--yres", str(args.yres), "--spp", str(args.spp), "--filter", args.filter]
-                live_hbm, why5 = live_pmc(a5l, (["FETCH_SIZE"], ["WRITE_SIZE"], ["TCC_EA0_RDREQ_DRAM_32B_sum"]))
-                if live_hbm is None: sys.stderr.write(f"bench: live PMC passes of the hbm-regime workload failed ({why5})\n")
-        # the frame the per-kernel figures come from: the serialised one where the timed frames overlapped kernels
-        km = m if m.serial is None else types.SimpleNamespace(cn=m.serial.cn, scene=m.scene)
-        ksteps = args.steps if m.serial is None else 1
-        kernels, working_set, bound, peak, pmc_kernels, pmc_src = kernel_rooflines(km, workload, live)
-        gather = gather_ceiling(km, working_set, pmc_kernels, pmc_src)
-        roofline = dict(kernels[0]) if kernels else {"kernel": None, "bound": bound, "achieved": 0.0, "peak": peak, "unit": "GB/s", "frac": 0.0, "traffic": None}
-        roofline["working_set_bytes"] = working_set
-        # every reading of the dominant kernel's rate at the top level: against the L2s' aggregate bandwidth, against the HBM peak (north star's
-        # yardstick; above 1 = the caches serve the gathers), and what the L2s' memory side moved against the HBM peak
-        if kernels:
-            roofline["frac_of_l2"] = roofline["achieved"] / L2_PEAK_GBS
-            roofline["frac_of_hbm_algorithmic"] = roofline["achieved"] / HBM_PEAK_GBS
-            roofline["cache_served"] = bool(roofline["bound"] == "l2")
-            if roofline.get("l2_memory_side"): roofline["l2_memory_side_frac_of_hbm"] = roofline["l2_memory_side"]["frac_of_hbm_peak"]
-        if gather is not None:
-            roofline["gather"] = gather
-        roofline["bound_reason"] = (f"BVH + triangle records {working_set / 2**20:.0f} MiB " +
-                                    ("fit the 256 MiB Infinity Cache: gathers are served on-die, L2 bandwidth is the ceiling"
-                                     if bound == "l2" else "exceed the 256 MiB Infinity Cache: gathers reach HBM"))
-        if hbm is not None:
-            hk, hws, hbound, _, _, _ = kernel_rooflines(hbm if hbm.serial is None else types.SimpleNamespace(cn=hbm.serial.cn, scene=hbm.scene), describe(hbm.args, hbm.scene), live_hbm)
-            t = next((k for k in hk if k["kernel"].startswith("k_trace<0>")), None)
-            if t is not None and hbound == "hbm":
-                roofline["hbm_regime"] = {
-                    "kernel": t["kernel"], "workload": describe(hbm.args, hbm.scene), "working_set_bytes": hws, "bound": "hbm",
-                    "achieved": t["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": t["achieved"] / HBM_PEAK_GBS,
-                    "avg_launch_ms": t["avg_launch_ms"], "launches": t["launches"], "algorithmic_bytes_per_launch": t["algorithmic_bytes_per_launch"],
-                    "steps": hbm.steps, "ms_per_step": hbm.elapsed / hbm.steps * 1e3, "Mrays_per_s": hbm.rays / hbm.elapsed / 1e6,
-                    "note": "timed in THIS run (HIP events per launch); algorithmic bytes (SURVEY 8d) / kernel time / 8 TB/s. Algorithmic bytes count "
-                            "every reference node fetch, also those the L2s serve, so this is the north star's roofline fraction, NOT memory-side "
-                            "traffic: `l2_memory_side` is what the L2s' fabric ports moved for this kernel (FETCH_SIZE x factor + WRITE_SIZE; Infinity-Cache hits included), beside the same 8 TB/s"}
-                for f in ("traffic", "l2_memory_side", "traffic_source"):  # the memory-side companion (weak point of round 3: 0.97 alone reads as HBM utilisation)
-                    if t.get(f) is not None: roofline["hbm_regime"][f] = t[f]
-        other_ms = {k: km.cn[k] for k in ("resolve_ms", "generate_ms", "film_ms")}
         if ctx.world == 1:
             sharding = ("one GPU renders every 16x16 film tile; " +
                         ("ONE-RANK RCCL run (PBRT_BENCH_FORCE_DIST=1): the packed gather of the frame runs over RCCL with one rank" if ctx.multi else "no gather") +
@@ -682,28 +740,15 @@ def main():
             **({"per_rank_kernel_ms_per_step": m.per_rank_kernel_ms} if ctx.multi else {}),
             "config": {"workload": workload, "sharding": sharding, "shading_mode": shading_mode(m.cn),
                        "rays_per_sample": m.rays / max(1.0, m.samples), "host_parse_and_bvh_s": m.t_parse},
-            "roofline": roofline,
-            "roofline_kernels": kernels,
-            "kernel_ms_per_step": {**{k["kernel"].split(" ")[0]: k["total_ms"] / ksteps for k in kernels},
-                                   **{k[:-3]: v / ksteps for k, v in other_ms.items()}},
         }
-        if roofline.get("hbm_regime"):  # also at the top level of the line (a parser that keeps only known keys of `roofline` still sees it)
-            result["hbm_regime"] = roofline["hbm_regime"]
-        if live:
-            # the counters of this run's own PMC passes, kernel by kernel (the shading slot's roofline merges k_shade_order + k_material + k_shade<.>)
-            result["pmc_by_kernel"] = {k.replace("void ", "")[:48]: {f: (round(v, 4) if isinstance(v, float) else v) for f, v in e.items()} for k, e in sorted(live.items())
-                                       if e.get("fetch_KiB_per_launch", 0) * e.get("launches", 1) > 1e5}
-        if m.serial is not None:
-            result["kernel_times"] = {
-                "from": "ONE extra frame after the timed region with every kernel alone on the chip (pg_scene_set_option PG_OPT_OVERLAP_SHADOW 0): kernel_ms_per_step, roofline and "
-                        "roofline_kernels are that frame's HIP-event times; the timed frames (ms_per_step, value) run each any-hit launch beside the next "
-                        "closest-hit launch, so they are shorter than the sum of the kernels",
-                "serialized_frame_ms": m.serial.ms, "sum_of_kernels_ms": sum(result["kernel_ms_per_step"].values()), "overlapped_frame_ms": result["ms_per_step"]}
+        if args.full:
+            result.update(full_measurements(ctx, args, m, hbm, workload, result["ms_per_step"]))
         if EMULATED:
             result["data"] = "synthetic (EMULATED DEVICE: functional check, not a measurement)"
-        if ctx.world == 1 and not args.no_cpu_baseline and not EMULATED:
-            result["cpu_baseline"] = cpu_baseline(m.workdir, args)
         print(json.dumps(result), flush=True)
+    for w in (m, hbm):  # the generated scene files
+        if w is not None:
+            shutil.rmtree(w.workdir, ignore_errors=True)
     if ctx.multi:
         dist.barrier()
         dist.destroy_process_group()

@@ -3,6 +3,7 @@ UNMODIFIED reference binary: tests/golden/*.pfm + *.json were rendered by oracle
 (oracle/make_golden.py).  Bit-exact images and identical ray statistics are required."""
 import json
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -33,50 +34,54 @@ def test_reference_binary_live_when_present(pkg, oracle, tmp_path):
     assert np.array_equal(pkg.read_pfm(out), pkg.read_pfm(os.path.join(GOLD, name + ".pfm")))
 
 
+CONFIG0 = os.path.join(os.path.dirname(GOLD), "golden_large", "config0")  # the reference's scenes/killeroo-simple.pbrt at 400x400 + its geometry
+
+
+def killeroo_scene(tmp_path, res, quad_light=False):
+    """scenes/killeroo-simple.pbrt of the reference (the committed fixture tests/golden_large/config0) at res x res; with `quad_light` its
+    sphere light swapped for an emissive quad at 2 spp.  Returns the scene file, written beside a copy of its geometry."""
+    os.makedirs(tmp_path / "geometry")
+    shutil.copy(os.path.join(CONFIG0, "geometry", "killeroo.pbrt"), tmp_path / "geometry" / "killeroo.pbrt")
+    s = open(os.path.join(CONFIG0, "config0.pbrt")).read()
+    s = s.replace('"integer xresolution" [400] "integer yresolution" [400]', f'"integer xresolution" [{res}] "integer yresolution" [{res}]').replace("config0.pfm", "kroo.pfm")
+    if quad_light:
+        s = (s.replace('"integer pixelsamples" [8]', '"integer pixelsamples" [2]')
+              .replace('Shape "sphere" "float radius" [3]', 'Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [ -3 -3 0  3 -3 0  3 3 0  -3 3 0 ]')
+              .replace('"integer nsamples" [8]', '"integer nsamples" [8] "bool twosided" "true"'))
+    scene_file = str(tmp_path / "kroo.pbrt")
+    open(scene_file, "w").write(s)
+    return scene_file
+
+
+def check_killeroo(pkg, oracle, tmp_path, scene_file, golden):
+    """Front end + oracle against the unmodified reference's image: the stored one (tests/golden/<golden>.pfm, rendered by
+    oracle/_ref/pbrt_oracle from this very scene file) and, where the reference binary is built, a live render of it now."""
+    img, _ = oracle.render_image(pkg.HostScene(scene_file))
+    assert np.array_equal(img, pkg.read_pfm(os.path.join(GOLD, golden + ".pfm")))
+    if os.path.exists(oracle.REF_BINARY):
+        out = str(tmp_path / "ref.pfm")
+        oracle.run_reference(scene_file, out, nthreads=4)
+        assert np.array_equal(img, pkg.read_pfm(out))
+
+
 def test_config0_killeroo_simple_unmodified(pkg, oracle, tmp_path):
     """BASELINE.json config 0, scenes/killeroo-simple.pbrt exactly as the reference ships it (sphere area light, two
     Loop-subdivided killeroos, plastic, uv'd planes) at a reduced resolution: the unmodified reference and this
-    repository's front end + oracle produce bit-identical images.  Reads /root/reference (build container only)."""
-    src = "/root/reference/scenes"
-    if not os.path.exists(os.path.join(src, "killeroo-simple.pbrt")) or not os.path.exists(oracle.REF_BINARY):
-        pytest.skip("reference scenes / binary not available here")
-    os.makedirs(tmp_path / "geometry")
-    os.symlink(os.path.join(src, "geometry", "killeroo.pbrt"), tmp_path / "geometry" / "killeroo.pbrt")
-    s = open(os.path.join(src, "killeroo-simple.pbrt")).read()
-    s = s.replace('"integer xresolution" [700] "integer yresolution" [700]', '"integer xresolution" [100] "integer yresolution" [100]').replace("killeroo-simple.exr", "kroo.pfm")
-    scene_file = str(tmp_path / "kroo.pbrt")
-    open(scene_file, "w").write(s)
-    out = str(tmp_path / "ref.pfm")
-    oracle.run_reference(scene_file, out, nthreads=4)
+    repository's front end + oracle produce bit-identical images."""
+    scene_file = killeroo_scene(tmp_path, 100)
     scene = pkg.HostScene(scene_file)
     assert scene.desc.n_tris == 2 * 33264 + 4 + 1 and scene.desc.n_spheres == 1
-    img, _ = oracle.render_image(scene)
-    assert np.array_equal(img, pkg.read_pfm(out))
+    check_killeroo(pkg, oracle, tmp_path, scene_file, "killeroo_simple_100")
 
 
 def test_killeroo_geometry_live_when_reference_present(pkg, oracle, tmp_path):
     """BASELINE.json config 0's scene (scenes/killeroo-simple.pbrt: two Loop-subdivided killeroos, 66 532 triangles, plastic,
-    uv'd planes) with its sphere light swapped for an emissive quad -- spheres are outside the closed set.  The scene data
-    belongs to the reference, so it is read from /root/reference where that exists (build container only) and rendered both
+    uv'd planes) with its sphere light swapped for an emissive quad -- spheres are outside the closed set -- rendered
     by the unmodified reference and by this repository's front end + oracle: the images must be bit-identical."""
-    src = "/root/reference/scenes"
-    if not os.path.exists(os.path.join(src, "killeroo-simple.pbrt")) or not os.path.exists(oracle.REF_BINARY):
-        pytest.skip("reference scenes / binary not available here")
-    os.makedirs(tmp_path / "geometry")
-    os.symlink(os.path.join(src, "geometry", "killeroo.pbrt"), tmp_path / "geometry" / "killeroo.pbrt")
-    s = open(os.path.join(src, "killeroo-simple.pbrt")).read()
-    s = (s.replace('"integer xresolution" [700] "integer yresolution" [700]', '"integer xresolution" [64] "integer yresolution" [64]')
-          .replace("killeroo-simple.exr", "kroo.pfm").replace('"integer pixelsamples" [8]', '"integer pixelsamples" [2]')
-          .replace('Shape "sphere" "float radius" [3]', 'Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [ -3 -3 0  3 -3 0  3 3 0  -3 3 0 ]')
-          .replace('"integer nsamples" [8]', '"integer nsamples" [8] "bool twosided" "true"'))
-    scene_file = str(tmp_path / "kroo.pbrt")
-    open(scene_file, "w").write(s)
-    out = str(tmp_path / "ref.pfm")
-    oracle.run_reference(scene_file, out, nthreads=4)
+    scene_file = killeroo_scene(tmp_path, 64, quad_light=True)
     scene = pkg.HostScene(scene_file)
     assert scene.desc.n_tris == 2 * 33264 + 4 + 2
-    img, _ = oracle.render_image(scene)
-    assert np.array_equal(img, pkg.read_pfm(out))
+    check_killeroo(pkg, oracle, tmp_path, scene_file, "killeroo_quad_light_64")
 
 
 def test_fuzz_scenes_live_when_reference_present(pkg, oracle, tmp_path):

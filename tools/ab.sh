@@ -7,7 +7,7 @@ ARGS=${BENCH_ARGS:---steps 1 --warmup 1 --spp 8 --no-cpu-baseline}
 i=0
 for CFG in "$@"; do
   i=$((i+1))
-  env $CFG timeout 300 python bench.py $ARGS > $OUT/ab$i.json 2> $OUT/ab$i.err
+  env $CFG timeout 300 python bench.py --full $ARGS > $OUT/ab$i.json 2> $OUT/ab$i.err
   python - "$CFG" $OUT/ab$i.json <<'PY'
 import json, sys
 try:
