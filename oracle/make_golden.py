@@ -373,6 +373,23 @@ def with_instances(s):
     return s[:i] + inst + s[j:]
 
 
+def with_projective(s, rows=((2e-4, -1e-4, 1.5e-4), (-3e-4, 2e-4, 1e-4), (4e-4, 3e-4, -2e-4))):
+    """with_instances' scene with a PROJECTIVE transform on one instance each of "boxes" (a BVHAccel object), "ball" (a lone sphere) and "tri" (a lone
+    triangle): `ConcatTransform` of the identity with last row (a, b, c, 1) -- file positions 3, 7, 11, 15, the file is column-major -- after the
+    instance's usual CTM, so Transform::operator()(Point3f) divides by a weight wp = a x + b y + c z + 1 that varies over the object (between 0.45 and 1.3
+    for world points as far as 20 % outside the room) and is nowhere near 0.  The reference renders these without a
+    warning.  The identity, affine and mirrored instances stay beside them."""
+    n = 0
+    for (a, b, c), old in zip(rows, ('  Scale 0.45 0.45 0.45\n  ObjectInstance "boxes"\n', '  Translate 120 0 420\n  ObjectInstance "ball"\n',
+                                     '  Rotate -30 0 1 0\n  ObjectInstance "tri"\n')):
+        head, inst = old.rsplit("  ObjectInstance", 1)
+        assert s.count(old) == 1
+        s = s.replace(old, head + f"  ConcatTransform [ 1 0 0 {a:g}  0 1 0 {b:g}  0 0 1 {c:g}  0 0 0 1 ]\n  ObjectInstance" + inst)
+        n += 1
+    assert n == 3 and s.count("ConcatTransform") == 3
+    return s
+
+
 def with_normals(s, tangents=False, uv=False):
     """Give both Cornell boxes smooth-ish per-vertex normals (outward from the box centre, one of them zero), optionally
     tangents and a uv parameterisation."""
@@ -694,6 +711,12 @@ SCENES = {
     # identity; a one-primitive object (no accelerator) holding a sphere; materials bound inside the definition
     "instance_boxes": cornell(40, 40, 8, integrator='Integrator "path" "integer maxdepth" [ 6 ]', world_edit=lambda s: with_instances(s)),
     "instance_accel": cornell(32, 32, 8, world_edit=lambda s: with_instances(s)).replace('WorldBegin', 'Accelerator "bvh" "integer maxnodeprims" [ 3 ] "string splitmethod" "middle"\nWorldBegin'),
+    # instances under PROJECTIVE transforms (row 3 of WorldToInstance is not (0, 0, 0, 1): Transform::operator()(Point3f, Vector3f *) ends in Point3 / wp,
+    # i.e. in products with ONE reciprocal, transform.h:299 / geometry.h Point3::operator/): a BVH object, a lone sphere and a lone triangle; with moving
+    # shapes inside the definitions (the still projective instance is entered once and derived again when the inner TransformedPrimitive is left); volpath
+    "instance_projective": cornell(40, 40, 8, integrator='Integrator "path" "integer maxdepth" [ 6 ]', world_edit=lambda s: with_projective(with_instances(s))),
+    "nest_motion_projective": with_nested_motion(with_projective(with_instances(cornell(40, 32, 8)))),
+    "vol_instance_projective": cornell(32, 32, 4, integrator='Integrator "volpath" "integer maxdepth" [ 5 ]', world_edit=lambda s: with_fog(with_projective(with_instances(s)))),
     # Shape "cylinder" and "disk" (cylinder.cpp, disk.cpp): as geometry (partial sweeps, annulus, non-uniform transforms,
     # reversed orientation) and as area-light shapes (Shape::Sample / Shape::Pdf over their Sample(u))
     "quadrics": cornell(32, 32, 8, integrator='Integrator "path" "integer maxdepth" [ 6 ]', world_edit=lambda s: s.replace(

@@ -514,7 +514,7 @@ __global__ __launch_bounds__(TR_BLOCK, ((XP == XP_INST || XP == (XP_INST | XP_AL
                             oErr = mk(ab[0], ab[1], ab[2]) * pgamma(3);
                             dd = mk(dp[0], dp[1], dp[2]);
                             if (wp == 1) o = mk(op[0], op[1], op[2]);
-                            else { o.x = op[0] / wp; PG_SCHED_BARRIER(); o.y = op[1] / wp; PG_SCHED_BARRIER(); o.z = op[2] / wp; }
+                            else { const float inv = 1.f / wp; o = mk(op[0] * inv, op[1] * inv, op[2] * inv); }  // Point3::operator/: one reciprocal, three products
                         }
                         const float lengthSquared = lensq(dd);
                         if (lengthSquared > 0) {

@@ -2,6 +2,7 @@
 (kernels, queues, wave-level code and host orchestration included; tests/emu/README.md), loaded through PBRT_GPU_LIB, and the GPU test
 files run unchanged in a child pytest.  A subset runs in the normal CPU suite; PBRT_EMULATE_ALL=1 runs everything that is feasible
 under emulation (about a quarter of an hour)."""
+import importlib.util
 import os
 import shutil
 import subprocess
@@ -30,7 +31,8 @@ def run_gpu_tests(lib, files, select, timeout):
     env = dict(os.environ, PBRT_GPU_LIB=lib, PBRT_EMULATED_DEVICE="1")
     # (several tests selected: three worker processes -- the emulated device is host code, the tests are independent; PBRT_EMULATE_WORKERS=0: serial)
     workers = os.environ.get("PBRT_EMULATE_WORKERS", "3")
-    par = ["-n", workers] if workers != "0" and not any("::" in f for f in files) else []
+    have_xdist = importlib.util.find_spec("xdist") is not None  # (without pytest-xdist: the same tests, one after the other)
+    par = ["-n", workers] if have_xdist and workers != "0" and not any("::" in f for f in files) else []
     p = subprocess.run([sys.executable, "-m", "pytest", *files, "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", *par, "-k", select], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=timeout)
     tail = p.stdout[-3000:] + p.stderr[-1500:]
@@ -121,6 +123,16 @@ def test_moving_shapes_inside_object_definitions_on_the_emulated_device(emulated
     assert "2 passed" in out and "failed" not in out
     out = run_gpu_tests(emulated, ["tests/test_gpu_fuzz.py::test_random_scene_with_moving_shapes_inside_object_definitions[1]"], "inside_object", 1500)
     assert "1 passed" in out and "failed" not in out
+
+
+def test_projective_instances_on_the_emulated_device(emulated):
+    """Instances whose WorldToInstance has a last row other than (0, 0, 0, 1): k_trace's entry step divides the carried origin by the homogeneous weight as
+    Point3::operator/ does (one reciprocal, three products) -- a BVH object, a lone sphere and a lone triangle, with moving shapes inside the definitions
+    (the nested exit derives the instance's ray again), under volpath: the three goldens of the reference binary, 20 000 ray queries on two of them, six random scenes."""
+    out = run_gpu_tests(emulated, ["tests/test_gpu_parity.py"], "(test_golden_images or test_instance_rays_bit_exact) and projective", 1500)
+    assert "5 passed" in out and "failed" not in out
+    out = run_gpu_tests(emulated, ["tests/test_gpu_fuzz.py"], " or ".join("test_random_scene_with_projective_transforms[%d]" % i for i in range(6)), 1500)
+    assert "6 passed" in out and "failed" not in out
 
 
 def test_material_pass_on_the_emulated_device(emulated):

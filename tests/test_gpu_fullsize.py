@@ -79,7 +79,7 @@ def test_million_triangle_rays_bit_exact_vs_oracle(gpu, oracle, synthetic_dir):
     gs.close()
 
 
-def test_config3_full_size_properties(gpu, synthetic_dir):
+def test_config3_full_size_properties(gpu, synthetic_dir, monkeypatch):
     """BASELINE.json config 3 itself: 1920x1080 @ 64 spp on the 999 710-triangle scene."""
     xres, yres, spp = 1920, 1080, 64
     scene = gpu.HostScene(text=scene_text(synthetic_dir, xres, yres, spp))
@@ -99,6 +99,20 @@ def test_config3_full_size_properties(gpu, synthetic_dir):
     # determinism: a second render is bit-identical
     film2, strays2 = gs.render(rd)
     assert np.array_equal(film["rgb"], film2["rgb"]) and len(strays) == len(strays2)
+    # the frame the benchmark reports: shadow rays in the product's free order, each bounce's any-hit launch on a second stream beside the
+    # next closest-hit launch -- the same film and strays to the last bit, the same rays
+    monkeypatch.delenv("PG_ANYHIT_ORDER", raising=False)
+    gf = gpu.GpuScene(scene.desc)
+    gf.set_option(gpu.abi.PG_OPT_OVERLAP_SHADOW, 1)
+    film3, strays3 = gf.render(rd)
+    cn3 = gf.counters()
+    gf.close()
+    assert np.array_equal(film["rgb"], film3["rgb"]) and np.array_equal(film["weight"], film3["weight"])
+    key = lambda s: np.lexsort((s["src_px"], s["src_py"], s["px"], s["py"]))
+    a, b = strays[key(strays)], strays3[key(strays3)]
+    assert len(a) == len(b) and all(np.array_equal(a[f], b[f]) for f in ("px", "py", "src_px", "src_py", "weight", "rgb"))
+    for k in ("camera_rays", "closest_rays", "shadow_rays"):
+        assert cn3[k] == cn[k], (k, cn3[k], cn[k])
     # tile sharding (the multi-GPU decomposition) does not change a single bit
     scene.film_clear()
     for r in range(3):
@@ -111,6 +125,81 @@ def test_config3_full_size_properties(gpu, synthetic_dir):
     scene2 = gpu.HostScene(text=scene_text(synthetic_dir, xres, yres, spp, light_scale=2))
     img2, _ = gpu.render_scene(scene2)
     assert np.array_equal(img2, whole * np.float32(2))
+
+
+FRAME_COUNTERS = ("camera_rays", "closest_rays", "shadow_rays", "mis_rays", "shade_items", "closest_node_visits", "closest_tri_tests", "light_tri_tests")
+
+
+@pytest.fixture(scope="module")
+def bench_like_frame(gpu, tmp_path_factory):
+    """A frame whose launches are long enough to coexist on the chip (19 612 triangles, 480x270 @ 8 spp: over a million paths per bounce; a 32x32
+    golden's kernels end before the next one starts) and what it must be: the render with one stream, shadow rays in the reference's order."""
+    import gen_synthetic
+    d = tmp_path_factory.mktemp("synthetic_n100")
+    gen_synthetic.write_scene(str(d / "frame.pbrt"), n=100, xres=480, yres=270, spp=8, filename="frame.pfm")
+    scene = gpu.HostScene(str(d / "frame.pbrt"))
+    saved = os.environ.get("PG_ANYHIT_ORDER")
+    os.environ["PG_ANYHIT_ORDER"] = "reference"
+    try:
+        gs = gpu.GpuScene(scene.desc)
+    finally:
+        if saved is None: del os.environ["PG_ANYHIT_ORDER"]
+        else: os.environ["PG_ANYHIT_ORDER"] = saved
+    gs.set_option(gpu.abi.PG_OPT_OVERLAP_SHADOW, 0)
+    film, strays = gs.render(scene.render_desc())
+    cn = gs.counters()
+    gs.close()
+    print(f"bench-like frame, serial: any-hit launches {cn['shadow_ms']:.3f} ms and closest-hit launches {cn['closest_ms']:.3f} ms over the frame's bounces, {cn['shadow_rays']} shadow rays")
+    return scene, film, len(strays), cn
+
+
+@pytest.mark.parametrize("batch_paths", [None, 4096])
+def test_bench_frame_sequence_overlapped_into_device_buffers(gpu, bench_like_frame, monkeypatch, batch_paths):
+    """What bench.py times, looked at: ONE scene in the product's default shadow-ray order with PG_OPT_OVERLAP_SHADOW 1 (each bounce's any-hit launch on a
+    second stream beside the next closest-hit launch), three frames enqueued back to back on torch's current stream into two alternating device
+    buffers with no host synchronisation between them, then the option toggled to 0 for one frame and back to 1 for one more.  Every frame's film,
+    stray count and counters equal the serial reference-order render's.  (A copy of each frame's buffer is enqueued behind it on the same stream, so
+    it sees what a consumer ordered behind pg_render sees.)  Once more with PG_BATCH_PATHS=4096: a frame is then hundreds of batches, and the second
+    stream is joined at every batch boundary."""
+    import torch
+    from pbrt_v3_amd import distributed as pdist
+    scene, film, n_strays, cn = bench_like_frame
+    monkeypatch.delenv("PG_ANYHIT_ORDER", raising=False)
+    if batch_paths: monkeypatch.setenv("PG_BATCH_PATHS", str(batch_paths))
+    gs = gpu.GpuScene(scene.desc)
+    gs.set_option(gpu.abi.PG_OPT_OVERLAP_SHADOW, 1)
+    rd = scene.render_desc()
+    n_tiles = gs.tile_count(rd)
+    bufs = [pdist.ShardBuffer(n_tiles, torch.device("cuda", 0), rd.tile_pixels) for _ in range(2)]
+    assert n_strays <= bufs[0].max_strays
+    copies = []
+
+    def frames(n):
+        """n frames enqueued, one synchronisation after the last; the counters they added."""
+        gs.counters_reset()
+        stream = torch.cuda.current_stream().cuda_stream
+        for _ in range(n):
+            b = bufs[len(copies) % 2]
+            gs.render_device(rd, b.film.data_ptr(), b.strays.data_ptr(), b.max_strays, b.nstrays.data_ptr(), stream=stream)
+            copies.append(b.words.clone())
+        torch.cuda.synchronize()
+        return gs.counters()
+
+    added = [(3, frames(3))]
+    gs.set_option(gpu.abi.PG_OPT_OVERLAP_SHADOW, 0)
+    added.append((1, frames(1)))
+    gs.set_option(gpu.abi.PG_OPT_OVERLAP_SHADOW, 1)
+    added.append((1, frames(1)))
+    gs.close()
+    assert len(copies) == 5
+    for i, words in enumerate(copies):
+        f, _, n = bufs[0].views_of(words)
+        f = np.ascontiguousarray(f.cpu().numpy()[:n_tiles * rd.tile_pixels]).view(gpu.FILM_PIXEL_DTYPE).reshape(-1)
+        assert np.array_equal(f["rgb"], film["rgb"]) and np.array_equal(f["weight"], film["weight"]), f"frame {i}: {(f['rgb'] != film['rgb']).any(axis=1).sum()} film pixels differ"
+        assert n == n_strays, (i, n, n_strays)
+    for n, c in added:
+        for k in FRAME_COUNTERS:
+            assert c[k] == n * cn[k], (n, k, c[k], cn[k])
 
 
 def test_config2_cornell_quarter_size_vs_reference(gpu):

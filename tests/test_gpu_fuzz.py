@@ -370,6 +370,114 @@ def test_random_scene_with_moving_shapes_inside_object_definitions(gpu, oracle, 
     check_scene(gpu, oracle, random_scene_nested_motion(seed), seed)
 
 
+def directive_matrix(lines):
+    """The CTM that Translate / Rotate / Scale directives build from the identity (each post-multiplies, api.cpp:405-460), in numpy."""
+    m = np.eye(4)
+    for l in lines:
+        w = l.split()
+        if not w or w[0] not in ("Translate", "Rotate", "Scale"): continue
+        v = [float(x) for x in w[1:]]
+        t = np.eye(4)
+        if w[0] == "Translate": t[:3, 3] = v
+        elif w[0] == "Scale": t[:3, :3] = np.diag(v)
+        else:  # transform.cpp:127-155
+            a, th = np.array(v[1:]) / np.linalg.norm(v[1:]), np.radians(v[0])
+            K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+            t[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+        m = m @ t
+    return m
+
+
+def random_scene_projective(seed, report=None):
+    """The extended, volumetric and nested-motion random scenes with PROJECTIVE transforms: every second still ObjectInstance block gets
+    `ConcatTransform` of the identity with a random last row (a, b, c, 1) after its CTM (a moving block stays as it is -- AnimatedTransform's decomposition
+    drops the row -- and a still projective instance of the same object is added beside it), and every third scene also has a plain sphere and a plain
+    triangle mesh under such a CTM (the front end's vertex transform, the sphere's own ObjectToWorld).  No light is declared under one of them.
+
+    The condition on the inputs: a ray origin whose homogeneous weight is 0 gives infinities, which is not this test's subject.  For every projective
+    CTM = M C emitted here, WorldToInstance = C^-1 M^-1 has row 3 r3 = (-a, -b, -c, 1) M^-1, formed below in numpy from the directives alone; the weight
+    w = r3 . (x, 1) is affine in x, so its extremes over a box are at the corners.  The box is the one check_scene draws its ray origins from -- the scene
+    bound grown by 20 % per side -- joined with the camera's positions; (a, b, c) shrinks until 0.25 <= w <= 4 at all eight corners, which is asserted.
+    `report`: a dict that receives the rows, the weights' range and the scene extent (the CPU suite checks that the rows did not shrink to nothing)."""
+    from __graft_entry__ import load_package
+    rng = np.random.default_rng(8000 + seed)
+    text = (random_scene_ext, random_scene_vol, random_scene_nested_motion)[seed % 3](seed // 3)
+    block = lambda name: ["Translate %.6g %.6g %.6g" % tuple(rng.normal(size=3) * 1.5), "Rotate %.6g %.6g %.6g %.6g" % (360 * rng.random(), *(rng.normal(size=3) + np.array([0, 1e-3, 0]))),
+                          "Scale %.6g %.6g %.6g" % tuple(0.5 + rng.random(3))]
+    sites, added = [], []  # a site: the CTM before the ConcatTransform and the row's direction; "@PROJ<i>@" stands for its directive in the text
+    def site(ctm_lines):
+        sites.append({"M": directive_matrix(ctm_lines), "abc": rng.normal(size=3) * 0.4, "shrink": 1.0})
+        return " @PROJ%d@" % (len(sites) - 1)
+    chunks = text.split("AttributeBegin\n")
+    n_inst = 0
+    for k in range(1, len(chunks)):
+        body, rest = chunks[k].split("AttributeEnd", 1)
+        if "ObjectInstance" not in body or "LightSource" in body: continue
+        n_inst += 1
+        if n_inst % 2 == 0: continue
+        lines = body.split("\n")
+        at = next(i for i, l in enumerate(lines) if l.lstrip().startswith("ObjectInstance "))
+        if "ActiveTransform" in body:
+            ctm = block(None)
+            added.append("AttributeBegin\n " + "\n ".join(ctm) + "\n" + site(ctm) + "\n" + lines[at] + "\nAttributeEnd")
+        else:
+            chunks[k] = "\n".join(lines[:at] + [site(lines[:at])] + lines[at:]) + "AttributeEnd" + rest
+    text = "AttributeBegin\n".join(chunks)
+    if (seed + seed // 3) % 3 == 0:
+        ctm = block(None)
+        added.append("AttributeBegin\n " + "\n ".join(ctm) + "\n" + site(ctm) + '\n Material "plastic" "rgb Kd" [ 0.3 0.5 0.2 ]\n Shape "sphere" "float radius" [ %.4g ]\nAttributeEnd' % (0.4 + 0.4 * rng.random()))
+        ctm = block(None)
+        nt = int(rng.integers(1, 6))
+        added.append("AttributeBegin\n " + "\n ".join(ctm) + "\n" + site(ctm) + '\n Material "matte" "rgb Kd" [ 0.6 0.3 0.3 ]\n Shape "trianglemesh" "integer indices" [ %s ] "point P" [ %s ]\nAttributeEnd'
+                     % (" ".join(map(str, range(3 * nt))), " ".join("%.9g" % x for x in (rng.normal(size=(nt, 3, 3)) * 0.6).astype(np.float32).ravel())))
+    assert sites, "no projective transform in this scene"
+    text = text.replace("WorldEnd\n", "\n".join(added + ["WorldEnd"]) + "\n")
+    # the camera's positions: LookAt's eye; under a moving camera the end transform's translation displaces it by at most its length; the lens
+    eye = np.array([float(x) for x in re.search(r"LookAt (\S+) (\S+) (\S+)", text).groups()])
+    head = text.split("Camera ", 1)[0]
+    pad = 0.05 + (np.linalg.norm([float(x) for x in re.search(r"Translate (\S+) (\S+) (\S+)", head.split("ActiveTransform EndTime", 1)[1]).groups()]) if "ActiveTransform EndTime" in head else 0.0)
+    pkg = load_package()
+    for _ in range(400):
+        out = text
+        for i, s in enumerate(sites):
+            a, b, c = (float(np.float32(x)) for x in s["abc"] * s["shrink"])
+            s["row"] = np.array([a, b, c])
+            out = out.replace("@PROJ%d@" % i, "ConcatTransform [ 1 0 0 %.9g  0 1 0 %.9g  0 0 1 %.9g  0 0 0 1 ]" % (a, b, c))
+        scene = pkg.HostScene(text=out)  # (only the bound comes from the front end: it moves with the rows)
+        nodes = scene.nodes()
+        lo, hi = nodes["bmin"][0].astype(np.float64), nodes["bmax"][0].astype(np.float64)
+        scene.close()
+        lo, hi = np.minimum(lo - 0.2 * (hi - lo), eye - pad), np.maximum(hi + 0.2 * (hi - lo), eye + pad)
+        corners = np.array([[(lo, hi)[(j >> a) & 1][a] for a in range(3)] + [1.0] for j in range(8)])
+        ok = True
+        for s in sites:
+            s["r3"] = np.array([*(-s["row"]), 1.0]) @ np.linalg.inv(s["M"])
+            s["w"] = corners @ s["r3"]
+            if not (s["w"].min() >= 0.25 and s["w"].max() <= 4):
+                s["shrink"] *= 0.8
+                ok = False
+        if ok: break
+    for s in sites:
+        assert 0.25 <= s["w"].min() and s["w"].max() <= 4, (seed, s["w"])
+    if report is not None:
+        report.update(r3=[s["r3"] for s in sites], w=(min(s["w"].min() for s in sites), max(s["w"].max() for s in sites)), extent=float((hi - lo).max()), n_sites=len(sites))
+    return out
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_random_scene_with_projective_transforms(gpu, oracle, seed):
+    """Instances, a sphere and a mesh under transforms whose last row is not (0, 0, 0, 1): film, strays and every counter against the oracle, the free-order
+    render, and 4096 ray queries both ways.  The weights stay within [0.25, 4] wherever a ray starts (random_scene_projective asserts it)."""
+    info = {}
+    text = random_scene_projective(seed, info)
+    scene = gpu.HostScene(text=text)
+    rows = sorted(tuple(np.float32(scene.desc.instances[i].w2i[12:16])) for i in range(scene.desc.n_instances) if tuple(scene.desc.instances[i].w2i[12:16]) != (0.0, 0.0, 0.0, 1.0))
+    assert rows, "no instance of this scene is projective"
+    for r in rows:  # the rows the condition was computed for are the rows the front end made (float32 inverse against numpy's: a few ulps of the largest entry)
+        assert min(np.abs(np.asarray(r, np.float64) - q).max() for q in info["r3"]) <= 1e-4 * np.abs(r).max(), r
+    check_scene(gpu, oracle, text, seed)
+
+
 def random_scene_nested_motion_sss_grid(seed):
     """Moving shapes inside object definitions beside subsurface materials (the probe chains' hits lie under two transforms: k_sss_probe<., ., NEST>, k_sss_exit), a
     GridDensityMedium (both shading phases around the transmittance rays), or both; every other scene with moving / rotating instances around them."""

@@ -152,13 +152,27 @@ def test_alpha_mask_rays_bit_exact(gpu, oracle):
     gs.close()
 
 
-@pytest.mark.parametrize("name", ["instance_boxes", "instance_accel"])
+def projective_instances(scene):
+    """How many of the scene's instances have a WorldToInstance whose row 3 is not (0, 0, 0, 1)."""
+    d = scene.desc
+    return sum(1 for i in range(d.n_instances) if tuple(d.instances[i].w2i[12:16]) != (0.0, 0.0, 0.0, 1.0))
+
+
+# per scene: the least number of instances, the number of objects (a moving shape inside one of nest_motion_projective's definitions is an instance of an
+# object of its own), the least number of projective instances
+INSTANCE_SCENES = {"instance_boxes": (7, 3, 0), "instance_accel": (7, 3, 0), "instance_projective": (7, 3, 3), "nest_motion_projective": (10, 6, 3)}
+
+
+@pytest.mark.parametrize("name", list(INSTANCE_SCENES))
 def test_instance_rays_bit_exact(gpu, oracle, name):
     """Object instances (TransformedPrimitive over an object definition's own BVH, or over a lone primitive): the ray is
     carried into instance space, traverses the second-level BVH and comes back with r.tMax = the instance-space tHit --
-    primitive, t, barycentrics and the node-visit / triangle-test counters equal the oracle's for every ray."""
+    primitive, t, barycentrics and the node-visit / triangle-test counters equal the oracle's for every ray.  The "_projective"
+    scenes: three of the instances divide the carried origin by a homogeneous weight that varies from ray to ray."""
     scene = gpu.HostScene(os.path.join(GOLD, name + ".pbrt"))
-    assert scene.desc.n_instances >= 7 and scene.desc.n_objects == 3 and scene.desc.n_prims_all > scene.desc.n_tris
+    n_inst, n_obj, n_proj = INSTANCE_SCENES[name]
+    assert scene.desc.n_instances >= n_inst and scene.desc.n_objects == n_obj and scene.desc.n_prims_all > scene.desc.n_tris
+    assert projective_instances(scene) >= n_proj and (n_proj > 0 or projective_instances(scene) == 0)
     gs = gpu.GpuScene(scene.desc)
     n = 20000
     o, d = random_rays(scene, n, 123)

@@ -340,3 +340,25 @@ def test_features_of_the_reference_outside_the_closed_set_refuse_the_frame(pkg):
     s = pkg.HostScene(text=mini.replace("WorldEnd", 'AttributeBegin\nMaterial "velvet"\n' + tri + 'Shape "teapot"\nTexture "t" "float" "plaid"\nAttributeEnd\nWorldEnd'))
     assert pkg.host_lib().pbrt_host_error_count() == before and s.desc.n_tris >= 1
     s.close()
+
+
+def test_projective_fuzz_scenes_keep_their_weights_away_from_zero(pkg):
+    """tests/test_gpu_fuzz.py random_scene_projective: for all 40 seeds of the GPU test the homogeneous weight of every projective WorldToInstance stays within
+    [0.25, 4] over the box the rays start in (the generator asserts it), and the rows have not shrunk to nothing on the way: the largest entry of a row,
+    times the extent of that box, is far above rounding (> 1e-3; a weight then varies by more than a thousand ulps across the scene)."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("fuzz_scenes", os.path.join(os.path.dirname(__file__), "test_gpu_fuzz.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    shapes = 0
+    for seed in range(40):
+        info = {}
+        text = fz.random_scene_projective(seed, info)
+        assert 0.25 <= info["w"][0] and info["w"][1] <= 4
+        assert text.count("ConcatTransform") == info["n_sites"] >= 1
+        assert max(np.abs(r[:3]).max() for r in info["r3"]) * info["extent"] > 1e-3, seed
+        lights = [b for b in text.split("AttributeBegin")[1:] if "LightSource" in b.split("AttributeEnd")[0]]
+        assert not any("ConcatTransform" in b.split("AttributeEnd")[0] for b in lights)
+        shapes += text.count("ConcatTransform") - sum("ConcatTransform" in b.split("AttributeEnd")[0] and "ObjectInstance" in b.split("AttributeEnd")[0] for b in text.split("AttributeBegin")[1:])
+    assert shapes >= 2 * (40 // 3)  # a sphere and a mesh of their own under a projective CTM in every third scene
