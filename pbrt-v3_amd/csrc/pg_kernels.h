@@ -33,6 +33,7 @@ struct DObject { float box[6]; int rootRef; int firstPrim; int nNodes; int pad; 
 // instance or a projective matrix goes through PgInstance as before.
 struct DInstEntry { float w2i[12]; float box[6]; int rootRef; int firstPrim; int nNodes; int affineStill; int pad[2]; };
 #define TR_NO_ROOT 0x7fffffff
+#define TR_STACK_TOTAL 64  // k_trace's stack entries behind the LDS part (pg_traverse.hip); pg_scene_prep.h refuses BVHs that need more
 
 // One tile's sampler when the sampler draws from one RNG stream per tile (PgSamplerKind 2 .. 5): the tile's PCG32 state
 // (core/rng.h:61-144), PixelSampler's current1DDimension / current2DDimension / currentPixelSampleIndex (sampler.cpp:100-134),

@@ -41,7 +41,6 @@
 #define TR_BLOCK 256
 #endif
 #define TR_NONE ((int)0x80000000)
-#define TR_STACK_TOTAL 64
 // 256-thread blocks resident per CU = min(8, floor(800 / (ceil(sgpr/16)*16 + 16))) (MI355X_MICROARCH.md): 106 SGPRs admit 6,
 // <= 96 admit 7.  The cap makes the compiler keep the excess in VGPR lanes (measured: +2.5 % whole-frame).
 #ifndef TR_SGPR_ATTR

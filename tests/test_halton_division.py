@@ -1,4 +1,4 @@
-"""The Halton digit loops of the shading kernels divide by multiplying (DScene::haltonDims, pbrt-v3_amd/csrc/pg_abi.hip):
+"""The Halton digit loops of the shading kernels divide by multiplying (DScene::haltonDims, built by pgPrepSamplerTables, pbrt-v3_amd/csrc/pg_scene_prep.h):
 floor(a / base) = (t + ((a - t) >> 1)) >> (L - 1) with t = mulhi(m, a), L = ceil(log2 base), m = floor(2^32 (2^L - base) / base) + 1.
 The kernels rely on this being exact for EVERY 32-bit a and every prime base of the sampler's table (the first 1000 primes,
 lowdiscrepancy.h:50-51); this test checks the identity in 32-bit arithmetic as the device evaluates it."""
