@@ -19,6 +19,7 @@
 #include "pg_device.h"
 #include "pg_kernels.h"
 #include "pg_scene_prep.h"
+#include "pg_render_check.h"
 
 static thread_local std::string g_lastError;
 static int setError(int code, const char *fmt, ...) {
@@ -280,15 +281,9 @@ static int withExactFallback(PgScene *s, const std::function<int()> &call) {
     return st;
 }
 
-static int tileCount(const PgRenderDesc *rd) {
-    int nx = (rd->sample_bounds[2] - rd->sample_bounds[0] + 15) / 16, ny = (rd->sample_bounds[3] - rd->sample_bounds[1] + 15) / 16;
-    if (nx <= 0 || ny <= 0 || rd->tile_step <= 0 || rd->tile_first < 0) return 0;
-    int total = nx * ny;
-    return rd->tile_first >= total ? 0 : (total - rd->tile_first + rd->tile_step - 1) / rd->tile_step;
-}
 int pg_render_tile_count(const PgRenderDesc *desc) {
     if (!desc) return setError(PG_ERR_INVALID, "pg_render_tile_count: null argument");
-    return tileCount(desc);
+    return pgTileCount(desc);
 }
 
 // Queue geometry for a batch of `capacity` path slots: PG_REGIONS regions of regionCap entries (multiple of 256) such
@@ -298,9 +293,13 @@ static int regionCapFor(int capacity, bool slack = false) {
     int nblk = (capacity + 255) / 256;
     return ((nblk + PG_REGIONS - 1) / PG_REGIONS) * 256 * (slack ? 2 : 1);
 }
-static int ensureWorkBuffers(PgScene *s, int capacity) {
+// Entries of one queue -- and of every per-entry work buffer -- for a frame of `capacity` path slots (>= capacity); asked once per frame
+static size_t queueEntries(const PgScene *s, int capacity) { return (size_t)regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS; }
+static const int QSTRIDE = PG_REGIONS * PG_COUNT_STRIDE;  // ints of counter storage per queue
+
+// The four groups of work buffers: each grows when its capacity field says so (n = queueEntries(s, capacity)); the last three fill the kernels' view
+static int ensureWorkBuffers(PgScene *s, int capacity, size_t n) {
     if (s->capacity >= capacity) return PG_OK;
-    const size_t n = (size_t)regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS;  // >= capacity
     if (s->d.sparseLights) HIP_TRY(s->retryList.alloc(n * sizeof(int)));
     // (scenes with moving instances: one float per entry behind `d`, the rays' times: PG_QUEUE_TIMES)
     for (int i = 0; i < 4; ++i) { HIP_TRY(s->qo[i].alloc(n * sizeof(float4))); HIP_TRY(s->qd[i].alloc(n * (sizeof(float4) + (s->d.hasMotion ? sizeof(float) : 0)))); }
@@ -330,14 +329,67 @@ static int ensureWorkBuffers(PgScene *s, int capacity) {
         s->d.nestXfOff = (int)(hitParts * n);
     }  // main-queue hits, then MIS-queue hits at offset n (one launch fills both)
     HIP_TRY(s->occluded.alloc(n * sizeof(int)));
-    HIP_TRY(s->stL.alloc(n * sizeof(float4)));
-    HIP_TRY(s->stBeta.alloc(n * sizeof(float4)));
-    HIP_TRY(s->stMeta.alloc(n * sizeof(int4)));
-    HIP_TRY(s->pdLight.alloc(n * sizeof(float4)));
-    HIP_TRY(s->pdMis.alloc(n * sizeof(float4)));
-    HIP_TRY(s->pdBeta.alloc(n * sizeof(float4)));
-    HIP_TRY(s->pdInfo.alloc(n * sizeof(int4)));
+    HIP_TRY(s->stL.alloc(n * sizeof(float4))); HIP_TRY(s->stBeta.alloc(n * sizeof(float4))); HIP_TRY(s->stMeta.alloc(n * sizeof(int4)));
+    HIP_TRY(s->pdLight.alloc(n * sizeof(float4))); HIP_TRY(s->pdMis.alloc(n * sizeof(float4))); HIP_TRY(s->pdBeta.alloc(n * sizeof(float4))); HIP_TRY(s->pdInfo.alloc(n * sizeof(int4)));
     s->capacity = capacity;
+    return PG_OK;
+}
+// VolPathIntegrator: the per-slot medium state, and in vq the second halves of the through-ray ping-pong (the first halves are q[2] and q[3])
+static int ensureVolBuffers(PgScene *s, int capacity, size_t n, VolState &vs, RayQueue vq[2]) {
+    if (s->volCapacity < capacity) {
+        for (int i = 0; i < 2; ++i) { HIP_TRY(s->vqo[i].alloc(n * sizeof(float4))); HIP_TRY(s->vqd[i].alloc(n * (sizeof(float4) + (s->d.hasMotion ? sizeof(float) : 0)))); HIP_TRY(s->trAcc[i].alloc(n * sizeof(float4))); }
+        for (int i = 0; i < 3; ++i) HIP_TRY(s->volP1[i].alloc(n * sizeof(float4)));
+        HIP_TRY(s->vCounts.alloc(2 * QSTRIDE * sizeof(int)));
+        HIP_TRY(s->volMedium.alloc(n * sizeof(int)));
+        HIP_TRY(s->misLi.alloc(n * sizeof(float4)));
+        HIP_TRY(s->pdLi.alloc(n * sizeof(float4)));
+        HIP_TRY(s->hitT.alloc((s->d.nGrids > 0 ? 3 : 2) * n * sizeof(float)));
+        s->volCapacity = capacity;
+    }
+    if (s->d.nGrids > 0 && s->gridVertex.bytes < n * sizeof(float4)) HIP_TRY(s->gridVertex.alloc(n * sizeof(float4)));
+    vs.medium = (int *)s->volMedium.p;
+    for (int i = 0; i < 2; ++i) vs.trAcc[i] = (float4 *)s->trAcc[i].p;
+    for (int i = 0; i < 3; ++i) vs.p1[i] = (float4 *)s->volP1[i].p;
+    vs.misLi = (float4 *)s->misLi.p; vs.pdLi = (float4 *)s->pdLi.p;
+    for (int i = 0; i < 2; ++i) { vq[i].o = (float4 *)s->vqo[i].p; vq[i].d = (float4 *)s->vqd[i].p; vq[i].counts = (int *)s->vCounts.p + i * QSTRIDE; }
+    return PG_OK;
+}
+// PathIntegrator, and VolPathIntegrator on scenes without BSSRDF materials or grid media (whose probe-chain / two-phase kernels find a
+// path's state by its slot): L / beta / meta (/ the ray's medium) in queue order beside each main queue.  (The kernels are compiled for one
+// or the other: k_shade's QSTATE.)
+static int ensureQueueState(PgScene *s, int capacity, size_t n, bool vol, PathState &ps) {
+    const bool volQ = vol && s->d.nBssrdfs == 0 && s->d.nGrids == 0;
+    if (vol && !volQ) return PG_OK;
+    if (s->qsCapacity < capacity) {
+        for (int i = 0; i < 2; ++i) { HIP_TRY(s->qsL[i].alloc(n * sizeof(float4))); HIP_TRY(s->qsBeta[i].alloc(n * sizeof(float4))); HIP_TRY(s->qsMeta[i].alloc(n * sizeof(int4))); }
+        s->qsCapacity = capacity;
+    }
+    if (volQ && s->qsMedium[0].bytes < n * sizeof(int)) for (int i = 0; i < 2; ++i) HIP_TRY(s->qsMedium[i].alloc(n * sizeof(int)));
+    for (int i = 0; i < 2; ++i) { ps.qs[i].L = (float4 *)s->qsL[i].p; ps.qs[i].beta = (float4 *)s->qsBeta[i].p; ps.qs[i].meta = (int4 *)s->qsMeta[i].p;
+                                  ps.qs[i].medium = volQ ? (int *)s->qsMedium[i].p : nullptr; }
+    return PG_OK;
+}
+// Subsurface scattering: per-slot state of the BSSRDF branch with its job queue, and in sssP the two probe queues
+static int ensureSssBuffers(PgScene *s, int capacity, size_t n, SssState &sq, RayQueue sssP[2]) {
+    if (s->sssCapacity < capacity) {
+        HIP_TRY(s->sssPo.alloc(n * sizeof(float4))); HIP_TRY(s->sssTarget.alloc(n * sizeof(float4))); HIP_TRY(s->sssCount.alloc(n * sizeof(int2)));
+        for (int i = 0; i < 3; ++i) HIP_TRY(s->sssFrame[i].alloc(n * sizeof(float4)));
+        for (int i = 0; i < 2; ++i) HIP_TRY(s->sssCoef[i].alloc(n * sizeof(float4)));
+        HIP_TRY(s->sssHit.alloc(n * sizeof(float4))); HIP_TRY(s->sssHitO.alloc(n * sizeof(float4))); HIP_TRY(s->sssHitD.alloc(n * sizeof(float4)));
+        HIP_TRY(s->sssHitInst.alloc(n * sizeof(int)));
+        if (s->d.hasMotion) HIP_TRY(s->sssHitXf.alloc((s->d.hasNest ? 2 : 1) * n * PG_XF_STRIDE * sizeof(float)));  // the chosen hit's interpolated instance matrices
+        HIP_TRY(s->sssMedium.alloc(n * sizeof(int2)));
+        for (int i = 0; i < 3; ++i) { HIP_TRY(s->sssQo[i].alloc(n * sizeof(float4))); HIP_TRY(s->sssQd[i].alloc(n * (sizeof(float4) + (s->d.hasMotion ? sizeof(float) : 0)))); }  // (+ the probe rays' times: PG_QUEUE_TIMES)
+        HIP_TRY(s->sssCounts.alloc(3 * QSTRIDE * sizeof(int)));
+        HIP_TRY(s->sssTail.alloc(QSTRIDE * sizeof(int)));
+        s->sssCapacity = capacity;
+    }
+    sq.po = (float4 *)s->sssPo.p; sq.target = (float4 *)s->sssTarget.p; sq.count = (int2 *)s->sssCount.p;
+    for (int i = 0; i < 3; ++i) sq.frame[i] = (float4 *)s->sssFrame[i].p;
+    for (int i = 0; i < 2; ++i) sq.coef[i] = (float4 *)s->sssCoef[i].p;
+    sq.hit = (float4 *)s->sssHit.p; sq.hitO = (float4 *)s->sssHitO.p; sq.hitD = (float4 *)s->sssHitD.p; sq.hitInst = (int *)s->sssHitInst.p; sq.hitXf = (float *)s->sssHitXf.p; sq.hitXfNest = (int)n; sq.medium = (int2 *)s->sssMedium.p;
+    sq.qjob.o = (float4 *)s->sssQo[0].p; sq.qjob.d = (float4 *)s->sssQd[0].p; sq.qjob.counts = (int *)s->sssCounts.p;
+    for (int i = 0; i < 2; ++i) { sssP[i].o = (float4 *)s->sssQo[1 + i].p; sssP[i].d = (float4 *)s->sssQd[1 + i].p; sssP[i].counts = (int *)s->sssCounts.p + (1 + i) * QSTRIDE; }
     return PG_OK;
 }
 
@@ -350,652 +402,554 @@ static hipEvent_t getEvent(PgScene *s, size_t idx) {
     return s->events[idx];
 }
 
-static int renderFrame(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays, int mem,
-                       void *streamPtr);
-int pg_render(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays,
-              int mem, void *streamPtr) {
-    if (!s || !rd || !film || !nStrays || (maxStrays > 0 && !strays)) return setError(PG_ERR_INVALID, "pg_render: null argument");
-    return withExactFallback(s, [&]() { return renderFrame(s, rd, film, strays, maxStrays, nStrays, mem, streamPtr); });
+extern "C++" {  // (templates)
+// HIP events around one launch on `st` (the stream the kernel runs on); per-kernel times are only meaningful while the
+// any-hit launch does not share the chip with the closest-hit launch (PG_OVERLAP_SHADOW=0, the default).  `on` = false: no event is
+// touched (the tile-serial mode: its hundreds of thousands of small launches would each need a pair of events).
+struct LaunchTimer {
+    PgScene *s = nullptr;
+    bool on = false; size_t ev = 2;  // (events 0 and 1 are the frame's)
+    std::vector<std::pair<size_t, int>> timed;  // (event index, kernel: 0 closest-hit, 1 any-hit, 2 shade, 3 resolve, 4 generate, 5 film)
+    template <class F> int run(int kind, hipStream_t st, F &&launch) {
+        if (!on) { launch(); return PG_OK; }
+        hipEvent_t a = getEvent(s, ev), b = getEvent(s, ev + 1);
+        if (!a || !b) return setError(PG_ERR_DEVICE, "hipEventCreate failed");
+        timed.push_back({ev, kind}); ev += 2;
+        HIP_TRY(hipEventRecord(a, st)); launch(); HIP_TRY(hipEventRecord(b, st));
+        return PG_OK;
+    }
+};
+// What the bounce loops and the frame drivers share
+struct FrameCtx {
+    PgScene *s = nullptr; const PgRenderDesc *rd = nullptr; hipStream_t stream = nullptr;
+    RenderParams rp = {};
+    DScene d;  // the frame's scene: s->d with this frame's sampler state (ts*); s->d itself is never written by a render
+    bool vol = false, tileSerial = false, sssOn = false;
+    size_t nQueue = 0;  // queueEntries of the frame's capacity
+    PathState ps = {}; VolState vs = {}; SssState sq = {};
+    RayQueue q[4] = {}, vq[2] = {}, sssP[2] = {};  // main ping-pong, shadow (2), MIS (3); the through rays' second halves; the probe queues
+    int *counts = nullptr, *cursors = nullptr, *cullGuard = nullptr;
+    float4 *hits = nullptr, *hitsMis = nullptr;
+    TraceCounters *cnClosest = nullptr, *cnShadow = nullptr;
+    unsigned long long *lightTests = nullptr;
+    PgFilmPixel *dFilm = nullptr; PgStraySample *dStrays = nullptr; int *dNStrays = nullptr, maxStrays = 0;  // device film / stray buffers (the caller's when mem == DEVICE)
+    BounceLimits lim = {};
+    DeviceBuffer countLog;  // per-bounce queue sizes, copied back after the batch for the ray statistics
+    std::vector<int> hostCounts, curQueueOfBounce, blk, vblk;  // (blk / vblk: host copies of the counter blocks of q[] / vq[])
+    uint64_t closestRays = 0, shadowRays = 0, cameraRays = 0, closestLaunches = 0, shadowLaunches = 0;
+    uint64_t shadeLaunches = 0, resolveLaunches = 0, shadeItems = 0, misRays = 0, shadingModes = 0;
+    LaunchTimer timer;
+};
+
+// sum of a queue's region counters in a host copy of the counter block
+static uint64_t queueTotal(const int *blk, int qi) { uint64_t t = 0; for (int r = 0; r < PG_REGIONS; ++r) t += (uint64_t)blk[qi * QSTRIDE + r * PG_COUNT_STRIDE]; return t; }
+// the counter blocks of the four queues (volpath: and of vq[]) back into c.blk (c.vblk)
+static int readCounts(FrameCtx &c) {
+    HIP_TRY(hipMemcpyAsync(c.blk.data(), c.counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    if (c.vol) HIP_TRY(hipMemcpyAsync(c.vblk.data(), c.s->vCounts.p, 2 * QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return PG_OK;
 }
-static int renderFrame(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays, int mem,
-                       void *streamPtr) {
-    if (rd->abi_version != PG_ABI_VERSION) return setError(PG_ERR_INVALID, "ABI version %d, expected %d", rd->abi_version, PG_ABI_VERSION);
-    if (rd->filter_radius[0] <= 0 || rd->filter_radius[1] <= 0) return setError(PG_ERR_INVALID, "pg_render: filter radius must be positive");
-    if (!rd->filter_general && (rd->filter_radius[0] > 0.5f || rd->filter_radius[1] > 0.5f || rd->tile_pixels != 256))
-        return setError(PG_ERR_INVALID, "pg_render: filter_general = 0 is the box filter of radius <= 0.5 with 256-entry tile blocks");
-    if (rd->filter_general && rd->tile_pixels != (16 + rd->tile_halo[0] + rd->tile_halo[2]) * (16 + rd->tile_halo[1] + rd->tile_halo[3]))
-        return setError(PG_ERR_INVALID, "pg_render: tile_pixels does not match tile_halo");
-    if (rd->spp <= 0 || rd->max_depth < 0 || rd->tile_step <= 0) return setError(PG_ERR_INVALID, "pg_render: bad spp/maxdepth/tile_step");
-    if (rd->integrator != 0 && rd->integrator != 1) return setError(PG_ERR_INVALID, "pg_render: integrator %d (0 = path, 1 = volpath)", rd->integrator);
-    const bool vol = rd->integrator == 1;
-    // (overlapShadow: the environment's PG_OVERLAP_SHADOW at pg_scene_create, then pg_scene_set_option -- a caller such as bench.py times
-    // frames with the overlap and takes per-kernel times from a serialised frame of the same scene)
-    if (rd->camera_medium < -1 || rd->camera_medium >= s->nMedia) return setError(PG_ERR_INVALID, "pg_render: camera_medium %d out of range", rd->camera_medium);
-    if (rd->sampler < PG_SAMPLER_HALTON || rd->sampler > PG_SAMPLER_MAXMINDIST) return setError(PG_ERR_INVALID, "pg_render: sampler %d (PgSamplerKind 0 .. 5)", rd->sampler);
-    // The PixelSamplers (stratified, 02sequence, maxmindist) fall back to their tile's RNG stream only for draws beyond their
-    // "dimensions" (sampler.cpp:108-134).  PathIntegrator::Li draws at most 1 + 2 maxdepth one-dimensional numbers (time; light choice and
-    // roulette per vertex) and 2 + 3 maxdepth two-dimensional ones (film, lens; uLight, uScattering, the next direction per vertex):
-    // with that many sampled dimensions StartPixel alone consumes the stream, every pixel's arrays can be generated ahead, and the
-    // paths run as one wavefront like the GlobalSamplers' (tsBatched).  Not for volpath (a ray through material-less surfaces samples
-    // its medium an unbounded number of times), materials with a BSSRDF, or sparse light tables (their deferred vertices re-draw).
-    bool tsBatched = false;
-    if (rd->sampler > PG_SAMPLER_RANDOM && rd->integrator == 0 && s->d.nBssrdfs == 0 && !s->d.sparseLights && rd->sampler_dims <= 63 &&
-        rd->sampler_dims >= 2 + 3 * (long long)rd->max_depth && !(getenv("PG_TS_BATCHED") && atoi(getenv("PG_TS_BATCHED")) == 0)) {
-        // The arrays of all local tiles are one allocation: taken here, before any state is set, so that a device without the room
-        // (less memory free, a large scene beside them) renders tile by tile as before instead of failing with PG_ERR_DEVICE.
-        const size_t nArr = (size_t)tileCount(rd) * 256 * (size_t)rd->sampler_dims * (size_t)rd->spp;
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { freeB = 0; (void)hipGetLastError(); }
-        const size_t have = s->ts1.bytes + s->ts2.bytes;  // (buffers of an earlier frame are given back first)
-        if (nArr * 12 <= ((size_t)48 << 30) && nArr * 12 + ((size_t)2 << 30) <= freeB + have) {
-            s->ts1.release(); s->ts2.release();
-            tsBatched = s->ts1.alloc(sizeof(float) * (nArr + 1)) == hipSuccess && s->ts2.alloc(sizeof(float) * 2 * (nArr + 1)) == hipSuccess;
-            if (!tsBatched) { s->ts1.release(); s->ts2.release(); (void)hipGetLastError(); }
+// one queue's counters on the device -> its size
+static int regionSum(FrameCtx &c, const int *dev, uint64_t &total) {
+    int jb[QSTRIDE];
+    HIP_TRY(hipMemcpyAsync(jb, dev, QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    total = queueTotal(jb, 0);
+    return PG_OK;
+}
+// PgCounters::shading_modes: which k_shade<MODE> this frame's shading launches are (pg_shade_mode, the launch functions' own choice)
+static void noteShading(FrameCtx &c, const DScene &dsc, bool vol, bool sss, bool gridPhase) {
+    const int mode = pg_shade_mode(dsc, c.rp, vol, sss, gridPhase);
+    c.shadingModes |= 1ull << mode;
+    if (mode == 3) c.shadingModes |= PG_SHADING_MATERIAL_PREPASS;
+    if (mode == 2 && !gridPhase && !(sss && dsc.nBssrdfs > 0) && c.s->matStride > 0) c.shadingModes |= PG_SHADING_LISTS_DID_NOT_FIT;
+}
+// Sparse "spatial" light tables: after a shading launch, compute the distributions of the voxels its lanes asked for and
+// shade the entries that waited for them (one host round trip per launch while the table warms up; none once every
+// voxel the image touches exists -- the tables stay with the scene).
+template <class F> static int settleLightTables(FrameCtx &c, F &&reshade) {
+    PgScene *s = c.s;
+    if (!c.d.sparseLights) return PG_OK;
+    int cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, s->voxelCounters.p, sizeof(cnt), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (cnt[0] == 0 && cnt[1] == 0) return PG_OK;
+    if (s->poolUsed + cnt[0] > s->poolSlots)
+        return setError(PG_ERR_UNSUPPORTED, "spatial light distribution: %d voxels x %d lights exceed the table pool (%d voxels); use "
+                                            "\"lightsamplestrategy\" \"power\" or \"uniform\"", s->poolUsed + cnt[0], c.d.nLights, s->poolSlots);
+    launch_light_tables_sparse(c.d, (float *)s->distTable.p, (const int *)s->voxelRequests.p, cnt[0], s->poolUsed, c.stream);
+    s->poolUsed += cnt[0];
+    HIP_TRY(hipMemsetAsync(s->voxelCounters.p, 0, sizeof(cnt), c.stream));
+    if (cnt[1] > 0) { c.rp.retryCount = cnt[1]; reshade(); c.rp.retryCount = 0; }
+    return PG_OK;
+}
+// The start of a batch of c.rp.capacity path slots: the queues' geometry, empty queues, the camera rays into the first main queue
+static int startBatch(FrameCtx &c, const std::function<void()> &generate) {
+    const int cap = regionCapFor(c.rp.capacity, c.d.sparseLights != 0);
+    for (int i = 0; i < 4; ++i) c.q[i].regionCap = cap;
+    c.vq[0].regionCap = c.vq[1].regionCap = c.sq.qjob.regionCap = c.sssP[0].regionCap = c.sssP[1].regionCap = cap;
+    c.curQueueOfBounce.clear();
+    HIP_TRY(hipMemsetAsync(c.counts, 0, 4 * QSTRIDE * sizeof(int), c.stream));
+    return c.timer.run(4, c.stream, generate);
+}
+// The probe chains of SeparableBSSRDF::Sample_Sp for the nJobs paths k_shade handed over (c.sq.qjob), walked twice through the
+// traversal kernel: pass 1 counts the hits on the material, pass 2 stops at the chosen one.  One counter read-back per step.  `d`
+// says where the probe rays' instances go, `hits` where their hits go; vol: the volpath variant of k_sss_probe.
+static int sssProbeChains(FrameCtx &c, const DScene &d, float4 *hits, uint64_t nJobs, bool vol) {
+    for (int pass = 1; pass <= 2; ++pass) {
+        RayQueue curQ = c.sq.qjob;
+        uint64_t nRays = nJobs;
+        for (int step = 0; nRays > 0; ++step) {
+            if (step > 1000000) return setError(PG_ERR_DEVICE, "pg_render: a BSSRDF probe chain did not terminate");
+            RayQueue outQ = c.sssP[step & 1];
+            HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), c.stream));
+            // the second walk repeats queries the reference makes once: its rays and traversal work are not counted
+            launch_closest(d, c.s->trace, curQ, hits, nullptr, pass == 1 ? c.cnClosest : c.cnClosest + 2, c.cursors, c.cullGuard, c.stream);
+            if (pass == 1) { c.closestRays += nRays; ++c.closestLaunches; }
+            launch_sss_probe(d, c.sq, pass, curQ, hits, outQ, c.stream, vol, vol && step == 0);
+            if (int e = regionSum(c, outQ.counts, nRays)) return e;
+            curQ = outQ;
         }
     }
-    const bool tileSerial = rd->sampler >= PG_SAMPLER_RANDOM && !tsBatched;
-    if (rd->sampler >= PG_SAMPLER_RANDOM) {
-        if (rd->sampler != PG_SAMPLER_RANDOM && (rd->sampler_dims < 0 || rd->sampler_dims > 4096)) return setError(PG_ERR_INVALID, "pg_render: sampler_dims %d", rd->sampler_dims);
-        if (rd->sampler == PG_SAMPLER_STRATIFIED && (rd->strat_samples[0] < 1 || rd->strat_samples[1] < 1 || rd->strat_samples[0] * rd->strat_samples[1] != rd->spp))
-            return setError(PG_ERR_INVALID, "pg_render: stratified sampler %d x %d samples, spp %d", rd->strat_samples[0], rd->strat_samples[1], rd->spp);
-        if ((rd->sampler == PG_SAMPLER_ZEROTWO || rd->sampler == PG_SAMPLER_MAXMINDIST) && (rd->spp & (rd->spp - 1)))
-            return setError(PG_ERR_INVALID, "pg_render: sampler %d needs a power-of-two spp (the reference rounds up), got %d", rd->sampler, rd->spp);
-        if (rd->sampler == PG_SAMPLER_MAXMINDIST && (!s->cmaxmin.p || rd->sampler_dims < 1 || rd->spp >= (1 << 17)))
-            return setError(PG_ERR_INVALID, "pg_render: maxmindist needs PgSceneDesc.cmaxmin, sampler_dims >= 1 and spp < 2^17");
-    }
-    if (rd->sampler == 1) {
-        if (!s->d.sobolMatrices) return setError(PG_ERR_INVALID, "pg_render: sampler = sobol, but the scene was created without the Sobol' tables");
-        if (rd->sobol_log2_resolution < 0 || rd->sobol_log2_resolution > 26 || rd->sobol_resolution != (1 << rd->sobol_log2_resolution))
-            return setError(PG_ERR_INVALID, "pg_render: sobol_resolution %d / sobol_log2_resolution %d", rd->sobol_resolution, rd->sobol_log2_resolution);
-    }
-    if (rd->sampler == 0 && (!s->d.perms || (5 + 8 * ((long long)rd->max_depth + 1) > s->d.nPermDims && s->d.nPermDims < 1000)))
-        return setError(PG_ERR_INVALID, "Halton table has %d dimensions; maxdepth %d needs %lld", s->d.nPermDims, rd->max_depth, 5 + 8 * ((long long)rd->max_depth + 1));
-    if (!rd->filter_general && pgh_box_filter_needs_gather(rd))
-        return setError(PG_ERR_INVALID, "pg_render: filter_general = 0, but in this frame a film position can round up onto the next pixel "
-                                        "(pg_box_filter_needs_gather, include/pbrt_gpu.h): render it with filter_general = 1");
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = (hipStream_t)streamPtr;
-    const int nLocalTiles = tileCount(rd);
-    RenderParams rp;
-    memset(&rp, 0, sizeof(rp));
-    rp.rd = *rd;
-    s->d.tsBatched = 0; s->d.tsOverflow = nullptr;  // (a call that failed half-way may have left them set)
-    rp.nTilesX = (rd->sample_bounds[2] - rd->sample_bounds[0] + 15) / 16;
-    rp.nTilesY = (rd->sample_bounds[3] - rd->sample_bounds[1] + 15) / 16;
+    return PG_OK;
+}
 
+// volpath's through rays: kind 0 = light samples (q[2] <-> vq[0]), kind 1 = BSDF / phase samples (q[3] <-> vq[1]), re-traced
+// until none is left under way
+static int throughRays(FrameCtx &c, const DScene &dv, float *hitT) {
+    const hipStream_t stream = c.stream; const int n1 = (int)c.nQueue;
+    if (c.d.nGrids > 0) {
+        // ratio tracking draws from the path's sampler: a path's kind-0 ray (visibility.Tr) runs to its end before
+        // its kind-1 ray (IntersectTr after the BSDF sample) starts, as in EstimateDirect; one queue pair at a time
+        for (int kind = 0; kind < 2; ++kind) {
+            RayQueue tk[2] = {kind == 0 ? c.q[2] : c.q[3], c.vq[kind]};
+            int tc = 0;
+            for (int pass = 0;; ++pass) {
+                if (pass > 100000) return setError(PG_ERR_DEVICE, "pg_render: transmittance loop did not terminate");
+                if (int e = readCounts(c)) return e;
+                const uint64_t nk = tc == 0 ? queueTotal(c.blk.data(), 2 + kind) : queueTotal(c.vblk.data(), kind);
+                if (nk == 0) break;
+                // (results at the offset the kind's through kernel reads them from)
+                const size_t off = (size_t)(1 + kind) * n1;  // part 0 keeps the main rays' hits for phase 2
+                DScene dk = dv;
+                if (dk.hitInst) dk.hitInst += off;
+                if (dk.animXf) dk.animXf += off * PG_XF_STRIDE;
+                if (int e = c.timer.run(0, stream, [&] { launch_closest(dk, c.s->trace, tk[tc], c.hits + off, hitT + off, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+                ++c.closestLaunches; c.closestRays += nk;
+                HIP_TRY(hipMemsetAsync(tk[tc ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
+                launch_through(dv, c.ps, c.vs, kind, tk[tc], c.hits, hitT, (int)off, tk[tc ^ 1], stream, &c.rp);
+                tc ^= 1;
+            }
+        }
+        return PG_OK;
+    }
+    RayQueue tq[2][2] = {{c.q[2], c.vq[0]}, {c.q[3], c.vq[1]}};
+    int tcur = 0;
+    for (int pass = 0;; ++pass) {
+        if (pass > 100000) return setError(PG_ERR_DEVICE, "pg_render: transmittance loop did not terminate");
+        if (int e = readCounts(c)) return e;
+        const uint64_t n0 = tcur == 0 ? queueTotal(c.blk.data(), 2) : queueTotal(c.vblk.data(), 0);
+        const uint64_t n1q = tcur == 0 ? queueTotal(c.blk.data(), 3) : queueTotal(c.vblk.data(), 1);
+        if (n0 + n1q == 0) break;
+        if (int e = c.timer.run(0, stream, [&] { launch_closest2(dv, c.s->trace, tq[0][tcur], tq[1][tcur], c.hits, n1, c.cnClosest, c.cursors, c.cullGuard, stream, hitT); })) return e;
+        ++c.closestLaunches; c.closestRays += n0 + n1q;
+        HIP_TRY(hipMemsetAsync(tq[0][tcur ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
+        HIP_TRY(hipMemsetAsync(tq[1][tcur ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
+        launch_through(dv, c.ps, c.vs, 0, tq[0][tcur], c.hits, hitT, 0, tq[0][tcur ^ 1], stream);
+        launch_through(dv, c.ps, c.vs, 1, tq[1][tcur], c.hits, hitT, n1, tq[1][tcur ^ 1], stream);
+        tcur ^= 1;
+    }
+    return PG_OK;
+}
+
+// One batch of paths from their camera rays (`generate` fills the first main queue) to their film samples (`film`): all the
+// bounces of the c.rp.capacity path slots described by c.rp, under VolPathIntegrator::Li (volpath.cpp:72-186).  Per loop iteration:
+// closest-hit(main rays, with the hits' ray parameters) -> shade with medium sampling -> the transmittance rays of the light samples
+// and of the BSDF/phase samples, re-traced until none is left under way (light.cpp:63-81, scene.cpp:57-70) -> resolve.
+// Crossing a surface without a material does not count as a bounce, so the loop runs until the queue is empty.
+static int bouncesVolpath(FrameCtx &c, const std::function<void()> &generate, const std::function<void()> &film) {
+    PgScene *s = c.s; const hipStream_t stream = c.stream; RayQueue *const q = c.q;
+    if (int e = startBatch(c, generate)) return e;
+    int cur = 0;  // main queue index (0/1 ping-pong); 2 = light-sample rays, 3 = BSDF / phase-sample rays
+    DScene dv = c.d;
+    dv.ext = 1;  // the general shading kernels
+    float *hitT = (float *)s->hitT.p;
+    launch_fill_int(c.vs.medium, c.rd->camera_medium + 1, c.rp.capacity, stream);  // camera rays start in the camera's medium (camera.h:78)
+    if (int e = readCounts(c)) return e;
+    uint64_t nMain = queueTotal(c.blk.data(), cur);
+    c.cameraRays += nMain;
+    const SssState *sssArg = c.sssOn ? &c.sq : nullptr;
+    // a scene with a grid medium shades in two phases around the transmittance rays (k_shade<., ., ., GRID>)
+    const bool gridOn = c.d.nGrids > 0;
+    float4 *gridVertex = (float4 *)s->gridVertex.p;
+    // (GlobalSamplers, dense light tables: the tile-serial streams and the deferred vertices of sparse tables draw in the shading kernel)
+    float2 *volPre = (s->volOrder && !c.tileSerial && !c.d.sparseLights) ? (float2 *)s->volPre.p : nullptr;
+    for (int iter = 0; nMain > 0; ++iter) {
+        if (iter > 100000) return setError(PG_ERR_DEVICE, "pg_render: volpath loop did not terminate");
+        const int nxt = cur ^ 1;
+        if (int e = c.timer.run(0, stream, [&] { launch_closest(dv, s->trace, q[cur], c.hits, hitT, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+        ++c.closestLaunches; c.closestRays += nMain; c.shadeItems += nMain;
+        HIP_TRY(hipMemsetAsync(c.counts + nxt * QSTRIDE, 0, QSTRIDE * sizeof(int), stream));
+        HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
+        if (c.sssOn) HIP_TRY(hipMemsetAsync(c.sq.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
+        c.rp.volPre = volPre;
+        c.rp.order = (c.d.primClass || volPre) ? (const int *)s->shadeOrder.p : nullptr;  // (the second phase of a grid scene takes the same order)
+        auto shade = [&](int phase) { launch_shade_vol(dv, c.rp, c.ps, c.vs, q[cur], c.hits, hitT, q[nxt], q[2], q[3], c.lightTests, stream, sssArg, gridVertex, phase, phase == 2 ? 0 : cur); };
+        if (int e = c.timer.run(2, stream, [&] { launch_shade_order_vol(dv, c.rp, c.ps, c.vs, q[cur], c.hits, hitT, (int *)s->shadeOrder.p, volPre, stream, cur); shade(gridOn ? 1 : 0); })) return e;
+        ++c.shadeLaunches; noteShading(c, dv, true, sssArg != nullptr, gridOn);
+        if (int e = settleLightTables(c, [&] { shade(gridOn ? 1 : 0); })) return e;
+        if (int e = throughRays(c, dv, hitT)) return e;
+        if (int e = c.timer.run(3, stream, [&] { launch_resolve_vol(dv, c.ps, c.vs, q[cur], stream, cur); })) return e;
+        ++c.resolveLaunches;
+        if (gridOn) {  // phase 2: the vertices' next directions, drawn behind the transmittance rays' numbers
+            if (int e = c.timer.run(2, stream, [&] { shade(2); })) return e;
+            ++c.shadeLaunches;
+            if (int e = readCounts(c)) return e;
+        }
+        if (c.sssOn) {
+            // ---- the BSSRDF branch (volpath.cpp:151-176) of the paths k_shade handed over: probe chains (two walks), exit
+            // vertices, their transmittance rays and resolve; the exit vertices' next rays join q[nxt], which is
+            // traced as a whole at the start of the next iteration
+            uint64_t nJobs = 0;
+            if (int e = regionSum(c, c.sq.qjob.counts, nJobs)) return e;
+            if (nJobs > 0) {
+                if (int e = sssProbeChains(c, dv, c.hits, nJobs, true)) return e;
+                HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
+                // (a grid medium's ratio tracking draws from the paths' samplers: the exit vertices' transmittance rays run between their direct
+                // lighting and their next directions, as at k_shade's vertices -- k_sss_exit in two phases; gridVertex is free again by now)
+                launch_sss_exit(dv, c.rp, c.ps, c.sq, q[nxt], q[2], q[3], c.lightTests, stream, nxt, true, c.vs, gridOn ? 1 : 0, gridVertex);
+                ++c.shadeLaunches; c.shadeItems += nJobs;
+                if (int e = throughRays(c, dv, hitT)) return e;
+                launch_resolve_vol(dv, c.ps, c.vs, c.sq.qjob, stream);
+                ++c.resolveLaunches;
+                if (gridOn) { launch_sss_exit(dv, c.rp, c.ps, c.sq, q[nxt], q[2], q[3], c.lightTests, stream, nxt, true, c.vs, 2, gridVertex); ++c.shadeLaunches; }
+            }
+            if (int e = readCounts(c)) return e;
+        }
+        // the last pass of the through loop read the counters: the main queue's size comes from the same block
+        nMain = queueTotal(c.blk.data(), nxt);
+        cur = nxt;
+    }
+    film();  // (not timed: volpath's film launch never was)
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PG_OK;
+}
+
+// The same under PathIntegrator::Li.  Launch order per bounce b (one stream): shade(b) -> any-hit(shadow rays of b) -> closest-hit(main
+// rays of b+1 and MIS rays of b in ONE launch) -> resolve(b).  The first closest-hit launch traces the camera rays alone.
+static int bouncesPath(FrameCtx &c, const std::function<void()> &generate, const std::function<void()> &film) {
+    PgScene *s = c.s; const PgRenderDesc *rd = c.rd;
+    const hipStream_t stream = c.stream; RayQueue *const q = c.q;
+    if (int e = startBatch(c, generate)) return e;
+    int cur = 0;  // main queue index (0/1 ping-pong); 2 = shadow, 3 = MIS
+    if (int e = c.timer.run(0, stream, [&] { launch_closest(c.d, s->trace, q[cur], c.hits, nullptr, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+    ++c.closestLaunches;
+    const SssState *sssArg = c.sssOn ? &c.sq : nullptr;
+    int iters = 0;
+    for (int bounce = 0; bounce < c.lim.maxIters; ++bounce, ++iters) {
+        const int nxt = cur ^ 1;
+        HIP_TRY(hipMemsetAsync(c.counts + nxt * QSTRIDE, 0, QSTRIDE * sizeof(int), stream));
+        HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
+        if (c.sssOn) HIP_TRY(hipMemsetAsync(c.sq.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
+        c.rp.order = c.d.primClass ? (const int *)s->shadeOrder.p : nullptr;
+        auto shade = [&] { launch_shade(c.d, c.rp, c.ps, q[cur], c.hits, q[nxt], q[2], q[3], c.lightTests, stream, cur, sssArg); };
+        if (int e = c.timer.run(2, stream, [&] { launch_shade_order(c.d, q[cur], c.hits, (int *)s->shadeOrder.p, stream); shade(); })) return e;
+        ++c.shadeLaunches; noteShading(c, c.d, false, sssArg != nullptr, false);
+        if (int e = settleLightTables(c, shade)) return e;
+        // paths that reach maxdepth neither continue nor sample lights (path.cpp:104): nothing left to trace
+        const bool lastDepth = !s->hasNullMaterial && bounce >= rd->max_depth;
+        if (!lastDepth) {
+            // The shadow rays of this bounce and the closest-hit rays of the next depend only on shade(b): the any-hit
+            // launch goes to a second stream so that its blocks fill the chip while the closest-hit launch's
+            // persistent waves drain (and vice versa); resolve(b) joins both.
+            // (tile-serial samplers: a handful of rays per launch, each a chain of dependent fetches -- both launches are
+            // latency-bound and run side by side)
+            // (overlapShadow: the environment's PG_OVERLAP_SHADOW at pg_scene_create, then pg_scene_set_option -- a caller such as bench.py times
+            // frames with the overlap and takes per-kernel times from a serialised frame of the same scene)
+            const bool overlap = s->overlapShadow || c.tileSerial;
+            hipStream_t sst = overlap ? s->shadowStream : stream;
+            if (overlap) { HIP_TRY(hipEventRecord(s->evShaded, stream)); HIP_TRY(hipStreamWaitEvent(sst, s->evShaded, 0)); }
+            if (int e = c.timer.run(1, sst, [&] { launch_anyhit(c.d, s->trace, q[2], (int *)s->occluded.p, c.cnShadow, (int *)s->cursors2.p, sst); })) return e;
+            ++c.shadowLaunches;
+            if (overlap) HIP_TRY(hipEventRecord(s->evShadowed, sst));
+            if (int e = c.timer.run(0, stream, [&] { launch_closest2(c.d, s->trace, q[nxt], q[3], c.hits, (int)c.nQueue, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+            ++c.closestLaunches;
+            if (overlap) HIP_TRY(hipStreamWaitEvent(stream, s->evShadowed, 0));
+            if (int e = c.timer.run(3, stream, [&] { launch_resolve(c.d, c.ps, q[cur], q[3], (const int *)s->occluded.p, c.hitsMis, stream, cur, c.lightTests); })) return e;
+            ++c.resolveLaunches;
+        }
+        // log this bounce's queue sizes
+        HIP_TRY(hipMemcpyAsync((int *)c.countLog.p + 4 * QSTRIDE * (size_t)bounce, c.counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToDevice, stream));
+        c.curQueueOfBounce.push_back(cur);
+        if (c.sssOn && !lastDepth) {
+            // ---- the BSSRDF branch of Li (path.cpp:152-174) for the paths k_shade handed over: the probe chains, then the exit
+            // vertices: their shadow / MIS rays, the tail of the next bounce's queue that their next rays form, and the resolve of
+            // their direct lighting.
+            uint64_t nJobs = 0;
+            if (int e = regionSum(c, c.sq.qjob.counts, nJobs)) return e;
+            if (nJobs > 0) {
+                const size_t n1 = (size_t)q[0].regionCap * PG_REGIONS;
+                DScene dprobe = c.d;  // the probe rays' hits go where the MIS rays' went (k_resolve is done with those)
+                if (dprobe.hitInst) dprobe.hitInst += n1;
+                if (dprobe.animXf) dprobe.animXf += n1 * PG_XF_STRIDE;
+                if (int e = sssProbeChains(c, dprobe, c.hitsMis, nJobs, false)) return e;
+                HIP_TRY(hipMemcpyAsync(s->sssTail.p, c.counts + nxt * QSTRIDE, QSTRIDE * sizeof(int), hipMemcpyDeviceToDevice, stream));
+                HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
+                launch_sss_exit(c.d, c.rp, c.ps, c.sq, q[nxt], q[2], q[3], c.lightTests, stream, nxt, false, c.vs);
+                ++c.shadeLaunches; c.shadeItems += nJobs;
+                launch_anyhit(c.d, s->trace, q[2], (int *)s->occluded.p, c.cnShadow, (int *)s->cursors2.p, stream);
+                ++c.shadowLaunches;
+                launch_closest2(c.d, s->trace, q[nxt], q[3], c.hits, (int)n1, c.cnClosest, c.cursors, c.cullGuard, stream, nullptr, (const int *)s->sssTail.p);
+                ++c.closestLaunches;
+                launch_resolve(c.d, c.ps, c.sq.qjob, q[3], (const int *)s->occluded.p, c.hitsMis, stream, cur);
+                ++c.resolveLaunches;
+                uint64_t nSh = 0, nMis = 0;
+                if (int e = regionSum(c, c.counts + 2 * QSTRIDE, nSh)) return e;
+                if (int e = regionSum(c, c.counts + 3 * QSTRIDE, nMis)) return e;
+                c.shadowRays += nSh; c.closestRays += nMis; c.misRays += nMis;  // (the next rays are counted with the next bounce's queue)
+            }
+        }
+        cur = nxt;
+        if ((s->hasNullMaterial && bounce >= rd->max_depth) || (bounce >= PG_MAX_BLIND_BOUNCES && bounce % 32 == 0)) {
+            if (int e = readCounts(c)) return e;
+            if (queueTotal(c.blk.data(), cur) == 0) { ++iters; break; }
+        }
+    }
+    if (iters == c.lim.maxIters && c.lim.wantIters > c.lim.maxIters) {  // the last allowed bounce: is anything still alive?
+        if (int e = readCounts(c)) return e;
+        if (queueTotal(c.blk.data(), cur) != 0) return setError(PG_ERR_UNSUPPORTED, "paths longer than %lld vertices (maxdepth %d)", PG_MAX_BOUNCES, rd->max_depth);
+    }
+    if (int e = c.timer.run(5, stream, film)) return e;
+    c.hostCounts.resize(4 * QSTRIDE * (size_t)iters);  // read back once per batch (pinned copy not needed: tiny)
+    HIP_TRY(hipMemcpyAsync(c.hostCounts.data(), c.countLog.p, sizeof(int) * 4 * QSTRIDE * (size_t)iters, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int b = 0; b < iters; ++b) {
+        const int *blk = c.hostCounts.data() + 4 * QSTRIDE * (size_t)b;
+        const uint64_t nMain = queueTotal(blk, c.curQueueOfBounce[b]), nShadow = queueTotal(blk, 2), nMis = queueTotal(blk, 3);
+        c.closestRays += nMain + nMis; c.shadowRays += nShadow; c.shadeItems += nMain; c.misRays += nMis;
+        if (getenv("PG_PRINT_COUNTS"))
+            fprintf(stderr, "pg_render: bounce %d main %llu shadow %llu mis %llu\n", b, (unsigned long long)nMain, (unsigned long long)nShadow, (unsigned long long)nMis);
+    }
+    if (iters > 0) c.cameraRays += queueTotal(c.hostCounts.data(), c.curQueueOfBounce[0]);
+    return PG_OK;
+}
+static int tracePaths(FrameCtx &c, const std::function<void()> &generate, const std::function<void()> &film) { return c.vol ? bouncesVolpath(c, generate, film) : bouncesPath(c, generate, film); }
+
+// The PixelSamplers (stratified, 02sequence, maxmindist) fall back to their tile's RNG stream only for draws beyond their
+// "dimensions" (sampler.cpp:108-134).  PathIntegrator::Li draws at most 1 + 2 maxdepth one-dimensional numbers (time; light choice and
+// roulette per vertex) and 2 + 3 maxdepth two-dimensional ones (film, lens; uLight, uScattering, the next direction per vertex):
+// with that many sampled dimensions StartPixel alone consumes the stream, every pixel's arrays can be generated ahead, and the
+// paths run as one wavefront like the GlobalSamplers' (tsBatched).  Not for volpath (a ray through material-less surfaces samples
+// its medium an unbounded number of times), materials with a BSSRDF, or sparse light tables (their deferred vertices re-draw).
+// The arrays of all local tiles are one allocation: taken here, before any state is set, so that a device without the room
+// (less memory free, a large scene beside them) renders tile by tile as before instead of failing with PG_ERR_DEVICE.
+static bool reserveSampleArrays(PgScene *s, const PgRenderDesc *rd) {
+    if (!(rd->sampler > PG_SAMPLER_RANDOM && rd->integrator == 0 && s->d.nBssrdfs == 0 && !s->d.sparseLights && rd->sampler_dims <= 63 &&
+          rd->sampler_dims >= 2 + 3 * (long long)rd->max_depth && !(getenv("PG_TS_BATCHED") && atoi(getenv("PG_TS_BATCHED")) == 0))) return false;
+    const size_t nArr = (size_t)pgTileCount(rd) * 256 * (size_t)rd->sampler_dims * (size_t)rd->spp;
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { freeB = 0; (void)hipGetLastError(); }
+    const size_t have = s->ts1.bytes + s->ts2.bytes;  // (buffers of an earlier frame are given back first)
+    if (!(nArr * 12 <= ((size_t)48 << 30) && nArr * 12 + ((size_t)2 << 30) <= freeB + have)) return false;
+    s->ts1.release(); s->ts2.release();
+    const bool ok = s->ts1.alloc(sizeof(float) * (nArr + 1)) == hipSuccess && s->ts2.alloc(sizeof(float) * 2 * (nArr + 1)) == hipSuccess;
+    if (!ok) { s->ts1.release(); s->ts2.release(); (void)hipGetLastError(); }
+    return ok;
+}
+
+// The frame's work buffers for `capacity` path slots and the views of them the kernels take
+static int setUpFrame(FrameCtx &c, int capacity) {
+    PgScene *s = c.s;
+    c.nQueue = queueEntries(s, capacity);
+    if (int e = ensureWorkBuffers(s, capacity, c.nQueue)) return e;
+    if (c.vol) if (int e = ensureVolBuffers(s, capacity, c.nQueue, c.vs, c.vq)) return e;
+    if (int e = ensureQueueState(s, capacity, c.nQueue, c.vol, c.ps)) return e;
+    c.sssOn = s->d.nBssrdfs > 0;
+    if (c.sssOn) if (int e = ensureSssBuffers(s, capacity, c.nQueue, c.sq, c.sssP)) return e;
+    c.d = s->d;
+    c.hits = (float4 *)s->hitsMain.p; c.hitsMis = c.hits + c.nQueue; c.cursors = (int *)s->cursors.p; c.cullGuard = (int *)s->cullGuard.p;
+    c.ps.L = (float4 *)s->stL.p; c.ps.beta = (float4 *)s->stBeta.p; c.ps.meta = (int4 *)s->stMeta.p;
+    c.ps.pdLight = (float4 *)s->pdLight.p; c.ps.pdMis = (float4 *)s->pdMis.p; c.ps.pdBeta = (float4 *)s->pdBeta.p; c.ps.pdInfo = (int4 *)s->pdInfo.p;
+    c.counts = (int *)s->counts.p;
+    for (int i = 0; i < 4; ++i) { c.q[i].o = (float4 *)s->qo[i].p; c.q[i].d = (float4 *)s->qd[i].p; c.q[i].counts = c.counts + i * QSTRIDE; }
+    c.cnClosest = (TraceCounters *)s->traceCn.p; c.cnShadow = c.cnClosest + 1;
+    c.lightTests = (unsigned long long *)s->lightTests.p;
+    c.rp.retryList = (int *)s->retryList.p;
+    if (s->matLobes.p && s->matHead.p) { c.rp.matPre.lobes = (float4 *)s->matLobes.p; c.rp.matPre.head = (float4 *)s->matHead.p; c.rp.matPre.stride = s->matStride; }
+    c.blk.resize(4 * QSTRIDE); c.vblk.resize(2 * QSTRIDE);
+    c.lim = pgBounceLimits(c.rd->max_depth, s->hasNullMaterial);
+    return PG_OK;
+}
+
+// The GlobalSamplers, and the PixelSamplers whose sample arrays were reserved (tsBatched): tile x sample batches, each one wavefront
+static int renderBatched(FrameCtx &c, int nLocalTiles, BatchShape shape, bool tsBatched) {
+    PgScene *s = c.s; const PgRenderDesc *rd = c.rd; RenderParams &rp = c.rp;
+    if (tsBatched) {  // every pixel's sample arrays, one lane per tile (the tile's stream in the reference's pixel order)
+        const size_t nArr = (size_t)nLocalTiles * 256 * (size_t)rd->sampler_dims * (size_t)rd->spp;
+        HIP_TRY(s->tsState.alloc(sizeof(TileSamplerState) * (size_t)nLocalTiles));
+        if (s->ts1.bytes < sizeof(float) * (nArr + 1) || s->ts2.bytes < sizeof(float) * 2 * (nArr + 1)) return setError(PG_ERR_DEVICE, "pg_render: sample arrays not allocated");  // (taken by reserveSampleArrays)
+        HIP_TRY(s->tsOverflow.alloc(sizeof(int)));
+        HIP_TRY(hipMemsetAsync(s->tsOverflow.p, 0, sizeof(int), c.stream));
+        c.d.ts = (TileSamplerState *)s->tsState.p; c.d.ts1 = (float *)s->ts1.p; c.d.ts2 = (float *)s->ts2.p;
+        c.d.tsDims = rd->sampler_dims; c.d.tsSpp = rd->spp; c.d.tsBatched = 1; c.d.tsOverflow = (int *)s->tsOverflow.p;
+        rp.tileLocal0 = 0; rp.nTilesBatch = nLocalTiles; rp.s0 = 0; rp.sCount = 1; rp.capacity = nLocalTiles;
+        launch_ts_init(c.d, rp, c.stream);
+        rp.tsGuessSkew = getenv("PG_TS_GUESS_SKEW") ? atoi(getenv("PG_TS_GUESS_SKEW")) : 0;
+        launch_ts_start_tile(c.d, rp, c.stream);
+    }
+    const std::function<void()> generate = [&]() { launch_generate(c.d, rp, c.ps, c.q[0], c.stream); };
+    const std::function<void()> film = [&]() { if (rd->filter_general) launch_film_general(rp, c.ps, c.dFilm, c.stream); else launch_film(rp, c.ps, c.dFilm, c.dStrays, c.maxStrays, c.dNStrays, c.stream); };
+    for (int tile0 = 0; tile0 < nLocalTiles; tile0 += shape.tiles)
+        for (int s0 = 0; s0 < rd->spp; s0 += shape.samples) {
+            rp.tileLocal0 = tile0; rp.nTilesBatch = std::min(shape.tiles, nLocalTiles - tile0);
+            rp.s0 = s0; rp.sCount = std::min(shape.samples, rd->spp - s0);
+            rp.capacity = rp.nTilesBatch * 256 * rp.sCount;
+            if (int e = tracePaths(c, generate, film)) return e;
+        }
+    if (tsBatched) {
+        int over = 0;
+        HIP_TRY(hipMemcpyAsync(&over, s->tsOverflow.p, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        if (over & 2) return setError(PG_ERR_DEVICE, "pg_render: the start offsets of a tile's pixel sample arrays did not converge (k_ts_start_tile, internal error)");
+        if (over) return setError(PG_ERR_DEVICE, "pg_render: a path drew beyond the %d sampled dimensions of the batched pixel sampler (internal error)", rd->sampler_dims);
+    }
+    return PG_OK;
+}
+// The samplers that draw from one RNG stream per tile (random, stratified, 02sequence, maxmindist): a tile's pixels, a
+// pixel's samples and a sample's draws consume the stream in order, and how many numbers a path takes depends on the
+// path -- so a tile has ONE path in flight, and the wavefront is one path of every tile: pixel (lx, ly) of all tiles,
+// sample by sample (integrator.cpp:247-332).  Tiles clipped by the image skip the pixels they do not have.
+static int renderTileSerial(FrameCtx &c, int nLocalTiles) {
+    PgScene *s = c.s; const PgRenderDesc *rd = c.rd; RenderParams &rp = c.rp;
+    const int nd = rd->sampler == PG_SAMPLER_RANDOM ? 0 : rd->sampler_dims;
+    HIP_TRY(s->tsState.alloc(sizeof(TileSamplerState) * (size_t)nLocalTiles));
+    HIP_TRY(s->ts1.alloc(sizeof(float) * ((size_t)nLocalTiles * nd * rd->spp + 1)));
+    HIP_TRY(s->ts2.alloc(sizeof(float) * 2 * ((size_t)nLocalTiles * nd * rd->spp + 1)));
+    c.d.ts = (TileSamplerState *)s->tsState.p; c.d.ts1 = (float *)s->ts1.p; c.d.ts2 = (float *)s->ts2.p;
+    c.d.tsDims = nd; c.d.tsSpp = rd->spp;
+    rp.tileLocal0 = 0; rp.nTilesBatch = nLocalTiles; rp.s0 = 0; rp.sCount = 1; rp.capacity = nLocalTiles;
+    launch_ts_init(c.d, rp, c.stream);
+    for (int ly = 0; ly < 16; ++ly)
+        for (int lx = 0; lx < 16; ++lx) {
+            if (rd->sample_bounds[0] + lx >= rd->sample_bounds[2] || rd->sample_bounds[1] + ly >= rd->sample_bounds[3]) continue;  // no tile has this pixel
+            launch_ts_start_pixel(c.d, rp, lx, ly, c.stream);
+            for (int sn = 0; sn < rd->spp; ++sn)
+                if (int e = tracePaths(c, [&]() { launch_ts_generate(c.d, rp, c.ps, c.q[0], sn, c.stream); },
+                                       [&]() { launch_ts_film(c.d, rp, c.ps, c.dFilm, c.dStrays, c.maxStrays, c.dNStrays, c.stream); })) return e;
+        }
+    return PG_OK;
+}
+
+// The film and the stray samples back to the caller (mem == HOST), or the stray count clamped in place; hostNStrays: the samples the frame produced
+static int readBackFrame(FrameCtx &c, PgFilmPixel *film, size_t filmBytes, PgStraySample *strays, int32_t *nStrays, int mem, int &hostNStrays) {
+    HIP_TRY(hipMemcpyAsync(&hostNStrays, c.dNStrays, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    if (mem == PG_MEM_HOST) {
+        HIP_TRY(hipMemcpyAsync(film, c.dFilm, filmBytes, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        int nCopy = std::min(hostNStrays, c.maxStrays);
+        if (nCopy > 0) HIP_TRY(hipMemcpy(strays, c.dStrays, sizeof(PgStraySample) * (size_t)nCopy, hipMemcpyDeviceToHost));
+        *nStrays = nCopy;
+    } else {
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        if (hostNStrays > c.maxStrays) { int v = c.maxStrays; HIP_TRY(hipMemcpy(c.dNStrays, &v, sizeof(int), hipMemcpyHostToDevice)); }
+    }
+    return PG_OK;
+}
+// The frame's tallies, the device's traversal and integrator statistics and the event times into the scene's PgCounters
+static int accountFrame(FrameCtx &c, hipEvent_t evStart, hipEvent_t evStop) {
+    PgScene *s = c.s;
+    PgCounters &pc = s->counters;
+    TraceCounters tc[2];
+    unsigned long long lt = 0;
+    HIP_TRY(hipMemcpy(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> shards(PG_LIGHT_TEST_SHARDS * PG_LIGHT_TEST_STRIDE);
+    HIP_TRY(hipMemcpy(shards.data(), c.lightTests, s->lightTests.bytes, hipMemcpyDeviceToHost));
+    for (int i = 0; i < PG_LIGHT_TEST_SHARDS; ++i) lt += shards[(size_t)i * PG_LIGHT_TEST_STRIDE];
+    // the integrators' own statistics, words 1 .. 8 of the same shards (pg_kernels.h): like the light tests they run on from pg_counters_reset
+    pc.paths_total = pc.paths_zero_radiance = pc.path_length_sum = pc.path_length_count = pc.path_length_min = pc.path_length_max = pc.volume_interactions = pc.surface_interactions = 0;
+    unsigned long long minc = 0, maxp = 0;
+    for (int i = 0; i < PG_LIGHT_TEST_SHARDS; ++i) {
+        const unsigned long long *sh = &shards[(size_t)i * PG_LIGHT_TEST_STRIDE];
+        pc.path_length_sum += sh[PG_STAT_LEN_SUM]; pc.path_length_count += sh[PG_STAT_LEN_COUNT];
+        minc = std::max(minc, sh[PG_STAT_LEN_MINC]); maxp = std::max(maxp, sh[PG_STAT_LEN_MAXP]);
+        pc.paths_total += sh[PG_STAT_PATHS]; pc.paths_zero_radiance += sh[PG_STAT_PATHS_ZERO];
+        pc.volume_interactions += sh[PG_STAT_VOLUME]; pc.surface_interactions += sh[PG_STAT_SURFACE];
+    }
+    if (pc.path_length_count > 0) { pc.path_length_min = 0xffff - minc; pc.path_length_max = maxp - 1; }
+    pc.camera_rays += c.cameraRays; pc.closest_rays += c.closestRays; pc.shadow_rays += c.shadowRays;
+    pc.node_visits = tc[0].node_visits + tc[1].node_visits;
+    pc.tri_tests = tc[0].tri_tests + tc[1].tri_tests + lt;
+    pc.light_tri_tests = lt;
+    pc.closest_node_visits = tc[0].node_visits; pc.closest_tri_tests = tc[0].tri_tests;
+    pc.shadow_node_visits = tc[1].node_visits; pc.shadow_tri_tests = tc[1].tri_tests;
+    pc.closest_launches += c.closestLaunches; pc.shadow_launches += c.shadowLaunches;
+    pc.shade_launches += c.shadeLaunches; pc.resolve_launches += c.resolveLaunches; pc.shade_items += c.shadeItems; pc.mis_rays += c.misRays;
+    pc.shading_modes |= c.shadingModes;
+    for (auto &te : c.timer.timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, s->events[te.first], s->events[te.first + 1]) != hipSuccess) continue;
+        double *acc[6] = {&pc.closest_ms, &pc.shadow_ms, &pc.shade_ms, &pc.resolve_ms, &pc.generate_ms, &pc.film_ms};
+        *acc[te.second] += ms;
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, evStart, evStop) == hipSuccess) pc.render_ms += ms;
+    return PG_OK;
+}
+}  // extern "C++"
+
+// One frame: check, reserve, set up, drive, read back, account.  The description is checked on the host (pg_check_render_desc,
+// pg_render_check.h) before anything is allocated or released.
+static int renderFrame(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays, int mem,
+                       void *streamPtr) {
+    std::string err;
+    const RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
+    if (int st = pg_check_render_desc(rd, facts, err)) return setError(st, "%s", err.c_str());
+    const bool tsBatched = reserveSampleArrays(s, rd);
+    HIP_TRY(hipSetDevice(s->device));
+    FrameCtx c;
+    c.s = s; c.rd = rd; c.stream = (hipStream_t)streamPtr; c.vol = rd->integrator == 1;
+    c.tileSerial = rd->sampler >= PG_SAMPLER_RANDOM && !tsBatched;
+    const int nLocalTiles = pgTileCount(rd);
+    c.rp.rd = *rd;
+    c.rp.nTilesX = (rd->sample_bounds[2] - rd->sample_bounds[0] + 15) / 16;
+    c.rp.nTilesY = (rd->sample_bounds[3] - rd->sample_bounds[1] + 15) / 16;
     // device film / stray buffers (caller's when mem == DEVICE)
-    PgFilmPixel *dFilm = film;
-    PgStraySample *dStrays = strays;
-    int *dNStrays = nStrays;
+    c.dFilm = film; c.dStrays = strays; c.dNStrays = nStrays; c.maxStrays = maxStrays;
     const size_t filmBytes = sizeof(PgFilmPixel) * (size_t)rd->tile_pixels * (size_t)nLocalTiles;
     if (mem == PG_MEM_HOST) {
         HIP_TRY(s->filmDev.alloc(filmBytes));
         HIP_TRY(s->straysDev.alloc(sizeof(PgStraySample) * (size_t)(maxStrays > 0 ? maxStrays : 1)));
         HIP_TRY(s->nStraysDev.alloc(sizeof(int)));
-        dFilm = (PgFilmPixel *)s->filmDev.p; dStrays = (PgStraySample *)s->straysDev.p; dNStrays = (int *)s->nStraysDev.p;
+        c.dFilm = (PgFilmPixel *)s->filmDev.p; c.dStrays = (PgStraySample *)s->straysDev.p; c.dNStrays = (int *)s->nStraysDev.p;
     }
-    if (filmBytes) HIP_TRY(hipMemsetAsync(dFilm, 0, filmBytes, stream));
-    HIP_TRY(hipMemsetAsync(dNStrays, 0, sizeof(int), stream));
-    if (nLocalTiles == 0) {
-        if (mem == PG_MEM_HOST) *nStrays = 0;
-        return PG_OK;
-    }
-    // batch shape: as many whole tiles x samples as fit the path budget
+    if (filmBytes) HIP_TRY(hipMemsetAsync(c.dFilm, 0, filmBytes, c.stream));
+    HIP_TRY(hipMemsetAsync(c.dNStrays, 0, sizeof(int), c.stream));
+    if (nLocalTiles == 0) { if (mem == PG_MEM_HOST) *nStrays = 0; return PG_OK; }
     size_t budget = (size_t)1 << 27;
     if (const char *e = getenv("PG_BATCH_PATHS")) { long v = atol(e); if (v >= 256) budget = (size_t)v; }
-    int sPerBatch = rd->spp, tilesPerBatch = nLocalTiles;
-    if ((size_t)tilesPerBatch * 256 * sPerBatch > budget) {
-        if (rd->filter_general) {
-            // the gathering film kernel needs all samples of a tile in one batch (reference summation order): split by tiles
-            tilesPerBatch = (int)(budget / ((size_t)256 * sPerBatch));
-            if (tilesPerBatch < 1) tilesPerBatch = 1;
-        } else {
-            // prefer all tiles with fewer samples (keeps primary rays coherent and every pixel busy)
-            sPerBatch = (int)(budget / ((size_t)tilesPerBatch * 256));
-            if (sPerBatch < 1) { sPerBatch = 1; tilesPerBatch = (int)(budget / 256); if (tilesPerBatch < 1) tilesPerBatch = 1; }
-        }
-    }
+    const BatchShape shape = pgBatchShape(rd->spp, nLocalTiles, rd->filter_general != 0, budget);
     // tile-serial samplers: one path per tile in flight, slot = the tile's local index
-    const int capacity = tileSerial ? std::max(nLocalTiles, 256) : tilesPerBatch * 256 * sPerBatch;
-    int st = ensureWorkBuffers(s, capacity);
-    if (st != PG_OK) return st;
-    const int QSTRIDE = PG_REGIONS * PG_COUNT_STRIDE;  // ints of counter storage per queue
-    VolState vs;
-    memset(&vs, 0, sizeof(vs));
-    RayQueue vq[2];  // second halves of the through-ray ping-pong (the first halves are q[2] and q[3])
-    if (vol) {
-        const size_t n = (size_t)regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS;
-        if (s->volCapacity < capacity) {
-            for (int i = 0; i < 2; ++i) { HIP_TRY(s->vqo[i].alloc(n * sizeof(float4))); HIP_TRY(s->vqd[i].alloc(n * (sizeof(float4) + (s->d.hasMotion ? sizeof(float) : 0)))); HIP_TRY(s->trAcc[i].alloc(n * sizeof(float4))); }
-            for (int i = 0; i < 3; ++i) HIP_TRY(s->volP1[i].alloc(n * sizeof(float4)));
-            HIP_TRY(s->vCounts.alloc(2 * QSTRIDE * sizeof(int)));
-            HIP_TRY(s->volMedium.alloc(n * sizeof(int)));
-            HIP_TRY(s->misLi.alloc(n * sizeof(float4)));
-            HIP_TRY(s->pdLi.alloc(n * sizeof(float4)));
-            HIP_TRY(s->hitT.alloc((s->d.nGrids > 0 ? 3 : 2) * n * sizeof(float)));
-            s->volCapacity = capacity;
-        }
-        if (s->d.nGrids > 0 && s->gridVertex.bytes < n * sizeof(float4)) HIP_TRY(s->gridVertex.alloc(n * sizeof(float4)));
-        vs.medium = (int *)s->volMedium.p;
-        for (int i = 0; i < 2; ++i) vs.trAcc[i] = (float4 *)s->trAcc[i].p;
-        for (int i = 0; i < 3; ++i) vs.p1[i] = (float4 *)s->volP1[i].p;
-        vs.misLi = (float4 *)s->misLi.p; vs.pdLi = (float4 *)s->pdLi.p;
-        for (int i = 0; i < 2; ++i) { vq[i].o = (float4 *)s->vqo[i].p; vq[i].d = (float4 *)s->vqd[i].p; vq[i].counts = (int *)s->vCounts.p + i * QSTRIDE; }
-    }
-
-    float4 *const hitsMis = (float4 *)s->hitsMain.p + (size_t)regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS;
-    PathState ps;
-    memset(&ps, 0, sizeof(ps));
-    // PathIntegrator, and VolPathIntegrator on scenes without BSSRDF materials or grid media (whose probe-chain / two-phase kernels find a
-    // path's state by its slot): L / beta / meta (/ the ray's medium) in queue order beside each main queue.  (The kernels are compiled for one
-    // or the other: k_shade's QSTATE.)
-    const bool volQ = vol && s->d.nBssrdfs == 0 && s->d.nGrids == 0;
-    if (!vol || volQ) {
-        const size_t n = (size_t)regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS;
-        if (s->qsCapacity < capacity) {
-            for (int i = 0; i < 2; ++i) { HIP_TRY(s->qsL[i].alloc(n * sizeof(float4))); HIP_TRY(s->qsBeta[i].alloc(n * sizeof(float4))); HIP_TRY(s->qsMeta[i].alloc(n * sizeof(int4))); }
-            s->qsCapacity = capacity;
-        }
-        if (volQ && s->qsMedium[0].bytes < n * sizeof(int)) for (int i = 0; i < 2; ++i) HIP_TRY(s->qsMedium[i].alloc(n * sizeof(int)));
-        for (int i = 0; i < 2; ++i) { ps.qs[i].L = (float4 *)s->qsL[i].p; ps.qs[i].beta = (float4 *)s->qsBeta[i].p; ps.qs[i].meta = (int4 *)s->qsMeta[i].p;
-                                      ps.qs[i].medium = volQ ? (int *)s->qsMedium[i].p : nullptr; }
-    }
-    // Subsurface scattering (PathIntegrator): per-slot state of the BSSRDF branch, the job queue and the two probe queues
-    const bool sssOn = s->d.nBssrdfs > 0;
-    SssState sq;
-    memset(&sq, 0, sizeof(sq));
-    RayQueue sssP[2];
-    if (sssOn) {
-        const size_t n = (size_t)regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS;
-        if (s->sssCapacity < capacity) {
-            HIP_TRY(s->sssPo.alloc(n * sizeof(float4))); HIP_TRY(s->sssTarget.alloc(n * sizeof(float4))); HIP_TRY(s->sssCount.alloc(n * sizeof(int2)));
-            for (int i = 0; i < 3; ++i) HIP_TRY(s->sssFrame[i].alloc(n * sizeof(float4)));
-            for (int i = 0; i < 2; ++i) HIP_TRY(s->sssCoef[i].alloc(n * sizeof(float4)));
-            HIP_TRY(s->sssHit.alloc(n * sizeof(float4))); HIP_TRY(s->sssHitO.alloc(n * sizeof(float4))); HIP_TRY(s->sssHitD.alloc(n * sizeof(float4)));
-            HIP_TRY(s->sssHitInst.alloc(n * sizeof(int)));
-            if (s->d.hasMotion) HIP_TRY(s->sssHitXf.alloc((s->d.hasNest ? 2 : 1) * n * PG_XF_STRIDE * sizeof(float)));  // the chosen hit's interpolated instance matrices
-            HIP_TRY(s->sssMedium.alloc(n * sizeof(int2)));
-            for (int i = 0; i < 3; ++i) { HIP_TRY(s->sssQo[i].alloc(n * sizeof(float4))); HIP_TRY(s->sssQd[i].alloc(n * (sizeof(float4) + (s->d.hasMotion ? sizeof(float) : 0)))); }  // (+ the probe rays' times: PG_QUEUE_TIMES)
-            HIP_TRY(s->sssCounts.alloc(3 * QSTRIDE * sizeof(int)));
-            HIP_TRY(s->sssTail.alloc(QSTRIDE * sizeof(int)));
-            s->sssCapacity = capacity;
-        }
-        sq.po = (float4 *)s->sssPo.p; sq.target = (float4 *)s->sssTarget.p; sq.count = (int2 *)s->sssCount.p;
-        for (int i = 0; i < 3; ++i) sq.frame[i] = (float4 *)s->sssFrame[i].p;
-        for (int i = 0; i < 2; ++i) sq.coef[i] = (float4 *)s->sssCoef[i].p;
-        sq.hit = (float4 *)s->sssHit.p; sq.hitO = (float4 *)s->sssHitO.p; sq.hitD = (float4 *)s->sssHitD.p; sq.hitInst = (int *)s->sssHitInst.p; sq.hitXf = (float *)s->sssHitXf.p; sq.hitXfNest = (int)n; sq.medium = (int2 *)s->sssMedium.p;
-        sq.qjob.o = (float4 *)s->sssQo[0].p; sq.qjob.d = (float4 *)s->sssQd[0].p; sq.qjob.counts = (int *)s->sssCounts.p;
-        for (int i = 0; i < 2; ++i) { sssP[i].o = (float4 *)s->sssQo[1 + i].p; sssP[i].d = (float4 *)s->sssQd[1 + i].p; sssP[i].counts = (int *)s->sssCounts.p + (1 + i) * QSTRIDE; }
-    }
-    ps.L = (float4 *)s->stL.p; ps.beta = (float4 *)s->stBeta.p; ps.meta = (int4 *)s->stMeta.p;
-    ps.pdLight = (float4 *)s->pdLight.p; ps.pdMis = (float4 *)s->pdMis.p; ps.pdBeta = (float4 *)s->pdBeta.p; ps.pdInfo = (int4 *)s->pdInfo.p;
-    int *counts = (int *)s->counts.p;
-    RayQueue q[4];
-    for (int i = 0; i < 4; ++i) { q[i].o = (float4 *)s->qo[i].p; q[i].d = (float4 *)s->qd[i].p; q[i].counts = counts + i * QSTRIDE; }
-    // sum of a queue's region counters in a host copy of the counter block
-    auto queueTotal = [&](const int *blk, int qi) { uint64_t t = 0; for (int r = 0; r < PG_REGIONS; ++r) t += (uint64_t)blk[qi * QSTRIDE + r * PG_COUNT_STRIDE]; return t; };
-    TraceCounters *cnClosest = (TraceCounters *)s->traceCn.p, *cnShadow = cnClosest + 1;
-    unsigned long long *lightTests = (unsigned long long *)s->lightTests.p;
-
-    size_t ev = 0;
-    std::vector<std::pair<size_t, int>> timed;  // (event index, kernel: 0 closest-hit, 1 any-hit, 2 shade, 3 resolve, 4 generate, 5 film)
-    // HIP events around one launch on `st_` (the stream the kernel runs on); per-kernel times are only meaningful while the
-    // any-hit launch does not share the chip with the closest-hit launch (PG_OVERLAP_SHADOW=0, the default)
-    // (not in the tile-serial mode: its hundreds of thousands of small launches would each need a pair of events)
-    const bool timing = !tileSerial;
-#define PG_TIMED(kind_, st_, launch_) do { if (!timing) { launch_; break; } hipEvent_t a_ = getEvent(s, ev), b_ = getEvent(s, ev + 1); \
-        if (!a_ || !b_) return setError(PG_ERR_DEVICE, "hipEventCreate failed"); \
-        timed.push_back({ev, kind_}); ev += 2; HIP_TRY(hipEventRecord(a_, st_)); launch_; HIP_TRY(hipEventRecord(b_, st_)); } while (0)
-    hipEvent_t evStart = getEvent(s, ev++), evStop = getEvent(s, ev++);
+    if (int e = setUpFrame(c, c.tileSerial ? std::max(nLocalTiles, 256) : shape.tiles * 256 * shape.samples)) return e;
+    c.timer.s = s; c.timer.on = !c.tileSerial;
+    hipEvent_t evStart = getEvent(s, 0), evStop = getEvent(s, 1);
     if (!evStart || !evStop) return setError(PG_ERR_DEVICE, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(evStart, stream));
-    // Sparse "spatial" light tables: after a shading launch, compute the distributions of the voxels its lanes asked for and
-    // shade the entries that waited for them (one host round trip per launch while the table warms up; none once every
-    // voxel the image touches exists -- the tables stay with the scene).
-    rp.retryList = (int *)s->retryList.p;
-    if (s->matLobes.p && s->matHead.p) { rp.matPre.lobes = (float4 *)s->matLobes.p; rp.matPre.head = (float4 *)s->matHead.p; rp.matPre.stride = s->matStride; }
-    auto settleLightTables = [&](const std::function<void()> &reshade) -> int {
-        if (!s->d.sparseLights) return PG_OK;
-        int cnt[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(cnt, s->voxelCounters.p, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (cnt[0] == 0 && cnt[1] == 0) return PG_OK;
-        if (s->poolUsed + cnt[0] > s->poolSlots)
-            return setError(PG_ERR_UNSUPPORTED, "spatial light distribution: %d voxels x %d lights exceed the table pool (%d voxels); use "
-                                                "\"lightsamplestrategy\" \"power\" or \"uniform\"", s->poolUsed + cnt[0], s->d.nLights, s->poolSlots);
-        launch_light_tables_sparse(s->d, (float *)s->distTable.p, (const int *)s->voxelRequests.p, cnt[0], s->poolUsed, stream);
-        s->poolUsed += cnt[0];
-        HIP_TRY(hipMemsetAsync(s->voxelCounters.p, 0, sizeof(cnt), stream));
-        if (cnt[1] > 0) { rp.retryCount = cnt[1]; reshade(); rp.retryCount = 0; }
-        return PG_OK;
-    };
-    uint64_t closestRays = 0, shadowRays = 0, cameraRays = 0, closestLaunches = 0, shadowLaunches = 0;
-    uint64_t shadeLaunches = 0, resolveLaunches = 0, shadeItems = 0, misRays = 0, shadingModes = 0;
-    // PgCounters::shading_modes: which k_shade<MODE> this frame's shading launches are (pg_shade_mode, the launch functions' own choice)
-    auto noteShading = [&](const DScene &dsc, bool vol, bool sss, bool gridPhase) {
-        const int mode = pg_shade_mode(dsc, rp, vol, sss, gridPhase);
-        shadingModes |= 1ull << mode;
-        if (mode == 3) shadingModes |= PG_SHADING_MATERIAL_PREPASS;
-        if (mode == 2 && !gridPhase && !(sss && dsc.nBssrdfs > 0) && s->matStride > 0) shadingModes |= PG_SHADING_LISTS_DID_NOT_FIT;
-    };
-    std::vector<int> hostCounts;  // read back once per batch at the end (pinned copy not needed: tiny)
-    DeviceBuffer countLog;        // per-bounce queue sizes, copied back after the batch for the ray statistics
-    // (64-bit: maxdepth comes from the caller / the scene file.)  Bounce launches are enqueued without looking at the queues, so
-    // a huge maxdepth is bounded here: beyond PG_MAX_BLIND_BOUNCES the host looks at the main queue every 32 bounces and stops
-    // when it is empty (Russian roulette ends every path), and a frame whose paths outlive PG_MAX_BOUNCES fails loudly.
-    const long long PG_MAX_BLIND_BOUNCES = 64, PG_MAX_BOUNCES = 4096;
-    const long long wantIters = (long long)rd->max_depth + 1 + (s->hasNullMaterial ? 64 : 0);
-    const int maxIters = (int)std::min<long long>(wantIters, PG_MAX_BOUNCES);
-    HIP_TRY(countLog.alloc(sizeof(int) * 4 * QSTRIDE * (size_t)(maxIters + 1)));
-    std::vector<int> curQueueOfBounce;
-
-    // One batch of paths from their camera rays (`generate` fills the first main queue) to their film samples (`film`): all the
-    // bounces of the rp.capacity path slots described by rp.
-    auto tracePaths = [&](const std::function<void()> &generate, const std::function<void()> &filmSamples) -> int {
-        {
-            for (int i = 0; i < 4; ++i) q[i].regionCap = regionCapFor(rp.capacity, s->d.sparseLights != 0);
-            if (sssOn) { sq.qjob.regionCap = q[0].regionCap; sssP[0].regionCap = sssP[1].regionCap = q[0].regionCap; }
-            curQueueOfBounce.clear();
-            HIP_TRY(hipMemsetAsync(counts, 0, 4 * QSTRIDE * sizeof(int), stream));
-            int cur = 0;  // main queue index (0/1 ping-pong); 2 = shadow, 3 = MIS
-            PG_TIMED(4, stream, generate());
-            if (vol) {
-                // VolPathIntegrator::Li (volpath.cpp:72-186).  Per loop iteration: closest-hit(main rays, with the hits' ray
-                // parameters) -> shade with medium sampling -> the transmittance rays of the light samples and of the
-                // BSDF/phase samples, re-traced until none is left under way (light.cpp:63-81, scene.cpp:57-70) -> resolve.
-                // Crossing a surface without a material does not count as a bounce, so the loop runs until the queue is empty.
-                DScene dv = s->d;
-                dv.ext = 1;  // the general shading kernels
-                const int n1 = regionCapFor(capacity, s->d.sparseLights != 0) * PG_REGIONS;
-                float *hitT = (float *)s->hitT.p;
-                for (int i = 0; i < 2; ++i) vq[i].regionCap = q[0].regionCap;
-                launch_fill_int(vs.medium, rd->camera_medium + 1, rp.capacity, stream);  // camera rays start in the camera's medium (camera.h:78)
-                std::vector<int> blk(4 * QSTRIDE), vblk(2 * QSTRIDE);
-                auto readCounts = [&]() -> int {
-                    HIP_TRY(hipMemcpyAsync(blk.data(), counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipMemcpyAsync(vblk.data(), s->vCounts.p, 2 * QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    return PG_OK;
-                };
-                if (int e = readCounts()) return e;
-                uint64_t nMain = queueTotal(blk.data(), cur);
-                cameraRays += nMain;
-                for (int iter = 0; nMain > 0; ++iter) {
-                    if (iter > 100000) return setError(PG_ERR_DEVICE, "pg_render: volpath loop did not terminate");
-                    const int nxt = cur ^ 1;
-                    PG_TIMED(0, stream, launch_closest(dv, s->trace, q[cur], (float4 *)s->hitsMain.p, hitT, cnClosest, (int *)s->cursors.p, (int *)s->cullGuard.p, stream));
-                    ++closestLaunches; closestRays += nMain; shadeItems += nMain;
-                    HIP_TRY(hipMemsetAsync(counts + nxt * QSTRIDE, 0, QSTRIDE * sizeof(int), stream));
-                    HIP_TRY(hipMemsetAsync(counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
-                    if (sssOn) HIP_TRY(hipMemsetAsync(sq.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
-                    const SssState *sssArg = sssOn ? &sq : nullptr;
-                    // a scene with a grid medium shades in two phases around the transmittance rays (k_shade<., ., ., GRID>)
-                    const bool gridOn = s->d.nGrids > 0;
-                    float4 *gridVertex = (float4 *)s->gridVertex.p;
-                    // (GlobalSamplers, dense light tables: the tile-serial streams and the deferred vertices of sparse tables draw in the shading kernel)
-                    float2 *volPre = (s->volOrder && !tileSerial && !s->d.sparseLights) ? (float2 *)s->volPre.p : nullptr;
-                    rp.volPre = volPre;
-                    rp.order = (s->d.primClass || volPre) ? (const int *)s->shadeOrder.p : nullptr;  // (the second phase of a grid scene takes the same order)
-                    PG_TIMED(2, stream, (launch_shade_order_vol(dv, rp, ps, vs, q[cur], (const float4 *)s->hitsMain.p, hitT, (int *)s->shadeOrder.p, volPre, stream, cur), launch_shade_vol(dv, rp, ps, vs, q[cur], (const float4 *)s->hitsMain.p, hitT, q[nxt], q[2], q[3], lightTests, stream, sssArg, gridVertex, gridOn ? 1 : 0, cur)));
-                    ++shadeLaunches; noteShading(dv, true, sssArg != nullptr, gridOn);
-                    if (int e = settleLightTables([&]() { launch_shade_vol(dv, rp, ps, vs, q[cur], (const float4 *)s->hitsMain.p, hitT, q[nxt], q[2], q[3], lightTests, stream, sssArg, gridVertex, gridOn ? 1 : 0, cur); })) return e;
-                    // through rays: kind 0 = light samples (q[2] <-> vq[0]), kind 1 = BSDF / phase samples (q[3] <-> vq[1]), re-traced
-                    // until none is left under way
-                    auto throughRays = [&]() -> int {
-                        if (gridOn) {
-                            // ratio tracking draws from the path's sampler: a path's kind-0 ray (visibility.Tr) runs to its end before
-                            // its kind-1 ray (IntersectTr after the BSDF sample) starts, as in EstimateDirect; one queue pair at a time
-                            for (int kind = 0; kind < 2; ++kind) {
-                                RayQueue tk[2] = {kind == 0 ? q[2] : q[3], vq[kind]};
-                                int tc = 0;
-                                for (int pass = 0;; ++pass) {
-                                    if (pass > 100000) return setError(PG_ERR_DEVICE, "pg_render: transmittance loop did not terminate");
-                                    if (int e = readCounts()) return e;
-                                    const uint64_t nk = tc == 0 ? queueTotal(blk.data(), 2 + kind) : queueTotal(vblk.data(), kind);
-                                    if (nk == 0) break;
-                                    // (results at the offset the kind's through kernel reads them from)
-                                    const size_t off = (size_t)(1 + kind) * n1;  // part 0 keeps the main rays' hits for phase 2
-                                    float4 *hk = (float4 *)s->hitsMain.p + off;
-                                    DScene dk = dv;
-                                    if (dk.hitInst) dk.hitInst += off;
-                                    if (dk.animXf) dk.animXf += off * PG_XF_STRIDE;
-                                    PG_TIMED(0, stream, launch_closest(dk, s->trace, tk[tc], hk, hitT + off, cnClosest, (int *)s->cursors.p, (int *)s->cullGuard.p, stream));
-                                    ++closestLaunches; closestRays += nk;
-                                    HIP_TRY(hipMemsetAsync(tk[tc ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
-                                    launch_through(dv, ps, vs, kind, tk[tc], (const float4 *)s->hitsMain.p, hitT, (int)off, tk[tc ^ 1], stream, &rp);
-                                    tc ^= 1;
-                                }
-                            }
-                            return PG_OK;
-                        }
-                        RayQueue tq[2][2] = {{q[2], vq[0]}, {q[3], vq[1]}};
-                        int tcur = 0;
-                        for (int pass = 0;; ++pass) {
-                            if (pass > 100000) return setError(PG_ERR_DEVICE, "pg_render: transmittance loop did not terminate");
-                            if (int e = readCounts()) return e;
-                            const uint64_t n0 = tcur == 0 ? queueTotal(blk.data(), 2) : queueTotal(vblk.data(), 0);
-                            const uint64_t n1q = tcur == 0 ? queueTotal(blk.data(), 3) : queueTotal(vblk.data(), 1);
-                            if (n0 + n1q == 0) break;
-                            PG_TIMED(0, stream, launch_closest2(dv, s->trace, tq[0][tcur], tq[1][tcur], (float4 *)s->hitsMain.p, n1, cnClosest, (int *)s->cursors.p, (int *)s->cullGuard.p, stream, hitT));
-                            ++closestLaunches; closestRays += n0 + n1q;
-                            HIP_TRY(hipMemsetAsync(tq[0][tcur ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
-                            HIP_TRY(hipMemsetAsync(tq[1][tcur ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
-                            launch_through(dv, ps, vs, 0, tq[0][tcur], (const float4 *)s->hitsMain.p, hitT, 0, tq[0][tcur ^ 1], stream);
-                            launch_through(dv, ps, vs, 1, tq[1][tcur], (const float4 *)s->hitsMain.p, hitT, n1, tq[1][tcur ^ 1], stream);
-                            tcur ^= 1;
-                        }
-                        return PG_OK;
-                    };
-                    if (int e = throughRays()) return e;
-                    PG_TIMED(3, stream, launch_resolve_vol(dv, ps, vs, q[cur], stream, cur));
-                    ++resolveLaunches;
-                    if (gridOn) {  // phase 2: the vertices' next directions, drawn behind the transmittance rays' numbers
-                        PG_TIMED(2, stream, launch_shade_vol(dv, rp, ps, vs, q[cur], (const float4 *)s->hitsMain.p, hitT, q[nxt], q[2], q[3], lightTests, stream, sssArg, gridVertex, 2));
-                        ++shadeLaunches;
-                        if (int e = readCounts()) return e;
-                    }
-                    if (sssOn) {
-                        // ---- the BSSRDF branch (volpath.cpp:151-176) of the paths k_shade handed over: probe chains (two walks), exit
-                        // vertices, their transmittance rays and resolve; the exit vertices' next rays join q[nxt], which is
-                        // traced as a whole at the start of the next iteration
-                        std::vector<int> jb(QSTRIDE);
-                        auto regionSum = [&](const int *dev, uint64_t &total) -> int {
-                            HIP_TRY(hipMemcpyAsync(jb.data(), dev, QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, stream));
-                            HIP_TRY(hipStreamSynchronize(stream));
-                            total = 0;
-                            for (int r = 0; r < PG_REGIONS; ++r) total += (uint64_t)jb[r * PG_COUNT_STRIDE];
-                            return PG_OK;
-                        };
-                        uint64_t nJobs = 0;
-                        if (int e = regionSum(sq.qjob.counts, nJobs)) return e;
-                        if (nJobs > 0) {
-                            for (int pass = 1; pass <= 2; ++pass) {
-                                RayQueue curQ = sq.qjob;
-                                uint64_t nRays = nJobs;
-                                for (int step = 0; nRays > 0; ++step) {
-                                    if (step > 1000000) return setError(PG_ERR_DEVICE, "pg_render: a BSSRDF probe chain did not terminate");
-                                    RayQueue outQ = sssP[step & 1];
-                                    HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), stream));
-                                    launch_closest(dv, s->trace, curQ, (float4 *)s->hitsMain.p, nullptr, pass == 1 ? cnClosest : cnClosest + 2, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-                                    if (pass == 1) { closestRays += nRays; ++closestLaunches; }
-                                    launch_sss_probe(dv, sq, pass, curQ, (const float4 *)s->hitsMain.p, outQ, stream, true, step == 0);
-                                    if (int e = regionSum(outQ.counts, nRays)) return e;
-                                    curQ = outQ;
-                                }
-                            }
-                            HIP_TRY(hipMemsetAsync(counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
-                            // (a grid medium's ratio tracking draws from the paths' samplers: the exit vertices' transmittance rays run between their direct
-                            // lighting and their next directions, as at k_shade's vertices -- k_sss_exit in two phases; gridVertex is free again by now)
-                            launch_sss_exit(dv, rp, ps, sq, q[nxt], q[2], q[3], lightTests, stream, nxt, true, vs, gridOn ? 1 : 0, gridVertex);
-                            ++shadeLaunches; shadeItems += nJobs;
-                            if (int e = throughRays()) return e;
-                            launch_resolve_vol(dv, ps, vs, sq.qjob, stream);
-                            ++resolveLaunches;
-                            if (gridOn) { launch_sss_exit(dv, rp, ps, sq, q[nxt], q[2], q[3], lightTests, stream, nxt, true, vs, 2, gridVertex); ++shadeLaunches; }
-                        }
-                        if (int e = readCounts()) return e;
-                    }
-                    // the last pass of the through loop read the counters: the main queue's size comes from the same block
-                    nMain = queueTotal(blk.data(), nxt);
-                    cur = nxt;
-                }
-                filmSamples();
-                HIP_TRY(hipStreamSynchronize(stream));
-                return PG_OK;
-            }
-            // Launch order per bounce b (one stream): shade(b) -> any-hit(shadow rays of b) -> closest-hit(main rays of b+1
-            // and MIS rays of b in ONE launch) -> resolve(b).  The first closest-hit launch traces the camera rays alone.
-            auto timedClosest = [&](RayQueue qa, float4 *ha, const RayQueue *qb, float4 *hb) -> int {
-                hipEvent_t a = nullptr, b = nullptr;
-                if (timing) { a = getEvent(s, ev); b = getEvent(s, ev + 1); timed.push_back({ev, 0}); ev += 2; HIP_TRY(hipEventRecord(a, stream)); }
-                if (qb) launch_closest2(s->d, s->trace, qa, *qb, ha, (int)(hb - ha), cnClosest, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-                else launch_closest(s->d, s->trace, qa, ha, nullptr, cnClosest, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-                if (timing) HIP_TRY(hipEventRecord(b, stream));
-                ++closestLaunches;
-                return PG_OK;
-            };
-            if (int e = timedClosest(q[cur], (float4 *)s->hitsMain.p, nullptr, nullptr)) return e;
-            int iters = 0;
-            for (int bounce = 0; bounce < maxIters; ++bounce, ++iters) {
-                const int nxt = cur ^ 1;
-                HIP_TRY(hipMemsetAsync(counts + nxt * QSTRIDE, 0, QSTRIDE * sizeof(int), stream));
-                HIP_TRY(hipMemsetAsync(counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
-                if (sssOn) HIP_TRY(hipMemsetAsync(sq.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
-                const SssState *sssArg = sssOn ? &sq : nullptr;
-                rp.order = s->d.primClass ? (const int *)s->shadeOrder.p : nullptr;
-                PG_TIMED(2, stream, (launch_shade_order(s->d, q[cur], (const float4 *)s->hitsMain.p, (int *)s->shadeOrder.p, stream), launch_shade(s->d, rp, ps, q[cur], (const float4 *)s->hitsMain.p, q[nxt], q[2], q[3], lightTests, stream, cur, sssArg)));
-                ++shadeLaunches; noteShading(s->d, false, sssArg != nullptr, false);
-                if (int e = settleLightTables([&]() { launch_shade(s->d, rp, ps, q[cur], (const float4 *)s->hitsMain.p, q[nxt], q[2], q[3], lightTests, stream, cur, sssArg); })) return e;
-                // paths that reach maxdepth neither continue nor sample lights (path.cpp:104): nothing left to trace
-                const bool lastDepth = !s->hasNullMaterial && bounce >= rd->max_depth;
-                if (!lastDepth) {
-                    // The shadow rays of this bounce and the closest-hit rays of the next depend only on shade(b): the any-hit
-                    // launch goes to a second stream so that its blocks fill the chip while the closest-hit launch's
-                    // persistent waves drain (and vice versa); resolve(b) joins both.
-                    // (tile-serial samplers: a handful of rays per launch, each a chain of dependent fetches -- both launches are
-                    // latency-bound and run side by side)
-                    const bool overlap = s->overlapShadow || tileSerial;
-                    hipStream_t sst = overlap ? s->shadowStream : stream;
-                    if (overlap) {
-                        HIP_TRY(hipEventRecord(s->evShaded, stream));
-                        HIP_TRY(hipStreamWaitEvent(sst, s->evShaded, 0));
-                    }
-#define PG_Q_SHADOW q[2]
-                    hipEvent_t a = nullptr, b = nullptr;
-                    if (timing) { a = getEvent(s, ev); b = getEvent(s, ev + 1); timed.push_back({ev, 1}); ev += 2; HIP_TRY(hipEventRecord(a, sst)); }
-                    launch_anyhit(s->d, s->trace, PG_Q_SHADOW, (int *)s->occluded.p, cnShadow, (int *)s->cursors2.p, sst);
-                    if (timing) HIP_TRY(hipEventRecord(b, sst));
-                    ++shadowLaunches;
-                    if (overlap) HIP_TRY(hipEventRecord(s->evShadowed, sst));
-                    if (int e = timedClosest(q[nxt], (float4 *)s->hitsMain.p, &q[3], hitsMis)) return e;
-                    if (overlap) HIP_TRY(hipStreamWaitEvent(stream, s->evShadowed, 0));
-                    PG_TIMED(3, stream, launch_resolve(s->d, ps, q[cur], q[3], (const int *)s->occluded.p, (const float4 *)hitsMis, stream, cur, lightTests));
-                    ++resolveLaunches;
-                }
-                // log this bounce's queue sizes
-                HIP_TRY(hipMemcpyAsync((int *)countLog.p + 4 * QSTRIDE * (size_t)bounce, counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToDevice, stream));
-                curQueueOfBounce.push_back(cur);
-                if (sssOn && !lastDepth) {
-                    // ---- the BSSRDF branch of Li (path.cpp:152-174) for the paths k_shade handed over: the probe chains of
-                    // SeparableBSSRDF::Sample_Sp walked twice through the traversal kernel (count the hits on the material; stop at
-                    // the chosen one), then the exit vertices: their shadow / MIS rays, the tail of the next bounce's queue that
-                    // their next rays form, and the resolve of their direct lighting.  One counter read-back per step.
-                    std::vector<int> jb(QSTRIDE);
-                    auto regionSum = [&](const int *dev, uint64_t &total) -> int {
-                        HIP_TRY(hipMemcpyAsync(jb.data(), dev, QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        total = 0;
-                        for (int r = 0; r < PG_REGIONS; ++r) total += (uint64_t)jb[r * PG_COUNT_STRIDE];
-                        return PG_OK;
-                    };
-                    uint64_t nJobs = 0;
-                    if (int e = regionSum(sq.qjob.counts, nJobs)) return e;
-                    if (nJobs > 0) {
-                        const size_t n1 = (size_t)q[0].regionCap * PG_REGIONS;
-                        DScene dprobe = s->d;  // the probe rays' hits go where the MIS rays' went (k_resolve is done with those)
-                        if (dprobe.hitInst) dprobe.hitInst += n1;
-                        if (dprobe.animXf) dprobe.animXf += n1 * PG_XF_STRIDE;
-                        for (int pass = 1; pass <= 2; ++pass) {
-                            RayQueue curQ = sq.qjob;
-                            uint64_t nRays = nJobs;
-                            for (int step = 0; nRays > 0; ++step) {
-                                if (step > 1000000) return setError(PG_ERR_DEVICE, "pg_render: a BSSRDF probe chain did not terminate");
-                                RayQueue outQ = sssP[step & 1];
-                                HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), stream));
-                                // the second walk repeats queries the reference makes once: its rays and traversal work are not counted
-                                launch_closest(dprobe, s->trace, curQ, hitsMis, nullptr, pass == 1 ? cnClosest : cnClosest + 2, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-                                if (pass == 1) { closestRays += nRays; ++closestLaunches; }
-                                launch_sss_probe(dprobe, sq, pass, curQ, hitsMis, outQ, stream);
-                                if (int e = regionSum(outQ.counts, nRays)) return e;
-                                curQ = outQ;
-                            }
-                        }
-                        HIP_TRY(hipMemcpyAsync(s->sssTail.p, counts + nxt * QSTRIDE, QSTRIDE * sizeof(int), hipMemcpyDeviceToDevice, stream));
-                        HIP_TRY(hipMemsetAsync(counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
-                        launch_sss_exit(s->d, rp, ps, sq, q[nxt], q[2], q[3], lightTests, stream, nxt, false, vs);
-                        ++shadeLaunches; shadeItems += nJobs;
-                        launch_anyhit(s->d, s->trace, q[2], (int *)s->occluded.p, cnShadow, (int *)s->cursors2.p, stream);
-                        ++shadowLaunches;
-                        launch_closest2(s->d, s->trace, q[nxt], q[3], (float4 *)s->hitsMain.p, (int)n1, cnClosest, (int *)s->cursors.p, (int *)s->cullGuard.p, stream, nullptr,
-                                        (const int *)s->sssTail.p);
-                        ++closestLaunches;
-                        launch_resolve(s->d, ps, sq.qjob, q[3], (const int *)s->occluded.p, (const float4 *)hitsMis, stream, cur);
-                        ++resolveLaunches;
-                        uint64_t nSh = 0, nMis = 0;
-                        if (int e = regionSum(counts + 2 * QSTRIDE, nSh)) return e;
-                        if (int e = regionSum(counts + 3 * QSTRIDE, nMis)) return e;
-                        shadowRays += nSh; closestRays += nMis; misRays += nMis;  // (the next rays are counted with the next bounce's queue)
-                    }
-                }
-                cur = nxt;
-                if ((s->hasNullMaterial && bounce >= rd->max_depth) || (bounce >= PG_MAX_BLIND_BOUNCES && bounce % 32 == 0)) {
-                    std::vector<int> blk(4 * QSTRIDE);
-                    HIP_TRY(hipMemcpyAsync(blk.data(), counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    if (queueTotal(blk.data(), cur) == 0) { ++iters; break; }
-                }
-            }
-            if (iters == maxIters && wantIters > maxIters) {  // the last allowed bounce: is anything still alive?
-                std::vector<int> blk(4 * QSTRIDE);
-                HIP_TRY(hipMemcpyAsync(blk.data(), counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (queueTotal(blk.data(), cur) != 0) return setError(PG_ERR_UNSUPPORTED, "paths longer than %lld vertices (maxdepth %d)", PG_MAX_BOUNCES, rd->max_depth);
-            }
-            PG_TIMED(5, stream, filmSamples());
-            hostCounts.resize(4 * QSTRIDE * (size_t)iters);
-            HIP_TRY(hipMemcpyAsync(hostCounts.data(), countLog.p, sizeof(int) * 4 * QSTRIDE * (size_t)iters, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            for (int b = 0; b < iters; ++b) {
-                const int *blk = hostCounts.data() + 4 * QSTRIDE * (size_t)b;
-                closestRays += queueTotal(blk, curQueueOfBounce[b]) + queueTotal(blk, 3);
-                shadowRays += queueTotal(blk, 2);
-                shadeItems += queueTotal(blk, curQueueOfBounce[b]);
-                misRays += queueTotal(blk, 3);
-                if (getenv("PG_PRINT_COUNTS"))
-                    fprintf(stderr, "pg_render: bounce %d main %llu shadow %llu mis %llu\n", b, (unsigned long long)queueTotal(blk, curQueueOfBounce[b]),
-                            (unsigned long long)queueTotal(blk, 2), (unsigned long long)queueTotal(blk, 3));
-            }
-            if (iters > 0) cameraRays += queueTotal(hostCounts.data(), curQueueOfBounce[0]);
-        }
-        return PG_OK;
-    };
-    const std::function<void()> filmBatch = [&]() {
-        if (rd->filter_general) launch_film_general(rp, ps, dFilm, stream);
-        else launch_film(rp, ps, dFilm, dStrays, maxStrays, dNStrays, stream);
-    };
-    if (tsBatched) {  // every pixel's sample arrays, one lane per tile (the tile's stream in the reference's pixel order)
-        const size_t nArr = (size_t)nLocalTiles * 256 * (size_t)rd->sampler_dims * (size_t)rd->spp;
-        HIP_TRY(s->tsState.alloc(sizeof(TileSamplerState) * (size_t)nLocalTiles));
-        if (s->ts1.bytes < sizeof(float) * (nArr + 1) || s->ts2.bytes < sizeof(float) * 2 * (nArr + 1)) return setError(PG_ERR_DEVICE, "pg_render: sample arrays not allocated");  // (taken where tsBatched was decided)
-        HIP_TRY(s->tsOverflow.alloc(sizeof(int)));
-        HIP_TRY(hipMemsetAsync(s->tsOverflow.p, 0, sizeof(int), stream));
-        s->d.ts = (TileSamplerState *)s->tsState.p; s->d.ts1 = (float *)s->ts1.p; s->d.ts2 = (float *)s->ts2.p;
-        s->d.tsDims = rd->sampler_dims; s->d.tsSpp = rd->spp; s->d.tsBatched = 1; s->d.tsOverflow = (int *)s->tsOverflow.p;
-        rp.tileLocal0 = 0; rp.nTilesBatch = nLocalTiles; rp.s0 = 0; rp.sCount = 1; rp.capacity = nLocalTiles;
-        launch_ts_init(s->d, rp, stream);
-        rp.tsGuessSkew = getenv("PG_TS_GUESS_SKEW") ? atoi(getenv("PG_TS_GUESS_SKEW")) : 0;
-        launch_ts_start_tile(s->d, rp, stream);
-    }
-    if (!tileSerial) {
-        for (int tile0 = 0; tile0 < nLocalTiles; tile0 += tilesPerBatch)
-            for (int s0 = 0; s0 < rd->spp; s0 += sPerBatch) {
-                rp.tileLocal0 = tile0;
-                rp.nTilesBatch = std::min(tilesPerBatch, nLocalTiles - tile0);
-                rp.s0 = s0;
-                rp.sCount = std::min(sPerBatch, rd->spp - s0);
-                rp.capacity = rp.nTilesBatch * 256 * rp.sCount;
-                if (int e = tracePaths([&]() { launch_generate(s->d, rp, ps, q[0], stream); }, filmBatch)) return e;
-            }
-    } else {
-        // The samplers that draw from one RNG stream per tile (random, stratified, 02sequence, maxmindist): a tile's pixels, a
-        // pixel's samples and a sample's draws consume the stream in order, and how many numbers a path takes depends on the
-        // path -- so a tile has ONE path in flight, and the wavefront is one path of every tile: pixel (lx, ly) of all tiles,
-        // sample by sample (integrator.cpp:247-332).  Tiles clipped by the image skip the pixels they do not have.
-        const int nd = rd->sampler == PG_SAMPLER_RANDOM ? 0 : rd->sampler_dims;
-        HIP_TRY(s->tsState.alloc(sizeof(TileSamplerState) * (size_t)nLocalTiles));
-        HIP_TRY(s->ts1.alloc(sizeof(float) * ((size_t)nLocalTiles * nd * rd->spp + 1)));
-        HIP_TRY(s->ts2.alloc(sizeof(float) * 2 * ((size_t)nLocalTiles * nd * rd->spp + 1)));
-        s->d.ts = (TileSamplerState *)s->tsState.p; s->d.ts1 = (float *)s->ts1.p; s->d.ts2 = (float *)s->ts2.p;
-        s->d.tsDims = nd; s->d.tsSpp = rd->spp;
-        rp.tileLocal0 = 0; rp.nTilesBatch = nLocalTiles; rp.s0 = 0; rp.sCount = 1; rp.capacity = nLocalTiles;
-        launch_ts_init(s->d, rp, stream);
-        int err = PG_OK;
-        for (int ly = 0; ly < 16 && !err; ++ly)
-            for (int lx = 0; lx < 16 && !err; ++lx) {
-                if (rd->sample_bounds[0] + lx >= rd->sample_bounds[2] || rd->sample_bounds[1] + ly >= rd->sample_bounds[3]) continue;  // no tile has this pixel
-                launch_ts_start_pixel(s->d, rp, lx, ly, stream);
-                for (int sn = 0; sn < rd->spp && !err; ++sn)
-                    err = tracePaths([&]() { launch_ts_generate(s->d, rp, ps, q[0], sn, stream); },
-                                     [&]() { launch_ts_film(s->d, rp, ps, dFilm, dStrays, maxStrays, dNStrays, stream); });
-            }
-        s->d.ts = nullptr; s->d.ts1 = s->d.ts2 = nullptr;
-        if (err) return err;
-    }
-    if (tsBatched) {
-        int over = 0;
-        HIP_TRY(hipMemcpyAsync(&over, s->tsOverflow.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        s->d.ts = nullptr; s->d.ts1 = s->d.ts2 = nullptr; s->d.tsBatched = 0; s->d.tsOverflow = nullptr;
-        if (over & 2) return setError(PG_ERR_DEVICE, "pg_render: the start offsets of a tile's pixel sample arrays did not converge (k_ts_start_tile, internal error)");
-        if (over) return setError(PG_ERR_DEVICE, "pg_render: a path drew beyond the %d sampled dimensions of the batched pixel sampler (internal error)", rd->sampler_dims);
-    }
-    HIP_TRY(hipEventRecord(evStop, stream));
+    HIP_TRY(hipEventRecord(evStart, c.stream));
+    HIP_TRY(c.countLog.alloc(sizeof(int) * 4 * QSTRIDE * (size_t)(c.lim.maxIters + 1)));
+    if (int e = c.tileSerial ? renderTileSerial(c, nLocalTiles) : renderBatched(c, nLocalTiles, shape, tsBatched)) return e;
+    HIP_TRY(hipEventRecord(evStop, c.stream));
     HIP_TRY(hipGetLastError());
     int hostNStrays = 0;
-    HIP_TRY(hipMemcpyAsync(&hostNStrays, dNStrays, sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (mem == PG_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(film, dFilm, filmBytes, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        int nCopy = std::min(hostNStrays, (int)maxStrays);
-        if (nCopy > 0) HIP_TRY(hipMemcpy(strays, dStrays, sizeof(PgStraySample) * (size_t)nCopy, hipMemcpyDeviceToHost));
-        *nStrays = nCopy;
-    } else {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (hostNStrays > maxStrays) { int v = maxStrays; HIP_TRY(hipMemcpy(dNStrays, &v, sizeof(int), hipMemcpyHostToDevice)); }
-    }
-    // statistics
-    TraceCounters tc[2];
-    unsigned long long lt = 0;
-    HIP_TRY(hipMemcpy(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost));
-    {
-        std::vector<unsigned long long> shards(PG_LIGHT_TEST_SHARDS * PG_LIGHT_TEST_STRIDE);
-        HIP_TRY(hipMemcpy(shards.data(), lightTests, s->lightTests.bytes, hipMemcpyDeviceToHost));
-        for (int i = 0; i < PG_LIGHT_TEST_SHARDS; ++i) lt += shards[(size_t)i * PG_LIGHT_TEST_STRIDE];
-        // the integrators' own statistics, words 1 .. 8 of the same shards (pg_kernels.h): like the light tests they run on from pg_counters_reset
-        PgCounters &c = s->counters;
-        c.paths_total = c.paths_zero_radiance = c.path_length_sum = c.path_length_count = c.path_length_min = c.path_length_max = c.volume_interactions = c.surface_interactions = 0;
-        unsigned long long minc = 0, maxp = 0;
-        for (int i = 0; i < PG_LIGHT_TEST_SHARDS; ++i) {
-            const unsigned long long *sh = &shards[(size_t)i * PG_LIGHT_TEST_STRIDE];
-            c.path_length_sum += sh[PG_STAT_LEN_SUM]; c.path_length_count += sh[PG_STAT_LEN_COUNT];
-            minc = std::max(minc, sh[PG_STAT_LEN_MINC]); maxp = std::max(maxp, sh[PG_STAT_LEN_MAXP]);
-            c.paths_total += sh[PG_STAT_PATHS]; c.paths_zero_radiance += sh[PG_STAT_PATHS_ZERO];
-            c.volume_interactions += sh[PG_STAT_VOLUME]; c.surface_interactions += sh[PG_STAT_SURFACE];
-        }
-        if (c.path_length_count > 0) { c.path_length_min = 0xffff - minc; c.path_length_max = maxp - 1; }
-    }
-    PgCounters &c = s->counters;
-    c.camera_rays += cameraRays; c.closest_rays += closestRays; c.shadow_rays += shadowRays;
-    c.node_visits = tc[0].node_visits + tc[1].node_visits;
-    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + lt;
-    c.light_tri_tests = lt;
-    c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
-    c.shadow_node_visits = tc[1].node_visits; c.shadow_tri_tests = tc[1].tri_tests;
-    c.closest_launches += closestLaunches; c.shadow_launches += shadowLaunches;
-    c.shade_launches += shadeLaunches; c.resolve_launches += resolveLaunches; c.shade_items += shadeItems; c.mis_rays += misRays;
-    c.shading_modes |= shadingModes;
-    for (auto &te : timed) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, s->events[te.first], s->events[te.first + 1]) != hipSuccess) continue;
-        double *acc[6] = {&c.closest_ms, &c.shadow_ms, &c.shade_ms, &c.resolve_ms, &c.generate_ms, &c.film_ms};
-        *acc[te.second] += ms;
-    }
-#undef PG_TIMED
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, evStart, evStop) == hipSuccess) c.render_ms += ms;
+    if (int e = readBackFrame(c, film, filmBytes, strays, nStrays, mem, hostNStrays)) return e;
+    if (int e = accountFrame(c, evStart, evStop)) return e;
     if (int st2 = checkCullGuard(s)) return st2;
     if (hostNStrays > maxStrays) return setError(PG_ERR_OVERFLOW, "%d stray samples, buffer holds %d", hostNStrays, maxStrays);
     return PG_OK;
+}
+int pg_render(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays,
+              int mem, void *streamPtr) {
+    if (!s || !rd || !film || !nStrays || (maxStrays > 0 && !strays)) return setError(PG_ERR_INVALID, "pg_render: null argument");
+    return withExactFallback(s, [&]() { return renderFrame(s, rd, film, strays, maxStrays, nStrays, mem, streamPtr); });
 }
 
 // ---- the film gather of pg_render_sharded over RCCL (ncclGather, rccl.h:745) ---------------------------------------
@@ -1076,7 +1030,7 @@ int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *des
     size_t filmMax = sizeof(PgFilmPixel);  // never an empty buffer, also when no rank owns a tile
     for (int r = 0; r < n; ++r) {
         rd[r].tile_first = r; rd[r].tile_step = n;
-        filmBytes[r] = sizeof(PgFilmPixel) * (size_t)desc->tile_pixels * (size_t)tileCount(&rd[r]);
+        filmBytes[r] = sizeof(PgFilmPixel) * (size_t)desc->tile_pixels * (size_t)pgTileCount(&rd[r]);
         filmMax = std::max(filmMax, filmBytes[r]);
         // a rank that owns no tile (more devices than tiles: a small image or crop window) has nothing to receive: its film
         // pointer may be null; it still runs pg_render (which handles an empty shard) so that its counters and stray count are set

@@ -1,0 +1,84 @@
+// pg_render_check.h -- everything pg_render (pg_abi.hip) decides from the caller's PgRenderDesc before it touches the device: the checks
+// of the description, in the order and with the texts they have always been reached, and the pure decisions of a frame (tile count,
+// batch shape, bounce limits).  Host code only: no HIP runtime call, so a program without a device can run it
+// (tests/render_check_host.hip does, under the sanitizers).
+#ifndef PG_RENDER_CHECK_H
+#define PG_RENDER_CHECK_H
+#include <algorithm>
+#include <string>
+#include "pg_scene_prep.h"  // pgPrepFail
+// What the checks need to know about the scene the frame is rendered on
+struct RenderSceneFacts {
+    int nMedia = 0;                                               // PgSceneDesc.n_media
+    bool hasCmaxmin = false, hasSobol = false, hasPerms = false;  // the scene carries CMaxMinDist / the Sobol' matrices / the Halton permutations
+    int nPermDims = 0;                                            // dimensions of the Halton permutation table
+};
+// the 16x16 tiles of the full-frame tiling that this description's shard (tile_first, tile_step) owns
+inline int pgTileCount(const PgRenderDesc *rd) {
+    int nx = (rd->sample_bounds[2] - rd->sample_bounds[0] + 15) / 16, ny = (rd->sample_bounds[3] - rd->sample_bounds[1] + 15) / 16;
+    if (nx <= 0 || ny <= 0 || rd->tile_step <= 0 || rd->tile_first < 0) return 0;
+    int total = nx * ny;
+    return rd->tile_first >= total ? 0 : (total - rd->tile_first + rd->tile_step - 1) / rd->tile_step;
+}
+
+// PG_OK, or PG_ERR_INVALID with its message in err
+#define RC_FAIL(...) return pgPrepFail(err, PG_ERR_INVALID, __VA_ARGS__)
+inline int pg_check_render_desc(const PgRenderDesc *rd, const RenderSceneFacts &sc, std::string &err) {
+    if (rd->abi_version != PG_ABI_VERSION) RC_FAIL("ABI version %d, expected %d", rd->abi_version, PG_ABI_VERSION);
+    if (rd->filter_radius[0] <= 0 || rd->filter_radius[1] <= 0) RC_FAIL("pg_render: filter radius must be positive");
+    if (!rd->filter_general && (rd->filter_radius[0] > 0.5f || rd->filter_radius[1] > 0.5f || rd->tile_pixels != 256))
+        RC_FAIL("pg_render: filter_general = 0 is the box filter of radius <= 0.5 with 256-entry tile blocks");
+    if (rd->filter_general && rd->tile_pixels != (16 + rd->tile_halo[0] + rd->tile_halo[2]) * (16 + rd->tile_halo[1] + rd->tile_halo[3]))
+        RC_FAIL("pg_render: tile_pixels does not match tile_halo");
+    if (rd->spp <= 0 || rd->max_depth < 0 || rd->tile_step <= 0) RC_FAIL("pg_render: bad spp/maxdepth/tile_step");
+    if (rd->integrator != 0 && rd->integrator != 1) RC_FAIL("pg_render: integrator %d (0 = path, 1 = volpath)", rd->integrator);
+    if (rd->camera_medium < -1 || rd->camera_medium >= sc.nMedia) RC_FAIL("pg_render: camera_medium %d out of range", rd->camera_medium);
+    if (rd->sampler < PG_SAMPLER_HALTON || rd->sampler > PG_SAMPLER_MAXMINDIST) RC_FAIL("pg_render: sampler %d (PgSamplerKind 0 .. 5)", rd->sampler);
+    if (rd->sampler >= PG_SAMPLER_RANDOM) {
+        if (rd->sampler != PG_SAMPLER_RANDOM && (rd->sampler_dims < 0 || rd->sampler_dims > 4096)) RC_FAIL("pg_render: sampler_dims %d", rd->sampler_dims);
+        if (rd->sampler == PG_SAMPLER_STRATIFIED && (rd->strat_samples[0] < 1 || rd->strat_samples[1] < 1 || rd->strat_samples[0] * rd->strat_samples[1] != rd->spp))
+            RC_FAIL("pg_render: stratified sampler %d x %d samples, spp %d", rd->strat_samples[0], rd->strat_samples[1], rd->spp);
+        if ((rd->sampler == PG_SAMPLER_ZEROTWO || rd->sampler == PG_SAMPLER_MAXMINDIST) && (rd->spp & (rd->spp - 1)))
+            RC_FAIL("pg_render: sampler %d needs a power-of-two spp (the reference rounds up), got %d", rd->sampler, rd->spp);
+        if (rd->sampler == PG_SAMPLER_MAXMINDIST && (!sc.hasCmaxmin || rd->sampler_dims < 1 || rd->spp >= (1 << 17)))
+            RC_FAIL("pg_render: maxmindist needs PgSceneDesc.cmaxmin, sampler_dims >= 1 and spp < 2^17");
+    }
+    if (rd->sampler == 1) {
+        if (!sc.hasSobol) RC_FAIL("pg_render: sampler = sobol, but the scene was created without the Sobol' tables");
+        if (rd->sobol_log2_resolution < 0 || rd->sobol_log2_resolution > 26 || rd->sobol_resolution != (1 << rd->sobol_log2_resolution))
+            RC_FAIL("pg_render: sobol_resolution %d / sobol_log2_resolution %d", rd->sobol_resolution, rd->sobol_log2_resolution);
+    }
+    if (rd->sampler == 0 && (!sc.hasPerms || (5 + 8 * ((long long)rd->max_depth + 1) > sc.nPermDims && sc.nPermDims < 1000)))
+        RC_FAIL("Halton table has %d dimensions; maxdepth %d needs %lld", sc.nPermDims, rd->max_depth, 5 + 8 * ((long long)rd->max_depth + 1));
+    if (!rd->filter_general && pgh_box_filter_needs_gather(rd))
+        RC_FAIL("pg_render: filter_general = 0, but in this frame a film position can round up onto the next pixel "
+                "(pg_box_filter_needs_gather, include/pbrt_gpu.h): render it with filter_general = 1");
+    return PG_OK;
+}
+#undef RC_FAIL
+// Batch shape: as many whole tiles x samples as fit the budget of path slots
+struct BatchShape { int tiles, samples; };
+inline BatchShape pgBatchShape(int spp, int nLocalTiles, bool filterGeneral, size_t budget) {
+    BatchShape b = {nLocalTiles, spp};
+    if ((size_t)b.tiles * 256 * b.samples <= budget) return b;
+    if (filterGeneral) {
+        // the gathering film kernel needs all samples of a tile in one batch (reference summation order): split by tiles
+        b.tiles = std::max(1, (int)(budget / ((size_t)256 * b.samples)));
+    } else {
+        // prefer all tiles with fewer samples (keeps primary rays coherent and every pixel busy)
+        b.samples = (int)(budget / ((size_t)b.tiles * 256));
+        if (b.samples < 1) { b.samples = 1; b.tiles = std::max(1, (int)(budget / 256)); }
+    }
+    return b;
+}
+
+// (64-bit: maxdepth comes from the caller / the scene file.)  Bounce launches are enqueued without looking at the queues, so
+// a huge maxdepth is bounded here: beyond PG_MAX_BLIND_BOUNCES the host looks at the main queue every 32 bounces and stops
+// when it is empty (Russian roulette ends every path), and a frame whose paths outlive PG_MAX_BOUNCES fails loudly.
+const long long PG_MAX_BLIND_BOUNCES = 64, PG_MAX_BOUNCES = 4096;
+struct BounceLimits { long long wantIters; int maxIters; };
+inline BounceLimits pgBounceLimits(int maxDepth, bool hasNullMaterial) {
+    const long long want = (long long)maxDepth + 1 + (hasNullMaterial ? 64 : 0);
+    return {want, (int)std::min<long long>(want, PG_MAX_BOUNCES)};
+}
+#endif

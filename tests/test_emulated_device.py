@@ -95,6 +95,13 @@ def test_round6_kernels_on_the_emulated_device(emulated):
     assert " passed" in out and "failed" not in out
 
 
+def test_work_buffers_regrow_on_the_emulated_device(emulated):
+    """The host side of pg_render between frames: one scene with a grid medium and BSSRDF materials rendered four times with growing batches,
+    both integrators and a tile shard -- every group of work buffers grows by its own capacity -- equals fresh scenes bit for bit (about a minute)."""
+    out = run_gpu_tests(emulated, ["tests/test_gpu_parity.py"], "test_work_buffers_regrow_between_frames", 900)
+    assert " passed" in out and "failed" not in out
+
+
 def test_moving_shapes_and_instances_on_the_emulated_device(emulated):
     """Round 5, last: TransformedPrimitive over an AnimatedTransform on the device -- the queues carry the rays' times, k_trace<., XP_ANIM>
     interpolates a moving instance's transform (and inverts it: Gauss-Jordan of the blended scale) at the ray's time when it enters the

@@ -544,6 +544,41 @@ def test_path_batching_does_not_change_the_film(gpu, name, monkeypatch):
     gs.close()
 
 
+def test_work_buffers_regrow_between_frames(gpu, monkeypatch):
+    """The work buffers stay with the scene and grow in four groups, each by its own capacity (the queues and path state, volpath's
+    medium state, the queue-order path state, the BSSRDF branch): a sequence of frames of growing size and changing integrator on ONE
+    scene -- grid_sss_sobol has a grid medium and BSSRDF materials, so every group exists -- must give, frame by frame, the film, strays
+    and counters of the same description on a fresh scene, bit for bit."""
+    scene = gpu.HostScene(os.path.join(GOLD, "grid_sss_sobol.pbrt"))
+    assert scene.desc.n_grids > 0 and scene.desc.n_bssrdfs > 0
+    path = scene.render_desc()
+    path.integrator = 0
+    frames = [("volpath, 256 paths per batch", scene.render_desc(), "256"), ("volpath", scene.render_desc(), None), ("path", path, None),
+              ("volpath, every second tile", scene.render_desc(tile_first=1, tile_step=2), None)]
+    assert frames[0][1].integrator == 1
+
+    def render(gs, rd, budget):
+        if budget:
+            monkeypatch.setenv("PG_BATCH_PATHS", budget)
+        else:
+            monkeypatch.delenv("PG_BATCH_PATHS", raising=False)
+        gs.counters_reset()
+        film, strays = gs.render(rd)
+        return film, strays, gs.counters()
+
+    shared = gpu.GpuScene(scene.desc)
+    for what, rd, budget in frames:
+        film, strays, cn = render(shared, rd, budget)
+        fresh = gpu.GpuScene(scene.desc)
+        film2, strays2, cn2 = render(fresh, rd, budget)
+        fresh.close()
+        assert film.tobytes() == film2.tobytes(), what
+        assert len(strays) == len(strays2) and strays.tobytes() == strays2.tobytes(), what
+        for k in ("camera_rays", "closest_rays", "shadow_rays", "node_visits", "tri_tests"):
+            assert cn[k] == cn2[k], (what, k)
+    shared.close()
+
+
 @pytest.mark.parametrize("name", ["cornell_32", "cornell_spot_power", "sphere_light", "instance_boxes", "tex_materials", "vol_smoke", "vol_fog", "sobol_vol_smoke", "filter_gaussian"])
 def test_sparse_light_tables_equal_dense(gpu, name, monkeypatch):
     """The "spatial" light distribution filled on first touch (PG_SPARSE_LIGHTS=1 forces the sparse tables that large light
