@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: the device arithmetic headers of the product (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h) compiled for the HOST
+// TEST INFRASTRUCTURE: the device arithmetic headers of the product (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h, pg_grid.h, pg_bssrdf.h, pg_motion.h) compiled for the HOST
 // (hipcc --cuda-host-only), so that the very source the HIP kernels execute can be run without a GPU and compared with the oracle
 // -- tests/test_device_headers_on_host.py.  Every PG_DEV function becomes __host__ __device__ (the attribute macro is redefined
 // after the runtime header has been read), and the handful of device-only intrinsics they call get host overloads (clang overloads
@@ -20,6 +20,7 @@ __host__ inline unsigned long long __brevll(unsigned long long v) { return __bui
 #include "../pbrt-v3_amd/csrc/pg_sphere.h"
 #include "../pbrt-v3_amd/csrc/pg_grid.h"
 #include "../pbrt-v3_amd/csrc/pg_bssrdf.h"
+#include "../pbrt-v3_amd/csrc/pg_motion.h"
 
 static V3 v3of(const float *p) { return mk(p[0], p[1], p[2]); }
 extern "C" {
@@ -78,5 +79,11 @@ int hostdev_bssrdf_probe_segment(const PgBSSRDF *d, const float *tables, const f
     const bool ok = bssrdf_probe_segment(bssrdf_bind(*d, tables), v3of(frame), v3of(frame + 3), v3of(frame + 6), v3of(po), u1, u2x, u2y, base, target);
     out[0] = u1; out[1] = base.x; out[2] = base.y; out[3] = base.z; out[4] = target.x; out[5] = target.y; out[6] = target.z;
     return ok ? 1 : 0;
+}
+// pg_motion.h: AnimatedTransform::Interpolate from PgInstance's T[2][3], R[2][4], S[2][9]; without inv mInv stays 0 (interpolate_trs<false> does not compute it)
+void hostdev_interpolate_trs(int inv, const float *T, const float *R, const float *S, float dt, float *m, float *mInv) {
+    for (int k = 0; k < 16; ++k) m[k] = mInv[k] = 0.f;
+    if (inv) interpolate_trs<true>((const float(*)[3])T, (const float(*)[4])R, (const float(*)[9])S, dt, m, mInv);
+    else interpolate_trs<false>((const float(*)[3])T, (const float(*)[4])R, (const float(*)[9])S, dt, m, mInv);
 }
 }

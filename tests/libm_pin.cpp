@@ -1,9 +1,10 @@
 // TEST INFRASTRUCTURE: pbrt-v3_amd/csrc/pg_libm.h against the system's libm (the one the reference binary links), argument by argument.
-// Built and driven by tests/test_libm_restated.py.
+// Built and driven by tests/test_libm_restated.py and tests/test_libm_chunk_sums.py.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../pbrt-v3_amd/csrc/pg_libm.h"
+#include "libm_chunk.h"
 
 static inline bool same(float a, float b) { return (a != a && b != b) || pgm_asuint(a) == pgm_asuint(b); }
 
@@ -30,26 +31,69 @@ extern "C" long long pin_unary(int fn, uint32_t first, uint32_t step, long long 
     if (firstBad) *firstBad = badArg;
     return bad;
 }
-// atan2f on `count` pseudo-random pairs of bit patterns (a 64-bit LCG per index, seeded), every exponent and sign reached; with
-// `special`, both arguments are drawn from a small set of edge values (zeros, infinities, NaN, 1, subnormals, huge ratios)
+// atan2f on `count` pairs of bit patterns, the ones lc_atan2_pair (libm_chunk.h) draws from the indices 0 .. count - 1
 extern "C" long long pin_atan2f(uint64_t seed, long long count, int special, uint32_t *badY, uint32_t *badX) {
-    static const uint32_t edge[] = {0x00000000, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 0x3f800000, 0xbf800000, 0x00000001, 0x80000001, 0x007fffff,
-                                    0x00800000, 0x7f7fffff, 0xff7fffff, 0x5e800000, 0x1e800000, 0x3f000000, 0x3ee00000, 0x3f300000, 0x3f980000, 0x401c0000, 0x4c000000, 0x31000000};
-    const int nEdge = sizeof(edge) / sizeof(edge[0]);
     long long bad = 0;
     uint32_t by = 0, bx = 0;
 #pragma omp parallel for reduction(+ : bad) schedule(static)
     for (long long i = 0; i < count; ++i) {
-        uint64_t s = (seed + (uint64_t)i) * 6364136223846793005ULL + 1442695040888963407ULL;
-        s ^= s >> 29; s *= 0xbf58476d1ce4e5b9ULL; s ^= s >> 32;
-        uint32_t uy = (uint32_t)s, ux = (uint32_t)(s >> 32);
-        if (special) { uy = edge[(i / nEdge) % nEdge]; ux = edge[i % nEdge]; }
-        else if ((i & 3) == 1) ux = (ux & 0x807fffff) | (uy & 0x7f800000);                         // same exponent: ratios near 1
-        else if ((i & 3) == 2) ux = (ux & 0x807fffff) | (((uy >> 23) + (uint32_t)(s >> 60)) & 0xff) << 23;  // exponents within 16
+        uint32_t uy, ux;
+        lc_atan2_pair(seed, (uint64_t)i, special, &uy, &ux);
         const float y = pgm_asfloat(uy), x = pgm_asfloat(ux);
         if (!same(pg_atan2f(y, x), atan2f(y, x))) { ++bad; by = uy; bx = ux; }
     }
     if (badY) *badY = by;
     if (badX) *badX = bx;
     return bad;
+}
+
+// ---- the sweeps as chunk sums (libm_chunk.h): what tests/golden/libm_chunk_sums.npz records and the device must reproduce ----
+// function fn (LC_NUM_FN of them) at index i -- an argument's bit pattern, for atan2f the index of a pair --: SYS = the system's
+// libm, else pg_libm.h; the results' bits in r[0] (and r[1]: sincosf's cosine), returns the hash term
+template <bool SYS> static inline uint64_t term(int fn, uint32_t i, uint32_t r[2]) {
+    const float x = pgm_asfloat(i);
+    float a = 0, b = 0;
+    switch (fn) {
+    case 0: a = SYS ? sinf(x) : pg_sinf(x); break;
+    case 1: a = SYS ? cosf(x) : pg_cosf(x); break;
+    case 2: if (SYS) sincosf(x, &a, &b); else pg_sincosf(x, &a, &b); break;
+    case 3: a = SYS ? logf(x) : pg_logf(x); break;
+    case 4: a = SYS ? expf(x) : pg_expf(x); break;
+    case 5: a = SYS ? acosf(x) : pg_acosf(x); break;
+    case 6: a = SYS ? atanf(x) : pg_atanf(x); break;
+    default: {
+        uint32_t uy, ux;
+        lc_atan2_pair(1, i, 0, &uy, &ux);
+        a = SYS ? atan2f(pgm_asfloat(uy), pgm_asfloat(ux)) : pg_atan2f(pgm_asfloat(uy), pgm_asfloat(ux));
+    }
+    }
+    r[0] = pgm_asuint(a); r[1] = pgm_asuint(b);
+    return fn == 2 ? lc_term2(i, a, b) : lc_term1(i, a);
+}
+// out[k] = the sum of chunk chunks[k]
+extern "C" void pin_chunk_sums(int fn, int system, const uint32_t *chunks, int n, uint64_t *out) {
+    for (int k = 0; k < n; ++k) {
+        const uint32_t first = chunks[k] << LC_CHUNK_BITS;
+        uint64_t sum = 0;
+#pragma omp parallel for reduction(+ : sum) schedule(static)
+        for (long long j = 0; j < (1LL << LC_CHUNK_BITS); ++j) {
+            uint32_t r[2];
+            sum += system ? term<true>(fn, first + (uint32_t)j, r) : term<false>(fn, first + (uint32_t)j, r);
+        }
+        out[k] = sum;
+    }
+}
+// the results themselves at the indices first .. first + count - 1 (out1: sincosf's cosine, may be null); atan2f with `special`: the edge grid
+extern "C" void pin_raw(int fn, int system, int special, uint32_t first, uint32_t count, uint32_t *out0, uint32_t *out1) {
+    for (uint32_t j = 0; j < count; ++j) {
+        uint32_t r[2];
+        if (fn == LC_ATAN2F && special) {
+            uint32_t uy, ux;
+            lc_atan2_pair(1, first + j, 1, &uy, &ux);
+            r[0] = pgm_asuint(system ? atan2f(pgm_asfloat(uy), pgm_asfloat(ux)) : pg_atan2f(pgm_asfloat(uy), pgm_asfloat(ux)));
+        } else if (system) term<true>(fn, first + j, r);
+        else term<false>(fn, first + j, r);
+        out0[j] = r[0];
+        if (out1) out1[j] = r[1];
+    }
 }

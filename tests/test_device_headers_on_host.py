@@ -2,7 +2,8 @@
 (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
 file compares their functions with the oracle bit for bit -- on inputs far outside what the golden scenes contain (coordinates from
 1e-8 to 1e8, quadric radii from 1e-4 to 1e4), including exactly the ray sets of the GPU tests test_triangle_reintersect_on_device /
-test_quadric_reintersect_on_device.  What a GPU run adds to this is the traversal around these functions, not their arithmetic."""
+test_quadric_reintersect_on_device.  That the gfx950 build of the same source returns the same bits is tests/test_gpu_device_arithmetic.py: it
+feeds the inputs built here (the *_inputs functions) to both builds and runs pg_libm.h over every argument on the device."""
 import ctypes as C
 import os
 import re
@@ -19,11 +20,9 @@ import test_reference_kats as K
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-@pytest.fixture(scope="module")
-def dev(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    so = str(tmp_path_factory.mktemp("hostdev") / "libdevice_headers_host.so")
+def build_host_headers(directory):
+    """tests/device_headers_host.hip compiled for the host into `directory`, loaded, its entry points typed."""
+    so = os.path.join(str(directory), "libdevice_headers_host.so")
     subprocess.check_call([HIPCC, "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
                            os.path.join(ROOT, "tests", "device_headers_host.hip"), "-o", so])
     lib = C.CDLL(so)
@@ -50,7 +49,18 @@ def dev(tmp_path_factory):
     lib.hostdev_bssrdf_pdf_sp.argtypes = [C.c_void_p] * 6
     lib.hostdev_bssrdf_probe_segment.restype = C.c_int
     lib.hostdev_bssrdf_probe_segment.argtypes = [C.c_void_p] * 4 + [C.c_float] * 3 + [C.c_void_p]
+    lib.hostdev_concentric_sample_disk.restype = None
+    lib.hostdev_concentric_sample_disk.argtypes = [C.c_float, C.c_float, C.c_void_p]
+    lib.hostdev_interpolate_trs.restype = None
+    lib.hostdev_interpolate_trs.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2
     return lib
+
+
+@pytest.fixture(scope="module")
+def dev(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    return build_host_headers(tmp_path_factory.mktemp("hostdev"))
 
 
 def bits(x):
@@ -61,6 +71,29 @@ def signed_pexp(rng):
     u = rng.uniform_float()
     lg = np.float32((1 - u) * -8.0 + u * 8)
     return np.float32((-1.0 if rng.uniform_float() < 0.5 else 1.0) * 10.0 ** float(lg))
+
+
+def triangle_inputs(oracle):
+    """(p0, p1, p2, o, d, tMax, n_reintersect): the spawned rays of the device Reintersect test (the first n_reintersect: none may hit) and
+    10 rays aimed at each of 120 random triangles, coordinates from 1e-8 to 1e8.  `oracle` spawns the first set's origins."""
+    rows = []
+    for text, o, d, tm in K.reintersect_cases(oracle, n_tris=12, n_rays=60):
+        P = np.array([float(x) for x in re.search(r'"point P" \[ (.*?) \]', text).group(1).split()], np.float32).reshape(3, 3)
+        for i in range(len(tm)):
+            rows.append((P[0], P[1], P[2], o[i], d[i], np.float32(tm[i])))
+    n_reintersect = len(rows)
+    for i in range(120):
+        rng = PCG32(5000 + i)
+        v = np.array([[signed_pexp(rng) for _ in range(3)] for _ in range(3)], np.float32)
+        for _ in range(10):
+            u0, u1 = rng.uniform_float(), rng.uniform_float()
+            su = np.float32(np.sqrt(np.float32(u0)))
+            b0, b1 = np.float32(1) - su, np.float32(u1) * su
+            pt = (b0 * v[0] + b1 * v[1] + (np.float32(1) - b0 - b1) * v[2]).astype(np.float32)
+            o = np.array([signed_pexp(rng) for _ in range(3)], np.float32)
+            rows.append((v[0], v[1], v[2], o, (pt - o).astype(np.float32), np.float32(np.inf)))
+    cols = [np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(6)]
+    return (*cols, n_reintersect)
 
 
 def test_triangle_intersect_equals_oracle_at_extreme_magnitudes(dev, oracle):
@@ -75,38 +108,23 @@ def test_triangle_intersect_equals_oracle_at_extreme_magnitudes(dev, oracle):
         if oh:
             assert bits([ot])[0] == bits(out[:1])[0] and np.array_equal(bits(ob), bits(out[1:]))
         return oh
-    n = 0
-    for text, o, d, tm in K.reintersect_cases(oracle, n_tris=12, n_rays=60):
-        P = np.array([float(x) for x in re.search(r'"point P" \[ (.*?) \]', text).group(1).split()], np.float32).reshape(3, 3)
-        for i in range(len(tm)):
-            assert not both(P, o[i], d[i], float(tm[i]))
-            n += 1
+    p0, p1, p2, o, d, tm, n = triangle_inputs(oracle)
+    for i in range(n):
+        assert not both((p0[i], p1[i], p2[i]), o[i], d[i], float(tm[i]))
     hits = 0
-    for i in range(120):
-        rng = PCG32(5000 + i)
-        v = np.array([[signed_pexp(rng) for _ in range(3)] for _ in range(3)], np.float32)
-        for _ in range(10):
-            u0, u1 = rng.uniform_float(), rng.uniform_float()
-            su = np.float32(np.sqrt(np.float32(u0)))
-            b0, b1 = np.float32(1) - su, np.float32(u1) * su
-            pt = (b0 * v[0] + b1 * v[1] + (np.float32(1) - b0 - b1) * v[2]).astype(np.float32)
-            o = np.array([signed_pexp(rng) for _ in range(3)], np.float32)
-            hits += both(v, o, (pt - o).astype(np.float32), np.inf)
-    assert n == 12 * 120 and hits > 1000
+    for i in range(n, len(tm)):
+        hits += both((p0[i], p1[i], p2[i]), o[i], d[i], np.inf)
+    assert n == 12 * 120 and len(tm) - n == 1200 and hits > 1000
 
 
-@pytest.mark.parametrize("kind", ["full_sphere", "partial_sphere", "cylinder"])
-def test_quadric_intersect_equals_both_oracle_builds(dev, pkg, oracle, kind):
-    """sphere_test (Sphere / Cylinder ::Intersect with EFloat error bounds, sphere.cpp:49-160, cylinder.cpp:42-143) on random quadrics
-    (radius 1e-4 .. 1e4, clipped in z and phi) against the oracle AND its correctly-rounded-libm build: hit / miss and tHit bit for bit
-    on rays from far outside, from inside the bounding box and in random directions."""
-    total = hits = 0
-    for i in range(16):
-        rng = PCG32(i)
-        radius = K._pexp(rng, 4)
+def quadric_shape_text(kind, rng):
+    """A random quadric of the kind, radius 1e-4 .. 1e4, clipped in z and phi where the shape has such parameters."""
+    radius = K._pexp(rng, 4)
+    signed = lambda: K._pexp(rng, 4) * (-1 if rng.uniform_float() < 0.5 else 1)
+    if kind in ("full_sphere", "partial_sphere", "cylinder"):
         if kind == "cylinder":
-            zmin = K._pexp(rng, 4) * (-1 if rng.uniform_float() < 0.5 else 1)
-            zmax = K._pexp(rng, 4) * (-1 if rng.uniform_float() < 0.5 else 1)
+            zmin = signed()
+            zmax = signed()
         elif kind == "partial_sphere":
             lerp = lambda u: (1 - u) * -radius + u * radius
             zmin = -radius if rng.uniform_float() < 0.5 else lerp(np.float32(rng.uniform_float()))
@@ -114,10 +132,30 @@ def test_quadric_intersect_equals_both_oracle_builds(dev, pkg, oracle, kind):
         else:
             zmin, zmax = -radius, radius
         phimax = 360.0 if (kind == "full_sphere" or rng.uniform_float() < 0.5) else rng.uniform_float() * 360.0
-        shape = ('Shape "%s" "float radius" [ %.9g ] "float zmin" [ %.9g ] "float zmax" [ %.9g ] "float phimax" [ %.9g ]'
-                 % ("cylinder" if kind == "cylinder" else "sphere", radius, zmin, zmax, phimax))
-        scene = pkg.HostScene(text=K.QUADRIC_SCENE % shape)
-        sp = scene.desc.spheres[0]
+        return ('Shape "%s" "float radius" [ %.9g ] "float zmin" [ %.9g ] "float zmax" [ %.9g ] "float phimax" [ %.9g ]'
+                % ("cylinder" if kind == "cylinder" else "sphere", radius, zmin, zmax, phimax))
+    phimax = 360.0 if rng.uniform_float() < 0.5 else rng.uniform_float() * 360.0
+    if kind == "disk":
+        inner = 0.0 if rng.uniform_float() < 0.5 else radius * rng.uniform_float()
+        return 'Shape "disk" "float height" [ %.9g ] "float radius" [ %.9g ] "float innerradius" [ %.9g ] "float phimax" [ %.9g ]' % (signed(), radius, inner, phimax)
+    if kind == "cone":
+        return 'Shape "cone" "float radius" [ %.9g ] "float height" [ %.9g ] "float phimax" [ %.9g ]' % (radius, K._pexp(rng, 4), phimax)
+    if kind == "paraboloid":
+        zmax = K._pexp(rng, 4)
+        zmin = 0.0 if rng.uniform_float() < 0.5 else zmax * rng.uniform_float()
+        return 'Shape "paraboloid" "float radius" [ %.9g ] "float zmin" [ %.9g ] "float zmax" [ %.9g ] "float phimax" [ %.9g ]' % (radius, zmin, zmax, phimax)
+    assert kind == "hyperboloid"
+    p1, p2 = [signed() for _ in range(3)], [signed() for _ in range(3)]
+    return 'Shape "hyperboloid" "point p1" [ %.9g %.9g %.9g ] "point p2" [ %.9g %.9g %.9g ] "float phimax" [ %.9g ]' % (*p1, *p2, phimax)
+
+
+def quadric_inputs(pkg, kind, n_shapes=16):
+    """[(scene, origins, directions)]: per random shape 60 rays from far outside towards its bounding box and 60 from inside the box in
+    random directions."""
+    cases = []
+    for i in range(n_shapes):
+        rng = PCG32(i)
+        scene = pkg.HostScene(text=K.QUADRIC_SCENE % quadric_shape_text(kind, rng))
         nodes = scene.nodes()
         lo, hi = nodes["bmin"][0], nodes["bmax"][0]
         os_, ds = [], []
@@ -127,7 +165,18 @@ def test_quadric_intersect_equals_both_oracle_builds(dev, pkg, oracle, kind):
             p2 = ((1 - tt) * lo + tt * hi).astype(np.float32)
             os_.append(o); ds.append((p2 - o).astype(np.float32))
             os_.append(p2); ds.append(uniform_sample_sphere((rng.uniform_float(), rng.uniform_float())))
-        os_, ds = np.asarray(os_, np.float32), np.asarray(ds, np.float32)
+        cases.append((scene, np.asarray(os_, np.float32), np.asarray(ds, np.float32)))
+    return cases
+
+
+@pytest.mark.parametrize("kind", ["full_sphere", "partial_sphere", "cylinder"])
+def test_quadric_intersect_equals_both_oracle_builds(dev, pkg, oracle, kind):
+    """sphere_test (Sphere / Cylinder ::Intersect with EFloat error bounds, sphere.cpp:49-160, cylinder.cpp:42-143) on random quadrics
+    (radius 1e-4 .. 1e4, clipped in z and phi) against the oracle AND its correctly-rounded-libm build: hit / miss and tHit bit for bit
+    on rays from far outside, from inside the bounding box and in random directions."""
+    total = hits = 0
+    for i, (scene, os_, ds) in enumerate(quadric_inputs(pkg, kind)):
+        sp = scene.desc.spheres[0]
         tm = np.full(len(os_), np.inf, np.float32)
         for cr in (False,):  # (one oracle: the device computes libm as the reference does, pg_libm.h)
             prim, t, _, _ = oracle.intersect(scene.desc, os_, ds, tm)
@@ -142,30 +191,43 @@ def test_quadric_intersect_equals_both_oracle_builds(dev, pkg, oracle, kind):
     assert total == 16 * 120 and hits > 300
 
 
-def test_offset_ray_origin_equals_oracle(dev, oracle):
-    """OffsetRayOrigin (geometry.h:1440-1454): every spawned ray's origin."""
-    lib = oracle.lib()
+def offset_ray_origin_inputs():
+    """(p, pError, n, w), 3 000 x 3 each: points from 1e-8 to 1e8 with error bounds up to 1e-5 of them, unit normals and directions."""
     rng = PCG32(77)
+    rows = []
     for _ in range(3000):
         p = np.array([signed_pexp(rng) for _ in range(3)], np.float32)
         perr = np.abs(p * np.float32(rng.uniform_float() * 1e-5)).astype(np.float32)
         n = uniform_sample_sphere((rng.uniform_float(), rng.uniform_float()))
         w = uniform_sample_sphere((rng.uniform_float(), rng.uniform_float()))
+        rows.append((p, perr, n, w))
+    return tuple(np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(4))
+
+
+def test_offset_ray_origin_equals_oracle(dev, oracle):
+    """OffsetRayOrigin (geometry.h:1440-1454): every spawned ray's origin."""
+    lib = oracle.lib()
+    for p, perr, n, w in zip(*offset_ray_origin_inputs()):
         a, b = np.zeros(3, np.float32), np.zeros(3, np.float32)
         lib.oracle_spawn_ray_origin(p.ctypes.data, perr.ctypes.data, n.ctypes.data, w.ctypes.data, a.ctypes.data)
         dev.hostdev_offset_ray_origin(p.ctypes.data, perr.ctypes.data, n.ctypes.data, w.ctypes.data, b.ctypes.data)
         assert np.array_equal(bits(a), bits(b))
 
 
-def test_radical_inverses_equal_oracle(dev, pkg, oracle):
-    """RadicalInverse / ScrambledRadicalInverse (lowdiscrepancy.cpp:389-436), 32- and 64-bit paths of the device form, the first 40 bases."""
-    lib = oracle.lib()
+def radical_inverse_inputs():
+    """([(base, its random digit permutation)] for the first 40 primes, the values to invert: small ones, around 2^32, random 31- and 62-bit ones)."""
     primes = [2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59, 61, 67, 71, 73, 79, 83, 89, 97, 101, 103, 107, 109, 113, 127, 131, 137, 139, 149, 151, 157,
               163, 167, 173]
     rng = np.random.default_rng(9)
     values = [0, 1, 2, 3, 255, 65535, 2**32 - 1, 2**32, 2**40 + 12345] + [int(x) for x in rng.integers(0, 2**62, size=40)] + [int(x) for x in rng.integers(0, 2**31, size=40)]
-    for bi, base in enumerate(primes):
-        perm = rng.permutation(base).astype(np.uint16)
+    return [(base, rng.permutation(base).astype(np.uint16)) for base in primes], values
+
+
+def test_radical_inverses_equal_oracle(dev, pkg, oracle):
+    """RadicalInverse / ScrambledRadicalInverse (lowdiscrepancy.cpp:389-436), 32- and 64-bit paths of the device form, the first 40 bases."""
+    lib = oracle.lib()
+    bases, values = radical_inverse_inputs()
+    for bi, (base, perm) in enumerate(bases):
         for a in values:
             assert bits([lib.oracle_radical_inverse(bi, a)])[0] == bits([dev.hostdev_radical_inverse(base, a)])[0], (base, a)
             want = lib.oracle_scrambled_radical_inverse(bi, a, perm.ctypes.data)
@@ -262,19 +324,19 @@ def test_new_device_headers_are_valid_gfx950_code(tmp_path):
 GRID_GOLD = os.path.join(ROOT, "tests", "golden")
 
 
-@pytest.mark.parametrize("name", ["grid_puff", "grid_puff_dense", "grid_transformed", "grid_fog_camera"])
-def test_grid_medium_device_functions_equal_the_correctly_rounded_oracle(dev, pkg, oracle, name):
-    """grid_density / grid_tr / grid_sample (GridDensityMedium::Density / Tr / Sample, media/grid.cpp) of pg_grid.h against the oracle's
-    correctly-rounded-libm build on the golden scenes' grids: random rays through, beside and inside the medium's box, random draw
-    streams -- transmittance (with its roulette), the interaction's t and the number of draws consumed, bit for bit."""
+GRID_SCENES = ["grid_puff", "grid_puff_dense", "grid_transformed", "grid_fog_camera"]
+
+
+def grid_inputs(pkg, name):
+    """(scene, its PgDensityGrid, the grid's densities, (o, d, tMax, draws, p)): 600 rays between points in and around the medium's box in
+    world space, every third one bounded, a stream of 4 096 draws each, and 600 points in and around the unit cube for Density."""
     scene = pkg.HostScene(os.path.join(GRID_GOLD, name + ".pbrt"))
     d = scene.desc
     g = d.grids[0]
     den = np.ctypeslib.as_array(d.grid_density, shape=(d.n_density_floats,))[g.density_offset:].copy()
     m2w = np.linalg.inv(np.array(list(g.world_to_medium), np.float64).reshape(4, 4))
-    L = oracle.lib()
     rng = np.random.default_rng(5)
-    n_tr = n_hit = 0
+    rows = []
     for trial in range(600):
         a = (m2w @ np.append(rng.random(3) * 1.6 - 0.3, 1.0))[:3]   # points in and around the unit cube, in world space
         b = (m2w @ np.append(rng.random(3) * 1.6 - 0.3, 1.0))[:3]
@@ -283,6 +345,19 @@ def test_grid_medium_device_functions_equal_the_correctly_rounded_oracle(dev, pk
         tmax = np.float32(np.inf if trial % 3 else 0.3 + rng.random())
         draws = rng.random(4096).astype(np.float32)
         p = rng.random(3).astype(np.float32) * np.float32(1.4) - np.float32(0.2)
+        rows.append((o, dvec, tmax, draws, p))
+    return scene, g, den, tuple(np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(5))
+
+
+@pytest.mark.parametrize("name", GRID_SCENES)
+def test_grid_medium_device_functions_equal_the_correctly_rounded_oracle(dev, pkg, oracle, name):
+    """grid_density / grid_tr / grid_sample (GridDensityMedium::Density / Tr / Sample, media/grid.cpp) of pg_grid.h against the oracle's
+    correctly-rounded-libm build on the golden scenes' grids: random rays through, beside and inside the medium's box, random draw
+    streams -- transmittance (with its roulette), the interaction's t and the number of draws consumed, bit for bit."""
+    scene, g, den, rays = grid_inputs(pkg, name)
+    L = oracle.lib()
+    n_tr = n_hit = 0
+    for trial, (o, dvec, tmax, draws, p) in enumerate(zip(*rays)):
         assert bits([L.oracle_grid_density(C.addressof(g), den.ctypes.data, p.ctypes.data)])[0] == bits([dev.hostdev_grid_density(C.addressof(g), den.ctypes.data, p.ctypes.data)])[0]
         ua, ub = C.c_int(), C.c_int()
         ta = L.oracle_grid_tr(C.addressof(g), den.ctypes.data, o.ctypes.data, dvec.ctypes.data, tmax, draws.ctypes.data, len(draws), C.byref(ua))
@@ -297,43 +372,52 @@ def test_grid_medium_device_functions_equal_the_correctly_rounded_oracle(dev, pk
     assert n_tr > 100 and n_hit > 20
 
 
-@pytest.mark.parametrize("material", ['Material "subsurface" "rgb sigma_a" [ 0.002 0.004 0.02 ] "rgb sigma_s" [ 0.05 0.06 0.08 ] "float eta" [ 1.33 ]',
-                                      'Material "kdsubsurface" "rgb Kd" [ 0.6 0.4 0.3 ] "rgb mfp" [ 8 12 20 ] "float g" [ 0.3 ]',
-                                      'Material "subsurface" "rgb sigma_a" [ 0 1 0.5 ] "rgb sigma_s" [ 0 0 2 ] "float eta" [ 1.5 ] "float g" [ -0.4 ]'])
+BSSRDF_MATERIALS = ['Material "subsurface" "rgb sigma_a" [ 0.002 0.004 0.02 ] "rgb sigma_s" [ 0.05 0.06 0.08 ] "float eta" [ 1.33 ]',
+                    'Material "kdsubsurface" "rgb Kd" [ 0.6 0.4 0.3 ] "rgb mfp" [ 8 12 20 ] "float g" [ 0.3 ]',
+                    'Material "subsurface" "rgb sigma_a" [ 0 1 0.5 ] "rgb sigma_s" [ 0 0 2 ] "float eta" [ 1.5 ] "float g" [ -0.4 ]']
+FRESNEL_MOMENT_ETAS = (0.5, 0.75, 0.999, 1.0, 1.33, 2.5)
+
+
+def bssrdf_radial_inputs(pkg, material):
+    """(scene with the material in place of sss_subsurface's, r, u), 1 500 each: radii from 0 to far beyond the table, every u with 0 and 0.999."""
+    text = open(os.path.join(ROOT, "tests", "golden", "sss_subsurface.pbrt")).read()
+    old = [l for l in text.splitlines() if l.startswith('Material "subsurface"')][0]
+    scene = pkg.HostScene(text=text.replace(old, material))
+    rng = np.random.default_rng(11)
+    r, u = np.zeros(1500, np.float32), np.zeros(1500, np.float32)
+    for trial in range(1500):
+        r[trial] = np.float32(0 if trial % 50 == 0 else 10.0 ** rng.uniform(-4, 3.5))
+        u[trial] = np.float32(rng.random() if trial % 37 else (0.0 if trial % 2 else 0.999))
+    return scene, r, u
+
+
+@pytest.mark.parametrize("material", BSSRDF_MATERIALS)
 def test_bssrdf_radial_device_functions_equal_the_oracle(dev, pkg, oracle, material):
     """bssrdf_sr / bssrdf_pdf_sr / bssrdf_sample_sr (TabulatedBSSRDF::Sr / Pdf_Sr / Sample_Sr with CatmullRomWeights and
     SampleCatmullRom2D under them) of pg_bssrdf.h against the oracle on the host front end's tables: radii from 0 to far beyond the
     table, every u, a channel without scattering (sigma_t = 0) and one without absorption (albedo 1)."""
-    text = open(os.path.join(ROOT, "tests", "golden", "sss_subsurface.pbrt")).read()
-    old = [l for l in text.splitlines() if l.startswith('Material "subsurface"')][0]
-    scene = pkg.HostScene(text=text.replace(old, material))
+    scene, rs, us = bssrdf_radial_inputs(pkg, material)
     d = scene.desc
     b = d.bssrdfs[0]
     L = oracle.lib()
-    rng = np.random.default_rng(11)
-    for trial in range(1500):
-        r = np.float32(0 if trial % 50 == 0 else 10.0 ** rng.uniform(-4, 3.5))
-        u = np.float32(rng.random() if trial % 37 else (0.0 if trial % 2 else 0.999))
+    for trial, (r, u) in enumerate(zip(rs, us)):
         a, c = np.zeros(9, np.float32), np.zeros(9, np.float32)
         L.oracle_bssrdf_radial(C.addressof(b), d.bssrdf_tables, r, u, a.ctypes.data)
         dev.hostdev_bssrdf_radial(C.addressof(b), d.bssrdf_tables, r, u, c.ctypes.data)
         same = (bits(a) == bits(c)) | (np.isnan(a) & np.isnan(c))
         assert same.all(), (trial, r, u, a, c)
-    for eta in (0.5, 0.75, 0.999, 1.0, 1.33, 2.5):
+    for eta in FRESNEL_MOMENT_ETAS:
         assert bits([L.oracle_fresnel_moment1(np.float32(eta))])[0] == bits([dev.hostdev_fresnel_moment1(np.float32(eta))])[0]
 
 
-def test_bssrdf_spatial_device_functions_equal_the_correctly_rounded_oracle(dev, pkg, oracle):
-    """bssrdf_pdf_sp (SeparableBSSRDF::Pdf_Sp), bssrdf_probe_segment (the first half of Sample_Sp: axis, channel, radius, angle -> probe
-    segment, u1 remapped) and invert_catmull_rom of pg_bssrdf.h against the oracle's correctly-rounded-libm build (cos / sin of the angle),
-    around random shading frames, bit for bit."""
+def bssrdf_spatial_inputs(pkg):
+    """(scene, (frame, po, pi, n, u1, u2x, u2y) of 1 500 probes around random shading frames, (the table's rho, rhoEff, the u to invert))"""
     text = open(os.path.join(ROOT, "tests", "golden", "sss_subsurface.pbrt")).read()
     scene = pkg.HostScene(text=text)
     d = scene.desc
     b = d.bssrdfs[0]
-    L = oracle.lib()
     rng = np.random.default_rng(21)
-    n_ok = 0
+    rows = []
     for trial in range(1500):
         ns = unit(rng)
         ss = np.cross(ns, unit(rng)).astype(np.float32); ss = (ss / np.linalg.norm(ss)).astype(np.float32)
@@ -342,20 +426,35 @@ def test_bssrdf_spatial_device_functions_equal_the_correctly_rounded_oracle(dev,
         po = (rng.normal(size=3) * 100).astype(np.float32)
         pi = (po + rng.normal(size=3) * 10.0 ** rng.uniform(-2, 2.5)).astype(np.float32)
         n = unit(rng)
+        u1, u2x, u2y = (np.float32(rng.random()) for _ in range(3))
+        rows.append((frame, po, pi, n, u1, u2x, u2y))
+    n = b.n_rho + b.n_radius + 2 * b.n_rho * b.n_radius + b.n_rho
+    table = np.ctypeslib.as_array(d.bssrdf_tables, shape=(d.n_bssrdf_floats,))[b.table:b.table + n].copy()
+    rho, rho_eff = table[:100].copy(), table[6564:6664].copy()
+    xs = np.array(list(rng.random(500).astype(np.float32)) + [np.float32(0), np.float32(1), np.float32(2), rho_eff[40]], np.float32)
+    return scene, tuple(np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(7)), (rho, rho_eff, xs)
+
+
+def test_bssrdf_spatial_device_functions_equal_the_correctly_rounded_oracle(dev, pkg, oracle):
+    """bssrdf_pdf_sp (SeparableBSSRDF::Pdf_Sp), bssrdf_probe_segment (the first half of Sample_Sp: axis, channel, radius, angle -> probe
+    segment, u1 remapped) and invert_catmull_rom of pg_bssrdf.h against the oracle's correctly-rounded-libm build (cos / sin of the angle),
+    around random shading frames, bit for bit."""
+    scene, probes, (rho, rho_eff, xs) = bssrdf_spatial_inputs(pkg)
+    d = scene.desc
+    b = d.bssrdfs[0]
+    L = oracle.lib()
+    n_ok = 0
+    for trial, (frame, po, pi, n, u1, u2x, u2y) in enumerate(zip(*probes)):
         a = L.oracle_bssrdf_pdf_sp(C.addressof(b), d.bssrdf_tables, frame.ctypes.data, po.ctypes.data, pi.ctypes.data, n.ctypes.data)
         c = dev.hostdev_bssrdf_pdf_sp(C.addressof(b), d.bssrdf_tables, frame.ctypes.data, po.ctypes.data, pi.ctypes.data, n.ctypes.data)
         assert bits([a])[0] == bits([c])[0], trial
-        u1, u2x, u2y = (np.float32(rng.random()) for _ in range(3))
         oa, oc = np.zeros(7, np.float32), np.zeros(7, np.float32)
         ka = L.oracle_bssrdf_probe_segment(C.addressof(b), d.bssrdf_tables, frame.ctypes.data, po.ctypes.data, u1, u2x, u2y, oa.ctypes.data)
         kc = dev.hostdev_bssrdf_probe_segment(C.addressof(b), d.bssrdf_tables, frame.ctypes.data, po.ctypes.data, u1, u2x, u2y, oc.ctypes.data)
         assert ka == kc and bits(oa[:1])[0] == bits(oc[:1])[0] and (not ka or np.array_equal(bits(oa), bits(oc))), trial
         n_ok += ka
     assert n_ok > 1000
-    n = b.n_rho + b.n_radius + 2 * b.n_rho * b.n_radius + b.n_rho
-    table = np.ctypeslib.as_array(d.bssrdf_tables, shape=(d.n_bssrdf_floats,))[b.table:b.table + n].copy()
-    rho, rho_eff = table[:100].copy(), table[6564:6664].copy()
-    for x in list(rng.random(500).astype(np.float32)) + [np.float32(0), np.float32(1), np.float32(2), rho_eff[40]]:
+    for x in xs:
         want = L.oracle_invert_catmull_rom(100, rho.ctypes.data, rho_eff.ctypes.data, x)
         assert bits([want])[0] == bits([dev.hostdev_invert_catmull_rom(100, rho.ctypes.data, rho_eff.ctypes.data, x)])[0]
 
