@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 29
+#define PG_ABI_VERSION 30
 
 typedef enum PgStatus {
     PG_OK = 0,
@@ -454,12 +454,13 @@ typedef enum PgSamplerKind {
     PG_SAMPLER_MAXMINDIST = 5     /* samplers/maxmin.cpp; needs PgSceneDesc.cmaxmin; spp rounded as its constructor does */
 } PgSamplerKind;
 
+#define PG_MAX_LENS_INTERFACES 32
 typedef struct PgRenderDesc {
     int32_t abi_version;
     /* camera: PerspectiveCamera (cameras/perspective.cpp:45-144) or OrthographicCamera (cameras/orthographic.cpp:44-118) */
     int32_t integrator;         /* 0 = PathIntegrator (integrators/path.cpp), 1 = VolPathIntegrator (integrators/volpath.cpp) */
     int32_t camera_medium;      /* Camera::medium: index into PgSceneDesc.media, -1 = none */
-    int32_t camera_type;        /* 0 = perspective, 1 = orthographic, 2 = environment (cameras/environment.cpp:43-56) */
+    int32_t camera_type;        /* 0 = perspective, 1 = orthographic, 2 = environment (cameras/environment.cpp:43-56), 3 = realistic (the lens block at the end) */
     float raster_to_camera[16]; /* row-major Matrix4x4 */
     float dx_camera[3], dy_camera[3]; /* ProjectiveCamera::dxCamera / dyCamera (perspective.cpp:60-63, orthographic.cpp:57-58): ray differentials */
     float camera_to_world[16];  /* AnimatedTransform CameraToWorld: its startTransform (the only one of a camera that does not move) */
@@ -519,6 +520,17 @@ typedef struct PgRenderDesc {
      * with (t % tile_count) == tile_first ... i.e. t = tile_first + k*tile_step.
      * Single GPU: tile_first=0, tile_step=1.                                 */
     int32_t tile_first, tile_step;
+    /* ABI 30 -- camera_type = 3: RealisticCamera (cameras/realistic.cpp).  The lens system after focusing, front element first, in metres
+     * (realistic.cpp:58-78): every camera sample is traced from the film through it (TraceLensesFromFilm, :100-151), starting from a point of
+     * the exit pupil box of the film point's distance from the centre (exitPupilBounds, :83-90; SampleExitPupil, :613-631).  The sample's
+     * weight (GenerateRay's return value, :704-711; 0 for a vignetted ray) multiplies its radiance on the film (film.h:121-161).  Inline
+     * arrays: nothing to keep alive.  All zero for the other cameras.  csrc/pg_lens.h names this block PgLensSystem. */
+    int32_t n_lens_interfaces;                                /* 1 .. PG_MAX_LENS_INTERFACES */
+    float lens_interfaces[PG_MAX_LENS_INTERFACES][4];         /* curvatureRadius, thickness, eta, apertureRadius (realistic.h:62-67) */
+    float exit_pupil_bounds[64][4];                           /* pMin.x, pMin.y, pMax.x, pMax.y */
+    float film_physical_extent[4];                            /* Film::GetPhysicalExtent (film.cpp:108-114): pMin.x, pMin.y, pMax.x, pMax.y */
+    float film_diagonal;                                      /* Film::diagonal: "diagonal" * .001 (film.cpp:51) */
+    int32_t lens_simple_weighting;                            /* "simpleweighting" (realistic.cpp:707-711) */
 } PgRenderDesc;
 
 /* Can a film position `(float)p + u` of GetCameraSample (sampler.cpp:46-52) round up to p + 1 for a pixel and a sample of the
@@ -612,6 +624,9 @@ typedef struct PgCounters {
     uint64_t paths_total, paths_zero_radiance;
     uint64_t path_length_sum, path_length_count, path_length_min, path_length_max;
     uint64_t volume_interactions, surface_interactions;
+    /* ABI 30 -- "Camera/Rays vignetted by lens system" (realistic.cpp:47): lens_rays_vignetted / lens_rays_total over every
+     * RealisticCamera::GenerateRay call, the shifted rays of the differentials included (camera.cpp:60-97) */
+    uint64_t lens_rays_total, lens_rays_vignetted;
 } PgCounters;
 #define PG_SHADING_MATERIAL_PREPASS 0x100u
 #define PG_SHADING_LISTS_DID_NOT_FIT 0x200u

@@ -5,7 +5,8 @@ sizeof() of every struct against values compiled from the headers.
 """
 import ctypes as C
 
-PG_ABI_VERSION = 29
+PG_ABI_VERSION = 30
+PG_MAX_LENS_INTERFACES = 32
 PG_SAMPLER_HALTON, PG_SAMPLER_SOBOL, PG_SAMPLER_RANDOM, PG_SAMPLER_STRATIFIED, PG_SAMPLER_ZEROTWO, PG_SAMPLER_MAXMINDIST = range(6)
 PG_OK = 0
 PG_MEM_HOST, PG_MEM_DEVICE = 0, 1
@@ -144,7 +145,11 @@ class PgRenderDesc(C.Structure):
                 ("sampler", C.c_int32), ("sobol_resolution", C.c_int32), ("sobol_log2_resolution", C.c_int32),
                 ("sampler_dims", C.c_int32), ("strat_samples", C.c_int32 * 2), ("strat_jitter", C.c_int32),
                 ("max_depth", C.c_int32), ("rr_threshold", C.c_float), ("pixel_bounds", C.c_int32 * 4),
-                ("tile_first", C.c_int32), ("tile_step", C.c_int32)]
+                ("tile_first", C.c_int32), ("tile_step", C.c_int32),
+                # ABI 30: the realistic camera's lens block (camera_type 3)
+                ("n_lens_interfaces", C.c_int32), ("lens_interfaces", (C.c_float * 4) * PG_MAX_LENS_INTERFACES),
+                ("exit_pupil_bounds", (C.c_float * 4) * 64), ("film_physical_extent", C.c_float * 4), ("film_diagonal", C.c_float),
+                ("lens_simple_weighting", C.c_int32)]
 
 
 class PgFilmPixel(C.Structure):
@@ -167,7 +172,8 @@ class PgCounters(C.Structure):
                 ("mis_rays", C.c_uint64), ("shade_ms", C.c_double), ("resolve_ms", C.c_double),
                 ("generate_ms", C.c_double), ("film_ms", C.c_double), ("shading_modes", C.c_uint64),
                 ("paths_total", C.c_uint64), ("paths_zero_radiance", C.c_uint64), ("path_length_sum", C.c_uint64), ("path_length_count", C.c_uint64),
-                ("path_length_min", C.c_uint64), ("path_length_max", C.c_uint64), ("volume_interactions", C.c_uint64), ("surface_interactions", C.c_uint64)]
+                ("path_length_min", C.c_uint64), ("path_length_max", C.c_uint64), ("volume_interactions", C.c_uint64), ("surface_interactions", C.c_uint64),
+                ("lens_rays_total", C.c_uint64), ("lens_rays_vignetted", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -54,6 +54,7 @@ struct DeviceBuffer {
 
 struct PgScene {
     int device = 0;
+    int callerAbi = PG_ABI_VERSION;  // the version the scene's creator was compiled against (pg_render_check.h): pg_counters fills what that caller's PgCounters holds
     DScene d;
     TraceConfig trace;  // k_trace's tunables for THIS scene's launches (the exact-fallback retry changes them for one call)
     DeviceBuffer nodes, wnodes, tris, spheres, bxdfs, objects, instances, instEntry, textures, textured, images, texels, ewaLut, envTables, alphas, alphaTex, triAlpha, triAttr, triS, uv, materials, lights, distTable, perms, permSums, primes, media, triMediumIn, triMediumOut, sobolMatrices, vdcSobol, vdcSobolInv, noisePerm;
@@ -90,6 +91,7 @@ struct PgScene {
     int sssCapacity = 0;
     DeviceBuffer lightHot;  // DScene::lightHot
     DeviceBuffer haltonDims;  // DScene::haltonDims
+    DeviceBuffer lensFrame;  // realistic-camera frames: the per-slot sample weights (+ differentials in textured scenes); absent otherwise
     DeviceBuffer cmaxmin, tsState, ts1, ts2;  // tile-serial samplers: CMaxMinDist, the tiles' sampler states and sample arrays
     DeviceBuffer voxelSlot, voxelRequests, voxelCounters, retryList;  // sparse "spatial" light tables (DScene::sparseLights)
     int poolSlots = 0, poolUsed = 0, nVoxelsTotal = 0;
@@ -134,7 +136,7 @@ static hipError_t upload(DeviceBuffer &b, const void *src, size_t bytes) {
 int pg_scene_create(const PgSceneDesc *desc, PgScene **out) {
     if (!desc || !out) return setError(PG_ERR_INVALID, "pg_scene_create: null argument");
     *out = nullptr;
-    if (desc->abi_version != PG_ABI_VERSION) return setError(PG_ERR_INVALID, "ABI version %d, expected %d", desc->abi_version, PG_ABI_VERSION);
+    if (!pgAbiAccepted(desc->abi_version)) return setError(PG_ERR_INVALID, "ABI version %d, expected %d", desc->abi_version, PG_ABI_VERSION);  // (PgSceneDesc is the same in 29 and 30)
     // (P may be absent when no primitive is a triangle -- a scene of quadrics only: every triangle's indices are checked against n_verts)
     if (desc->n_tris < 0 || desc->n_nodes < 0 || desc->n_verts < 0 || (desc->n_tris > 0 && (!desc->nodes || !desc->indices || (desc->n_verts > 0 && !desc->P))))
         return setError(PG_ERR_INVALID, "pg_scene_create: malformed geometry arrays");
@@ -152,6 +154,7 @@ int pg_scene_create(const PgSceneDesc *desc, PgScene **out) {
     const int status = pg_prepare_scene(desc, trace.depth, ps, err);
     if (status != PG_OK) return setError(status, "%s", err.c_str());
     PgScene *s = new PgScene;
+    s->callerAbi = desc->abi_version;
     s->device = device;
     s->trace = trace;
     memset(&s->counters, 0, sizeof(s->counters));
@@ -283,7 +286,8 @@ static int withExactFallback(PgScene *s, const std::function<int()> &call) {
 
 int pg_render_tile_count(const PgRenderDesc *desc) {
     if (!desc) return setError(PG_ERR_INVALID, "pg_render_tile_count: null argument");
-    return pgTileCount(desc);
+    PgRenderDesc current;
+    return pgTileCount(pgCurrentRenderDesc(desc, current));
 }
 
 // Queue geometry for a batch of `capacity` path slots: PG_REGIONS regions of regionCap entries (multiple of 256) such
@@ -329,7 +333,7 @@ static int ensureWorkBuffers(PgScene *s, int capacity, size_t n) {
         s->d.nestXfOff = (int)(hitParts * n);
     }  // main-queue hits, then MIS-queue hits at offset n (one launch fills both)
     HIP_TRY(s->occluded.alloc(n * sizeof(int)));
-    HIP_TRY(s->stL.alloc(n * sizeof(float4))); HIP_TRY(s->stBeta.alloc(n * sizeof(float4))); HIP_TRY(s->stMeta.alloc(n * sizeof(int4)));
+    HIP_TRY(s->stL.alloc(PG_LENS_FRAME_BYTES + n * sizeof(float4)));  /* (a realistic frame's LensFrame in front of the array) */ HIP_TRY(s->stBeta.alloc(n * sizeof(float4))); HIP_TRY(s->stMeta.alloc(n * sizeof(int4)));
     HIP_TRY(s->pdLight.alloc(n * sizeof(float4))); HIP_TRY(s->pdMis.alloc(n * sizeof(float4))); HIP_TRY(s->pdBeta.alloc(n * sizeof(float4))); HIP_TRY(s->pdInfo.alloc(n * sizeof(int4)));
     s->capacity = capacity;
     return PG_OK;
@@ -769,7 +773,7 @@ static int setUpFrame(FrameCtx &c, int capacity) {
     if (c.sssOn) if (int e = ensureSssBuffers(s, capacity, c.nQueue, c.sq, c.sssP)) return e;
     c.d = s->d;
     c.hits = (float4 *)s->hitsMain.p; c.hitsMis = c.hits + c.nQueue; c.cursors = (int *)s->cursors.p; c.cullGuard = (int *)s->cullGuard.p;
-    c.ps.L = (float4 *)s->stL.p; c.ps.beta = (float4 *)s->stBeta.p; c.ps.meta = (int4 *)s->stMeta.p;
+    c.ps.L = (float4 *)((char *)s->stL.p + PG_LENS_FRAME_BYTES); c.ps.beta = (float4 *)s->stBeta.p; c.ps.meta = (int4 *)s->stMeta.p;
     c.ps.pdLight = (float4 *)s->pdLight.p; c.ps.pdMis = (float4 *)s->pdMis.p; c.ps.pdBeta = (float4 *)s->pdBeta.p; c.ps.pdInfo = (int4 *)s->pdInfo.p;
     c.counts = (int *)s->counts.p;
     for (int i = 0; i < 4; ++i) { c.q[i].o = (float4 *)s->qo[i].p; c.q[i].d = (float4 *)s->qd[i].p; c.q[i].counts = c.counts + i * QSTRIDE; }
@@ -779,6 +783,17 @@ static int setUpFrame(FrameCtx &c, int capacity) {
     if (s->matLobes.p && s->matHead.p) { c.rp.matPre.lobes = (float4 *)s->matLobes.p; c.rp.matPre.head = (float4 *)s->matHead.p; c.rp.matPre.stride = s->matStride; }
     c.blk.resize(4 * QSTRIDE); c.vblk.resize(2 * QSTRIDE);
     c.lim = pgBounceLimits(c.rd->max_depth, s->hasNullMaterial);
+    if (c.rd->camera_type == 3) {  // the realistic camera: the lens block, zeroed statistics and room for the slots' weights, for this frame only
+        const bool diffs = s->d.hasTextured != 0;  // (the camera ray's differentials are read at the first textured hit alone)
+        const size_t weightBytes = ((size_t)capacity * sizeof(float) + 255) & ~(size_t)255;
+        const size_t need = weightBytes + (diffs ? (size_t)capacity * 3 * sizeof(float4) : 0);
+        if (s->lensFrame.bytes < need) HIP_TRY(s->lensFrame.alloc(need));
+        LensFrame head = {};
+        memcpy(&head.lens, &c.rd->n_lens_interfaces, sizeof(PgLensSystem));
+        head.weights = (float *)s->lensFrame.p;
+        head.differentials = diffs ? (float4 *)((char *)s->lensFrame.p + weightBytes) : nullptr;
+        HIP_TRY(hipMemcpy(lens_frame(c.ps.L), &head, sizeof(head), hipMemcpyHostToDevice));
+    }
     return PG_OK;
 }
 
@@ -878,6 +893,11 @@ static int accountFrame(FrameCtx &c, hipEvent_t evStart, hipEvent_t evStop) {
     }
     if (pc.path_length_count > 0) { pc.path_length_min = 0xffff - minc; pc.path_length_max = maxp - 1; }
     pc.camera_rays += c.cameraRays; pc.closest_rays += c.closestRays; pc.shadow_rays += c.shadowRays;
+    if (c.rd->camera_type == 3) {  // the realistic camera's GenerateRay calls; a sample of weight 0 entered no queue but is a camera ray all the same (integrator.cpp:296)
+        unsigned long long ls[3];
+        HIP_TRY(hipMemcpy(ls, (const char *)lens_frame(c.ps.L) + offsetof(LensFrame, stats), sizeof(ls), hipMemcpyDeviceToHost));
+        pc.lens_rays_total += ls[0]; pc.lens_rays_vignetted += ls[1]; pc.camera_rays += ls[2];
+    }
     pc.node_visits = tc[0].node_visits + tc[1].node_visits;
     pc.tri_tests = tc[0].tri_tests + tc[1].tri_tests + lt;
     pc.light_tri_tests = lt;
@@ -949,6 +969,8 @@ static int renderFrame(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, Pg
 int pg_render(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays,
               int mem, void *streamPtr) {
     if (!s || !rd || !film || !nStrays || (maxStrays > 0 && !strays)) return setError(PG_ERR_INVALID, "pg_render: null argument");
+    PgRenderDesc current;
+    rd = pgCurrentRenderDesc(rd, current);
     return withExactFallback(s, [&]() { return renderFrame(s, rd, film, strays, maxStrays, nStrays, mem, streamPtr); });
 }
 
@@ -1011,7 +1033,10 @@ const char *pg_shard_transport(void) {
     mine = g_shardTransport;
     return mine.c_str();
 }
-int pg_box_filter_needs_gather(const PgRenderDesc *rd) { return rd ? pgh_box_filter_needs_gather(rd) : 0; }
+int pg_box_filter_needs_gather(const PgRenderDesc *rd) {
+    PgRenderDesc current;
+    return rd ? pgh_box_filter_needs_gather(pgCurrentRenderDesc(rd, current)) : 0;
+}
 
 // ---- one frame over several devices of the node, from one host process ---------------------------------------------------------
 // One host thread per device (pg_set_device is per thread); every thread renders its tiles into a packed shard on its own device,
@@ -1021,6 +1046,8 @@ int pg_box_filter_needs_gather(const PgRenderDesc *rd) { return rd ? pgh_box_fil
 int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *desc, PgFilmPixel *const *film, PgStraySample *const *strays,
                       int32_t maxStrays, int32_t *nStrays) {
     if (!scenes || n < 1 || !desc || !film || !nStrays || (maxStrays > 0 && !strays)) return setError(PG_ERR_INVALID, "pg_render_sharded: null argument");
+    PgRenderDesc current;
+    desc = pgCurrentRenderDesc(desc, current);
     if (desc->tile_first != 0 || desc->tile_step != 1) return setError(PG_ERR_INVALID, "pg_render_sharded: desc must describe the whole frame (tile_first 0, tile_step 1)");
     for (int r = 0; r < n; ++r) if (!scenes[r] || (maxStrays > 0 && !strays[r])) return setError(PG_ERR_INVALID, "pg_render_sharded: null entry for rank %d", r);
     PgScene *root = scenes[0];
@@ -1271,7 +1298,7 @@ int pg_intersect_p(PgScene *s, int32_t n, const float *o, const float *d, const 
 
 int pg_counters(PgScene *s, PgCounters *out) {
     if (!s || !out) return setError(PG_ERR_INVALID, "pg_counters: null argument");
-    *out = s->counters;
+    memcpy(out, &s->counters, s->callerAbi >= 30 ? sizeof(PgCounters) : PG_ABI29_COUNTERS_BYTES);
     return PG_OK;
 }
 int pg_scene_set_option(PgScene *s, int32_t option, int32_t value) {

@@ -5,7 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <stddef.h>
 #include "../../include/pbrt_gpu.h"
+#include "pg_lens.h"  // PgLensSystem
 
 // Per-triangle flag bits stored in tris[3*i].w, on top of PG_TRI_*.
 #ifndef PG_TRI_STRIDE
@@ -315,8 +317,33 @@ struct MatPre { float4 *lobes; float4 *head; int stride; };  // lobes: packed 48
 #define PG_META_DONE 0x20000
 #define PG_META_HASDIFF 0x80000  // the ray still is the camera's RayDifferential (cleared by the first SpawnRay)
 
+// The kernels' copy of the frame's description: PgRenderDesc up to its lens block (ABI 30).  The 1.5 KB of lens tables beside the 1.6 KB before
+// them would take a shading launch's arguments past 4 KB, and one kernel reads them: they live in device memory (LensFrame) instead.  Reads as the
+// PgRenderDesc it was copied from (operator->, or bound to a const PgRenderDesc &) -- whose lens block must not be read through it.
+struct RenderDescHead {
+    alignas(4) unsigned char bytes[offsetof(PgRenderDesc, n_lens_interfaces)];
+    __host__ __device__ const PgRenderDesc *operator->() const { return reinterpret_cast<const PgRenderDesc *>(bytes); }
+    __host__ __device__ operator const PgRenderDesc &() const { return *reinterpret_cast<const PgRenderDesc *>(bytes); }
+    RenderDescHead &operator=(const PgRenderDesc &rd) { memcpy(bytes, &rd, sizeof(bytes)); return *this; }
+};
+static_assert(sizeof(PgLensSystem) == sizeof(PgRenderDesc) - offsetof(PgRenderDesc, n_lens_interfaces), "PgLensSystem mirrors PgRenderDesc's lens block");
+// A realistic-camera frame's own device state (camera_type 3): the lens block of the description, the frame's lens statistics, and where the
+// frame keeps one float per path slot -- the sample's weight (Camera::GenerateRayDifferential's return value, camera.cpp:60-97), read by the film
+// kernels -- and, in scenes with textures, three float4 per slot: the camera ray's scaled differentials (rxOrigin, rxDirection, ryOrigin,
+// ryDirection as 12 floats), read where the first textured hit needs them (tex_hit_setup); nullptr otherwise.  It lies in PG_LENS_FRAME_BYTES of
+// room IN FRONT OF PathState::L (the allocation always has them; only such frames fill them) and is not a kernel argument: a pointer more among the
+// arguments moves every kernel's scalar registers (as PG_QUEUE_TIMES found), and the other cameras' kernels are to stay as they were.
+struct LensFrame {
+    PgLensSystem lens;
+    unsigned long long stats[3];  // GenerateRay calls, of them vignetted (realistic.cpp:47); samples of weight 0 (they count as camera rays, integrator.cpp:296)
+    float *weights;
+    float4 *differentials;
+};
+#define PG_LENS_FRAME_BYTES ((sizeof(LensFrame) + 255) & ~(size_t)255)
+__host__ __device__ inline LensFrame *lens_frame(const float4 *stL) { return reinterpret_cast<LensFrame *>(reinterpret_cast<char *>(const_cast<float4 *>(stL)) - PG_LENS_FRAME_BYTES); }
+
 struct RenderParams {
-    PgRenderDesc rd;
+    RenderDescHead rd;
     int nTilesX, nTilesY;
     // batch description: tiles [tileLocal0, tileLocal0+nTilesBatch) of this shard, samples [s0, s0+sCount)
     int tileLocal0, nTilesBatch, s0, sCount;

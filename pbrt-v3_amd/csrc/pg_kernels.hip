@@ -18,6 +18,7 @@
 #include "pg_motion.h"
 #include "pg_bssrdf.h"
 #include "pg_grid.h"
+#include "pg_lens.h"
 
 #define PG_BLOCK 256
 // threads per block of the shading kernel: its blocks meet at two barriers around the queue append, so a block is only as fast
@@ -347,18 +348,18 @@ PG_DEV void ts_sobol2d(int n, float *samples, TileSamplerState &t) {  // Sobol2D
 }
 // a tile's global index, pixel (lx, ly) of it and whether that pixel exists (tiles at the image edge are clipped)
 PG_DEV bool ts_tile_pixel(const RenderParams &rp, int local, int lx, int ly, int &t, int &px, int &py) {
-    t = rp.rd.tile_first + local * rp.rd.tile_step;
+    t = rp.rd->tile_first + local * rp.rd->tile_step;
     const int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    px = rp.rd.sample_bounds[0] + tx * 16 + lx;
-    py = rp.rd.sample_bounds[1] + ty * 16 + ly;
-    return px < rp.rd.sample_bounds[2] && py < rp.rd.sample_bounds[3];
+    px = rp.rd->sample_bounds[0] + tx * 16 + lx;
+    py = rp.rd->sample_bounds[1] + ty * 16 + ly;
+    return px < rp.rd->sample_bounds[2] && py < rp.rd->sample_bounds[3];
 }
 // tileSampler = sampler->Clone(seed), seed = tile.y * nTiles.x + tile.x (integrator.cpp:247-248); RNG::SetSequence, rng.h:129-135
 __global__ void k_ts_init(DScene sc, RenderParams rp) {
     const int local = blockIdx.x * blockDim.x + threadIdx.x;
     if (local >= rp.nTilesBatch) return;
     TileSamplerState t;
-    t.state = 0u; t.inc = ((unsigned long long)(rp.rd.tile_first + local * rp.rd.tile_step) << 1u) | 1u;
+    t.state = 0u; t.inc = ((unsigned long long)(rp.rd->tile_first + local * rp.rd->tile_step) << 1u) | 1u;
     rng_u32(t);
     t.state += 0x853c49e6748fea9bULL;
     rng_u32(t);
@@ -537,14 +538,14 @@ PG_DEV bool slot_to_pixel(const RenderParams &rp, int slot, int &px, int &py, in
     int sIdx = rest % rp.sCount;
     int tileInBatch = rest / rp.sCount;
     int local = rp.tileLocal0 + tileInBatch;
-    int t = rp.rd.tile_first + local * rp.rd.tile_step;
+    int t = rp.rd->tile_first + local * rp.rd->tile_step;
     int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    px = rp.rd.sample_bounds[0] + tx * 16 + (pix & 15);
-    py = rp.rd.sample_bounds[1] + ty * 16 + (pix >> 4);
+    px = rp.rd->sample_bounds[0] + tx * 16 + (pix & 15);
+    py = rp.rd->sample_bounds[1] + ty * 16 + (pix >> 4);
     sn = rp.s0 + sIdx;
-    if (px >= rp.rd.sample_bounds[2] || py >= rp.rd.sample_bounds[3]) return false;
+    if (px >= rp.rd->sample_bounds[2] || py >= rp.rd->sample_bounds[3]) return false;
     // InsideExclusive(pixel, pixelBounds), integrator.cpp:273
-    return px >= rp.rd.pixel_bounds[0] && px < rp.rd.pixel_bounds[2] && py >= rp.rd.pixel_bounds[1] && py < rp.rd.pixel_bounds[3];
+    return px >= rp.rd->pixel_bounds[0] && px < rp.rd->pixel_bounds[2] && py >= rp.rd->pixel_bounds[1] && py < rp.rd->pixel_bounds[3];
 }
 
 // The matrix AnimatedTransform CameraToWorld carries a ray of time `time` to world space with (AnimatedTransform::operator()(Ray),
@@ -654,14 +655,69 @@ PG_DEV void camera_differentials(const PgRenderDesc &rd, const float *c2w, float
 }
 // ANIM: the camera moves (PgRenderDesc::camera_animated) -- every sample's camera-to-world matrix is interpolated at its time; the still
 // camera's kernel does not carry that code (64 instead of 39 registers, 113 spilled scalars)
-template <bool ANIM>
+// The realistic camera's sample (camera_type 3): Camera::GenerateRayDifferential over the lens system `L` (pg_lens.h) -- the main ray and the
+// shifted rays, each carried to world space by c2w and normalized (realistic.cpp:700-701) -- giving the world-space ray, the sample's weight
+// (0: vignetted), the calls' statistics, and where `diff` is not null the differentials scaled by 1 / sqrt(spp) (integrator.cpp:282-283) as 12 floats.
+PG_DEV float lens_camera_sample(const PgLensSystem &L, const PgRenderDesc &rd, const float *c2w, float pFilmX, float pFilmY, float l0, float l1, V3 &o, V3 &d, float &tMax,
+                                int &nCalls, int &nVignetted, float4 *diff) {
+    LensRay rays[3];
+    float eps[2] = {.05f, .05f};
+    auto toWorld = [&](LensRay &r) {
+        V3 ro = mk(r.o.x, r.o.y, r.o.z), rdir = mk(r.d.x, r.d.y, r.d.z);
+        float tm = PG_INF;
+        xform_ray(c2w, ro, rdir, tm);
+        rdir = normalize(rdir);
+        r.o = lens_v(ro.x, ro.y, ro.z); r.d = lens_v(rdir.x, rdir.y, rdir.z);
+    };
+    const float wt = lens_generate_ray_differential(L, pFilmX, pFilmY, rd.full_res[0], rd.full_res[1], l0, l1, rd.shutter_close - rd.shutter_open, toWorld, rays, eps,
+                                                    &nCalls, &nVignetted);
+    if (wt == 0) return 0;
+    o = mk(rays[0].o.x, rays[0].o.y, rays[0].o.z); d = mk(rays[0].d.x, rays[0].d.y, rays[0].d.z);
+    tMax = PG_INF;
+    if (diff) {
+        const V3 xo = mk(rays[1].o.x, rays[1].o.y, rays[1].o.z), xd = mk(rays[1].d.x, rays[1].d.y, rays[1].d.z);
+        const V3 yo = mk(rays[2].o.x, rays[2].o.y, rays[2].o.z), yd = mk(rays[2].d.x, rays[2].d.y, rays[2].d.z);
+        V3 rxO = o + vdiv(xo - o, eps[0]), rxD = d + vdiv(xd - d, eps[0]);  // camera.cpp:72-73, :87-88
+        V3 ryO = o + vdiv(yo - o, eps[1]), ryD = d + vdiv(yd - d, eps[1]);
+        const float sc = 1 / sqrtf((float)rd.spp);
+        rxO = o + (rxO - o) * sc; ryO = o + (ryO - o) * sc;
+        rxD = d + (rxD - d) * sc; ryD = d + (ryD - d) * sc;
+        diff[0] = make_float4(rxO.x, rxO.y, rxO.z, rxD.x); diff[1] = make_float4(rxD.y, rxD.z, ryO.x, ryO.y); diff[2] = make_float4(ryO.z, ryD.x, ryD.y, ryD.z);
+    }
+    return wt;
+}
+// The lens statistics of the lanes of a wave in one set of atomics (as the integrator statistics are counted): calls, vignetted, samples of weight 0
+PG_DEV void lens_stats_add(LensFrame *lens, int nCalls, int nVignetted, bool zeroWeight) {
+    const unsigned long long calls = wave_sum((unsigned long long)nCalls), vig = wave_sum((unsigned long long)nVignetted), zero = wave_sum(zeroWeight ? 1ull : 0ull);
+    if (lane_id() == 0 && calls) {
+        unsigned long long *st = lens->stats;
+        atomicAdd(st, calls);
+        if (vig) atomicAdd(st + 1, vig);
+        if (zero) atomicAdd(st + 2, zero);
+    }
+}
+// REAL: the realistic camera (camera_type 3), an instantiation of its own chosen only for such frames: the lens block is staged from the frame's
+// LensFrame into LDS once per block (1.5 KB; every lane walks the interfaces with a uniform index and picks a pupil box with its own), each sample
+// runs 3 to 5 lens traces, and the sample's weight goes to the LensFrame's per-slot array.  A sample of weight 0 enters no queue: its path never
+// starts (integrator.cpp:294-296: Li is not called), its L stays 0 and it still reaches the film.
+template <bool ANIM, bool REAL = false>
 __global__ __launch_bounds__(PG_BLOCK) void k_generate(DScene sc, RenderParams rp, PathState st, RayQueue q) {
+    const PgLensSystem *lensLds = nullptr;
+    if constexpr (REAL) {
+        __shared__ uint32_t s_lensWords[sizeof(PgLensSystem) / 4];
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(&lens_frame(st.L)->lens);
+        for (int k = threadIdx.x; k < (int)(sizeof(PgLensSystem) / 4); k += PG_BLOCK) s_lensWords[k] = src[k];
+        __syncthreads();
+        lensLds = reinterpret_cast<const PgLensSystem *>(s_lensWords);
+    }
     int slot = blockIdx.x * PG_BLOCK + threadIdx.x;
     bool valid = slot < rp.capacity;
     int px = 0, py = 0, sn = 0;
     if (valid) valid = slot_to_pixel(rp, slot, px, py, sn);
     V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
     float tMax = PG_INF, rayTime = 0;
+    int lensCalls = 0, lensVignetted = 0;
+    bool lensZero = false;
     if (valid) {
         const PgRenderDesc &rd = rp.rd;
         uint64_t index = sc.tsBatched ? 0 : sampler_index(sc, rd, px, py, (uint64_t)sn);
@@ -686,8 +742,20 @@ __global__ __launch_bounds__(PG_BLOCK) void k_generate(DScene sc, RenderParams r
         float pFilmX = (float)px + u0, pFilmY = (float)py + u1;
         float l0 = 0, l1 = 0;
         if (sc.tsBatched) { l0 = tsl0; l1 = tsl1; }
-        else if (rd.lens_radius > 0) { l0 = halton_sample(sc, rd, index, 3); l1 = halton_sample(sc, rd, index, 4); }
-        if constexpr (ANIM) {
+        else if (REAL || rd.lens_radius > 0) { l0 = halton_sample(sc, rd, index, 3); l1 = halton_sample(sc, rd, index, 4); }
+        float weight = 1;
+        if constexpr (REAL) {
+            LensFrame *lf = lens_frame(st.L);
+            float4 *diff = lf->differentials ? lf->differentials + 3 * (size_t)slot : nullptr;
+            if constexpr (ANIM) {
+                float c2w[16];
+                rayTime = camera_time(rd, uTime);
+                camera_matrix_at(rd, rayTime, c2w);
+                weight = lens_camera_sample(*lensLds, rd, c2w, pFilmX, pFilmY, l0, l1, o, d, tMax, lensCalls, lensVignetted, diff);
+            } else weight = lens_camera_sample(*lensLds, rd, rd.camera_to_world, pFilmX, pFilmY, l0, l1, o, d, tMax, lensCalls, lensVignetted, diff);
+            lf->weights[slot] = weight;
+            lensZero = weight == 0;
+        } else if constexpr (ANIM) {
             float c2w[16];
             rayTime = camera_time(rd, uTime);
             camera_matrix_at(rd, rayTime, c2w);
@@ -695,11 +763,13 @@ __global__ __launch_bounds__(PG_BLOCK) void k_generate(DScene sc, RenderParams r
         } else camera_ray(rd, rd.camera_to_world, pFilmX, pFilmY, l0, l1, o, d, tMax);
         st.L[slot] = make_float4(0, 0, 0, pFilmX);
         st.beta[slot] = make_float4(1, 1, 1, pFilmY);
-        st.meta[slot] = make_int4((int)(uint32_t)index, (int)(uint32_t)(index >> 32), __float_as_int(1.f), ((sc.tsBatched ? tsDim : 5) << 20) | PG_META_HASDIFF);
+        st.meta[slot] = make_int4((int)(uint32_t)index, (int)(uint32_t)(index >> 32), __float_as_int(1.f), ((sc.tsBatched ? tsDim : 5) << 20) | (lensZero ? PG_META_DONE : PG_META_HASDIFF));
+        if (lensZero) valid = false;  // the film takes the sample from its slot; no ray is queued
     } else if (slot < rp.capacity) {
         st.L[slot] = make_float4(0, 0, 0, 0);
         st.meta[slot] = make_int4(0, 0, 0, PG_META_DONE | 0x40000);  // 0x40000: slot holds no sample
     }
+    if constexpr (REAL) lens_stats_add(lens_frame(st.L), lensCalls, lensVignetted, lensZero);
     int pos;
     block_push<1, false>(&q, &valid, &pos);
     if (valid) {
@@ -707,22 +777,29 @@ __global__ __launch_bounds__(PG_BLOCK) void k_generate(DScene sc, RenderParams r
         q.d[pos] = make_float4(d.x, d.y, d.z, __int_as_float(slot));
         if (float *qt = PG_QUEUE_TIMES(sc, q)) qt[pos] = rayTime;  // Ray::time (perspective.cpp:90 / :121), read by k_trace at moving instances
         if (st.qs[0].L) { st.qs[0].L[pos] = st.L[slot]; st.qs[0].beta[pos] = st.beta[slot]; st.qs[0].meta[pos] = st.meta[slot]; }  // just written by this thread
-        if (st.qs[0].medium) st.qs[0].medium[pos] = rp.rd.camera_medium + 1;  // volpath: camera rays start in the camera's medium (camera.h:78)
+        if (st.qs[0].medium) st.qs[0].medium[pos] = rp.rd->camera_medium + 1;  // volpath: camera rays start in the camera's medium (camera.h:78)
     }
 }
 void launch_generate(const DScene &sc, const RenderParams &rp, PathState st, RayQueue q, hipStream_t s) {
     int nblk = (rp.capacity + PG_BLOCK - 1) / PG_BLOCK;
-    if (rp.rd.camera_animated || sc.hasMotion) hipLaunchKernelGGL(k_generate<true>  /* moving instances need the samples' times too */, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, rp, st, q);
-    else hipLaunchKernelGGL(k_generate<false>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, rp, st, q);
+    const bool anim = rp.rd->camera_animated || sc.hasMotion;  // (moving instances need the samples' times too)
+    if (rp.rd->camera_type == 3) {
+        if (anim) hipLaunchKernelGGL((k_generate<true, true>), dim3(nblk), dim3(PG_BLOCK), 0, s, sc, rp, st, q);
+        else hipLaunchKernelGGL((k_generate<false, true>), dim3(nblk), dim3(PG_BLOCK), 0, s, sc, rp, st, q);
+    } else if (anim) hipLaunchKernelGGL((k_generate<true>), dim3(nblk), dim3(PG_BLOCK), 0, s, sc, rp, st, q);
+    else hipLaunchKernelGGL((k_generate<false>), dim3(nblk), dim3(PG_BLOCK), 0, s, sc, rp, st, q);
 }
 
 // Tile-serial samplers: sample `sampleIndex` of every tile's current pixel -- StartNextSample's reset, GetCameraSample's draws
 // (film 2D, time 1D, lens 2D: always drawn, they advance the stream), the camera ray.  Slot = the tile's local index.
+template <bool REAL>
 __global__ __launch_bounds__(PG_BLOCK) void k_ts_generate(DScene sc, RenderParams rp, PathState st, RayQueue q, int sampleIndex) {
     const int local = blockIdx.x * PG_BLOCK + threadIdx.x;
     bool valid = local < rp.nTilesBatch && sc.ts[local].active;
     V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
     float tMax = PG_INF, rayTime = 0;
+    int lensCalls = 0, lensVignetted = 0;
+    bool lensZero = false;
     if (valid) {
         const PgRenderDesc &rd = rp.rd;
         TileSamplerState &t = sc.ts[local];
@@ -736,11 +813,19 @@ __global__ __launch_bounds__(PG_BLOCK) void k_ts_generate(DScene sc, RenderParam
         float c2w[16];
         rayTime = camera_time(rd, uTime);
         camera_matrix_at(rd, rayTime, c2w);
-        camera_ray(rd, c2w, pFilmX, pFilmY, l0, l1, o, d, tMax);
+        if constexpr (REAL) {  // (a handful of lanes per launch: the lens block is read where it lies; a sample of weight 0 has drawn its camera sample and nothing more)
+            LensFrame *lf = lens_frame(st.L);
+            const float weight = lens_camera_sample(lf->lens, rd, c2w, pFilmX, pFilmY, l0, l1, o, d, tMax, lensCalls, lensVignetted,
+                                                    lf->differentials ? lf->differentials + 3 * (size_t)local : nullptr);
+            lf->weights[local] = weight;
+            lensZero = weight == 0;
+        } else camera_ray(rd, c2w, pFilmX, pFilmY, l0, l1, o, d, tMax);
         st.L[local] = make_float4(0, 0, 0, pFilmX);
         st.beta[local] = make_float4(1, 1, 1, pFilmY);
-        st.meta[local] = make_int4(0, 0, __float_as_int(1.f), PG_META_HASDIFF);
+        st.meta[local] = make_int4(0, 0, __float_as_int(1.f), lensZero ? PG_META_DONE : PG_META_HASDIFF);
+        if (lensZero) valid = false;
     }
+    if constexpr (REAL) lens_stats_add(lens_frame(st.L), lensCalls, lensVignetted, lensZero);
     int pos;
     block_push<1, false>(&q, &valid, &pos);
     if (valid) {
@@ -748,11 +833,12 @@ __global__ __launch_bounds__(PG_BLOCK) void k_ts_generate(DScene sc, RenderParam
         q.d[pos] = make_float4(d.x, d.y, d.z, __int_as_float(local));
         if (float *qt = PG_QUEUE_TIMES(sc, q)) qt[pos] = rayTime;
         if (st.qs[0].L) { st.qs[0].L[pos] = st.L[local]; st.qs[0].beta[pos] = st.beta[local]; st.qs[0].meta[pos] = st.meta[local]; }
-        if (st.qs[0].medium) st.qs[0].medium[pos] = rp.rd.camera_medium + 1;
+        if (st.qs[0].medium) st.qs[0].medium[pos] = rp.rd->camera_medium + 1;
     }
 }
 void launch_ts_generate(const DScene &sc, const RenderParams &rp, PathState st, RayQueue q, int sampleIndex, hipStream_t s) {
-    hipLaunchKernelGGL(k_ts_generate, dim3((rp.nTilesBatch + PG_BLOCK - 1) / PG_BLOCK), dim3(PG_BLOCK), 0, s, sc, rp, st, q, sampleIndex);
+    if (rp.rd->camera_type == 3) hipLaunchKernelGGL(k_ts_generate<true>, dim3((rp.nTilesBatch + PG_BLOCK - 1) / PG_BLOCK), dim3(PG_BLOCK), 0, s, sc, rp, st, q, sampleIndex);
+    else hipLaunchKernelGGL(k_ts_generate<false>, dim3((rp.nTilesBatch + PG_BLOCK - 1) / PG_BLOCK), dim3(PG_BLOCK), 0, s, sc, rp, st, q, sampleIndex);
 }
 
 // ===========================================================================
@@ -2099,7 +2185,7 @@ PG_DEV void isect_to_world(const float *i2w, const float *w2i, Isect &is) {
 // (interaction.cpp:101-147).  sph*: a quadric hit's (u, v) and geometric dpdu / dpdv; filmX / filmY: the camera sample's pFilm
 PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQueue &qin, int i, int slot, int prim, const Tri &tri, float4 h4, V3 rayD, int inst, int inst2,
                           bool onSphere, float sphU, float sphV, V3 sphDpdu, V3 sphDpdv, const Isect &is, int4 meta, float filmX, float filmY,
-                          bool tileSerial, bool pixelArrays, uint64_t index, TexHit &th) {
+                          bool tileSerial, bool pixelArrays, uint64_t index, TexHit &th, const float4 *stL) {
     th.p = is.p;
     V3 gdpdu, gdpdv;  // the geometric dpdu / dpdv (not the shading ones)
     if (onSphere) { th.u = sphU; th.v = sphV; gdpdu = sphDpdu; gdpdv = sphDpdv; }
@@ -2117,6 +2203,12 @@ PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQue
     if (meta.w & PG_META_HASDIFF) {  // SurfaceInteraction::ComputeDifferentials, interaction.cpp:101-147
         const float4 o4 = qin.o[i];
         const V3 rayO = mk(o4.x, o4.y, o4.z);
+        V3 rxO, rxD, ryO, ryD;
+        if (rd.camera_type == 3) {  // the realistic camera: k_generate traced the shifted rays through the lens and kept the scaled differentials by slot
+            const float4 *df = lens_frame(stL)->differentials + 3 * (size_t)slot;
+            const float4 a = df[0], b = df[1], c = df[2];
+            rxO = mk(a.x, a.y, a.z); rxD = mk(a.w, b.x, b.y); ryO = mk(b.z, b.w, c.x); ryD = mk(c.y, c.z, c.w);
+        } else {
         float l0 = 0, l1 = 0;
         if (tileSerial) { l0 = sc.ts[slot].lens0; l1 = sc.ts[slot].lens1; }  // the camera sample's pLens, kept by k_ts_generate
         else if (pixelArrays) { int d2 = 1 << 6; tsb_get2d(sc, meta.x, meta.y, d2, l0, l1); }  // (its second 2D dimension)
@@ -2128,12 +2220,12 @@ PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQue
             else if (pixelArrays) { int d1 = 0; uTime = tsb_get1d(sc, meta.x, meta.y, d1); }
             else uTime = halton_sample(sc, rd, index, 2);
         }
-        V3 rxO, rxD, ryO, ryD;
         if (rd.camera_animated) {  // (two calls: one pointer that is either the description's matrix or a private array would be a generic one)
             float c2w[16];
             camera_matrix_at(rd, camera_time(rd, uTime), c2w);
             camera_differentials(rd, c2w, filmX, filmY, l0, l1, rayO, rayD, rxO, rxD, ryO, ryD);
         } else camera_differentials(rd, rd.camera_to_world, filmX, filmY, l0, l1, rayO, rayD, rxO, rxD, ryO, ryD);
+        }
         const V3 n = is.n, p = is.p;
         const float dd = dot(n, p);
         const float tx = -(dot(n, rxO) - dd) / dot(n, rxD);
@@ -2554,7 +2646,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                     TexHit th;
                     if constexpr (TEX) {
                         tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst, inst2, onSphere, sphU, sphV, sphDpdu, sphDpdv, is, meta, L4.w, B4.w, tileSerial,
-                                      pixelArrays, index, th);
+                                      pixelArrays, index, th, st.L);
                         material_bump(sc, tri.material, th, is);
                     }
                     const bool preEvaluated = PRE && m.type == PG_MAT_TEXTURED;
@@ -2821,7 +2913,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
     }
     if (deferred) {  // retried once the voxel's distribution exists: no ray, no state, no pending term leaves this launch
         pushNext = pushShadow = misCand = false;
-        if (rp.rd.sampler >= PG_SAMPLER_RANDOM) { sc.ts[slot].state = tsState0; sc.ts[slot].cur1D = tsCur1D0; sc.ts[slot].cur2D = tsCur2D0; }  // nor a draw from the tile's stream
+        if (rp.rd->sampler >= PG_SAMPLER_RANDOM) { sc.ts[slot].state = tsState0; sc.ts[slot].cur1D = tsCur1D0; sc.ts[slot].cur2D = tsCur2D0; }  // nor a draw from the tile's stream
         rp.retryList[atomicAdd(&sc.voxelCounters[1], 1)] = shade_position(rp, qin);
     }
     if (misCand) {
@@ -2972,7 +3064,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, PG_MATERIAL_WAVES) void k_material(
     float filmX = 0, filmY = 0;  // the camera sample's pFilm, for the camera ray's differentials
     if (meta.w & PG_META_HASDIFF) { filmX = bySlot ? st.L[slot].w : qsIn.L[i].w; filmY = bySlot ? st.beta[slot].w : qsIn.beta[i].w; }
     TexHit th;
-    tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst, -1, onSphere, sphU, sphV, sphDpdu, sphDpdv, is, meta, filmX, filmY, tileSerial, pixelArrays, index, th);
+    tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst, -1, onSphere, sphU, sphV, sphDpdu, sphDpdv, is, meta, filmX, filmY, tileSerial, pixelArrays, index, th, st.L);
     material_bump<1>(sc, tri.material, th, is);
     int nl = 0;
     float etaL = 1;
@@ -3000,7 +3092,8 @@ static void launch_material(const DScene &sc, const RenderParams &rp, PathState 
 // volPre instead of drawing them) and gives the entries that scatter inside the medium a class of their own.
 template <bool VOL>
 __global__ __launch_bounds__(1024) void k_shade_order(DScene sc, RayQueue q, const float4 *__restrict__ hits, int *__restrict__ order,
-                                                      PgRenderDesc rd, PathState st, VolState vs, const float *__restrict__ hitT, float2 *__restrict__ volPre, QueueState qs) {
+                                                      RenderDescHead rdHead, PathState st, VolState vs, const float *__restrict__ hitT, float2 *__restrict__ volPre, QueueState qs) {
+    const PgRenderDesc &rd = rdHead;
     constexpr int NCHUNK = PG_ORDER_WINDOW / 64, ROUNDS = PG_ORDER_WINDOW / 1024, NW = 1024 / 64;
     static_assert(PG_ORDER_WINDOW % 1024 == 0 && PG_ORDER_CLASSES == 16, "k_shade_order: window of whole blocks, 16 classes");
     const int r = blockIdx.x & (PG_REGIONS - 1), base = (blockIdx.x >> 3) * PG_ORDER_WINDOW;
@@ -3063,7 +3156,7 @@ __global__ __launch_bounds__(1024) void k_shade_order(DScene sc, RayQueue q, con
 void launch_shade_order(const DScene &sc, RayQueue qin, const float4 *hits, int *order, hipStream_t s) {
     const int nblk = PG_REGIONS * ((qin.regionCap + PG_ORDER_WINDOW - 1) / PG_ORDER_WINDOW);
     if (nblk == 0 || !sc.primClass || !order) return;
-    hipLaunchKernelGGL(k_shade_order<false>, dim3(nblk), dim3(1024), 0, s, sc, qin, hits, order, PgRenderDesc{}, PathState{}, VolState{}, (const float *)nullptr, (float2 *)nullptr, QueueState{});
+    hipLaunchKernelGGL(k_shade_order<false>, dim3(nblk), dim3(1024), 0, s, sc, qin, hits, order, RenderDescHead{}, PathState{}, VolState{}, (const float *)nullptr, (float2 *)nullptr, QueueState{});
 }
 void launch_shade_order_vol(const DScene &sc, const RenderParams &rp, PathState st, VolState vs, RayQueue qin, const float4 *hits, const float *hitT,
                             int *order, float2 *volPre, hipStream_t s, int cur) {
@@ -3251,7 +3344,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_through(DScene sc, PathState st, V
                 int4 meta = st.meta[slot];
                 const uint64_t index = (uint64_t)(uint32_t)meta.x | ((uint64_t)(uint32_t)meta.y << 32);
                 int dim = (int)((uint32_t)meta.w >> 20);
-                const bool tileSerial = rp.rd.sampler >= PG_SAMPLER_RANDOM;
+                const bool tileSerial = rp.rd->sampler >= PG_SAMPLER_RANDOM;
                 auto draw = [&]() -> float { return tileSerial ? ts_get1d(sc, slot) : halton_sample(sc, rp.rd, index, dim++); };
                 Tr = Tr * sp(grid_tr(gd, sc.gridDensity + gd.density_offset, mk(o4.x, o4.y, o4.z), rayD, surface ? hitT[ri] : o4.w, draw));
                 meta.w = (int)(((uint32_t)dim << 20) | ((uint32_t)meta.w & 0xfffffu));
@@ -3793,6 +3886,9 @@ void launch_sss_exit(const DScene &sc, const RenderParams &rp, PathState st, Sss
 // Film: one lane per pixel of the batch's tiles; samples are added in sample
 // order so a pixel's sum is the reference's (integrator.cpp:276-325).
 // ===========================================================================
+// WEIGHTED: the realistic camera's frames -- AddSample(pFilm, L, rayWeight) with the sample's weight from the LensFrame: (L * sampleWeight) * filterWeight
+// (film.h:121-161); the luminance clamp acts on L before it.  The other cameras' weight is 1 and their kernels do not read one.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(PG_BLOCK) void k_film(RenderParams rp, PathState st, PgFilmPixel *film, PgStraySample *strays, int maxStrays,
                                                     int *nStrays) {
     const int tileInBatch = blockIdx.x;
@@ -3828,7 +3924,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film(RenderParams rp, PathState st
         const float dx = pFilmX - 0.5f, dy = pFilmY - 0.5f;
         const int p0x = max((int)ceilf(dx - frx), tp0x), p0y = max((int)ceilf(dy - fry), tp0y);
         const int p1x = min((int)floorf(dx + frx) + 1, tp1x), p1y = min((int)floorf(dy + fry) + 1, tp1y);
-        Spec c = (L * 1.f) * 1.f;
+        Spec c = (L * (WEIGHTED ? lens_frame(st.L)->weights[slot] : 1.f)) * 1.f;
         for (int y = p0y; y < p1y; ++y)
             for (int x = p0x; x < p1x; ++x) {
                 if (x == px && y == py) { r += c.r; g += c.g; b += c.b; w += 1.f; }
@@ -3852,6 +3948,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film(RenderParams rp, PathState st
 // block pixel walks the tile's samples in the reference's order (pixels row-major, samples in order) and adds those whose
 // footprint covers it.  Deterministic, no atomics, and a pixel's tile-local sum has the reference's summation order;
 // the host merges the overlapping blocks in tile order (Film::MergeFilmTile).  All samples of a tile are in one batch.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, PathState st, PgFilmPixel *film) {
     const int tileInBatch = blockIdx.x;
     const PgRenderDesc &rd = rp.rd;
@@ -3920,7 +4017,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, Path
                     const float fx = fabsf(((float)X - dx) * invRx * 16), fy = fabsf(((float)Y - dy) * invRy * 16);
                     const int ifx = min((int)floorf(fx), 15), ify = min((int)floorf(fy), 15);
                     const float fw = rd.filter_table[ify * 16 + ifx];
-                    const Spec c = (L * 1.f) * fw;
+                    const Spec c = (L * (WEIGHTED ? lens_frame(st.L)->weights[slot] : 1.f)) * fw;
                     r += c.r; g += c.g; b += c.b; w += fw;
                 }
             }
@@ -3930,6 +4027,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, Path
 }
 // Tile-serial samplers: the one finished sample of every tile, added to the tile's film block exactly as FilmTile::AddSample
 // does it (film.h:121-161) -- one lane per tile walks the sample's footprint, so a block's sums have the reference's order.
+template <bool WEIGHTED>
 __global__ void k_ts_film(DScene sc, RenderParams rp, PathState st, PgFilmPixel *film, PgStraySample *strays, int maxStrays, int *nStrays) {
     const int local = blockIdx.x * blockDim.x + threadIdx.x;
     if (local >= rp.nTilesBatch || !sc.ts[local].active) return;
@@ -3954,6 +4052,7 @@ __global__ void k_ts_film(DScene sc, RenderParams rp, PathState st, PgFilmPixel 
     const float dx = pFilmX - 0.5f, dy = pFilmY - 0.5f;
     const int p0x = max((int)ceilf(dx - frx), tp0x), p0y = max((int)ceilf(dy - fry), tp0y);
     const int p1x = min((int)floorf(dx + frx) + 1, tp1x), p1y = min((int)floorf(dy + fry) + 1, tp1y);
+    const float sampleWeight = WEIGHTED ? lens_frame(st.L)->weights[local] : 1.f;
     if (rd.filter_general) {
         const int tw = 16 + rd.tile_halo[0] + rd.tile_halo[2];
         const float invRx = 1 / frx, invRy = 1 / fry;
@@ -3964,14 +4063,14 @@ __global__ void k_ts_film(DScene sc, RenderParams rp, PathState st, PgFilmPixel 
                 const float fx = fabsf(((float)x - dx) * invRx * 16);
                 const int ifx = min((int)floorf(fx), 15);
                 const float fw = rd.filter_table[ify * 16 + ifx];
-                const Spec c = (L * 1.f) * fw;
+                const Spec c = (L * sampleWeight) * fw;
                 PgFilmPixel *fp = &film[(size_t)local * rd.tile_pixels + (size_t)(y - (y0 - rd.tile_halo[1])) * tw + (x - (x0 - rd.tile_halo[0]))];
                 fp->rgb[0] += c.r; fp->rgb[1] += c.g; fp->rgb[2] += c.b; fp->weight += fw;
             }
         }
         return;
     }
-    const Spec c = (L * 1.f) * 1.f;
+    const Spec c = (L * sampleWeight) * 1.f;
     for (int y = p0y; y < p1y; ++y)
         for (int x = p0x; x < p1x; ++x) {
             if (x == px && y == py) {
@@ -3990,16 +4089,19 @@ __global__ void k_ts_film(DScene sc, RenderParams rp, PathState st, PgFilmPixel 
 }
 void launch_ts_film(const DScene &sc, const RenderParams &rp, PathState st, PgFilmPixel *film, PgStraySample *strays, int maxStrays, int *nStrays,
                     hipStream_t s) {
-    hipLaunchKernelGGL(k_ts_film, dim3((rp.nTilesBatch + 63) / 64), dim3(64), 0, s, sc, rp, st, film, strays, maxStrays, nStrays);
+    if (rp.rd->camera_type == 3) hipLaunchKernelGGL(k_ts_film<true>, dim3((rp.nTilesBatch + 63) / 64), dim3(64), 0, s, sc, rp, st, film, strays, maxStrays, nStrays);
+    else hipLaunchKernelGGL(k_ts_film<false>, dim3((rp.nTilesBatch + 63) / 64), dim3(64), 0, s, sc, rp, st, film, strays, maxStrays, nStrays);
 }
 void launch_film_general(const RenderParams &rp, PathState st, PgFilmPixel *film, hipStream_t s) {
     if (rp.nTilesBatch == 0) return;
-    hipLaunchKernelGGL(k_film_general, dim3(rp.nTilesBatch), dim3(PG_BLOCK), 0, s, rp, st, film);
+    if (rp.rd->camera_type == 3) hipLaunchKernelGGL(k_film_general<true>, dim3(rp.nTilesBatch), dim3(PG_BLOCK), 0, s, rp, st, film);
+    else hipLaunchKernelGGL(k_film_general<false>, dim3(rp.nTilesBatch), dim3(PG_BLOCK), 0, s, rp, st, film);
 }
 void launch_film(const RenderParams &rp, PathState st, PgFilmPixel *film, PgStraySample *strays, int maxStrays, int *nStrays,
                  hipStream_t s) {
     if (rp.nTilesBatch == 0) return;
-    hipLaunchKernelGGL(k_film, dim3(rp.nTilesBatch), dim3(PG_BLOCK), 0, s, rp, st, film, strays, maxStrays, nStrays);
+    if (rp.rd->camera_type == 3) hipLaunchKernelGGL(k_film<true>, dim3(rp.nTilesBatch), dim3(PG_BLOCK), 0, s, rp, st, film, strays, maxStrays, nStrays);
+    else hipLaunchKernelGGL(k_film<false>, dim3(rp.nTilesBatch), dim3(PG_BLOCK), 0, s, rp, st, film, strays, maxStrays, nStrays);
 }
 
 // ===========================================================================

@@ -5,6 +5,9 @@
 #ifndef PG_RENDER_CHECK_H
 #define PG_RENDER_CHECK_H
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
 #include <string>
 #include "pg_scene_prep.h"  // pgPrepFail
 // What the checks need to know about the scene the frame is rendered on
@@ -19,6 +22,27 @@ inline int pgTileCount(const PgRenderDesc *rd) {
     if (nx <= 0 || ny <= 0 || rd->tile_step <= 0 || rd->tile_first < 0) return 0;
     int total = nx * ny;
     return rd->tile_first >= total ? 0 : (total - rd->tile_first + rd->tile_step - 1) / rd->tile_step;
+}
+
+// ABI 30 appended to PgRenderDesc (the realistic camera's lens block) and to PgCounters (its two statistics) and changed nothing before them; PgSceneDesc is
+// the same.  A caller compiled against ABI 29 -- a host application, or the reference-side binding, built before the library was replaced -- therefore goes on
+// working: its descriptions are taken as what they are, the first PG_ABI29_RENDER_DESC_BYTES of today's PgRenderDesc with the lens block absent (no byte behind
+// them is read), and pg_counters fills the PG_ABI29_COUNTERS_BYTES such a caller has room for.  Any other version is refused as before.
+#define PG_ABI_OLDEST_ACCEPTED 29
+#define PG_ABI29_RENDER_DESC_BYTES offsetof(PgRenderDesc, n_lens_interfaces)
+#define PG_ABI29_COUNTERS_BYTES offsetof(PgCounters, lens_rays_total)
+inline bool pgAbiAccepted(int version) { return version >= PG_ABI_OLDEST_ACCEPTED && version <= PG_ABI_VERSION; }
+// The caller's render description as a description of THIS version: `rd` itself, or -- for an ABI 29 caller -- `local`, filled from the bytes that caller owns
+// (an ABI 29 caller's object is SHORTER than PgRenderDesc: until the version is known the description is read as bytes, never through a member of the longer type)
+inline const PgRenderDesc *pgCurrentRenderDesc(const PgRenderDesc *rd, PgRenderDesc &local) {
+    static_assert(offsetof(PgRenderDesc, abi_version) == 0, "the version is a description's first field");
+    int32_t version;
+    memcpy(&version, rd, sizeof(version));
+    if (version != 29) return rd;
+    memset(&local, 0, sizeof(local));
+    memcpy(&local, rd, PG_ABI29_RENDER_DESC_BYTES);
+    local.abi_version = PG_ABI_VERSION;
+    return &local;
 }
 
 // PG_OK, or PG_ERR_INVALID with its message in err
@@ -53,6 +77,19 @@ inline int pg_check_render_desc(const PgRenderDesc *rd, const RenderSceneFacts &
     if (!rd->filter_general && pgh_box_filter_needs_gather(rd))
         RC_FAIL("pg_render: filter_general = 0, but in this frame a film position can round up onto the next pixel "
                 "(pg_box_filter_needs_gather, include/pbrt_gpu.h): render it with filter_general = 1");
+    // ABI 30: the cameras, and the realistic camera's lens block (the device indexes both tables with what is checked here)
+    if (rd->camera_type < 0 || rd->camera_type > 3) RC_FAIL("pg_render: camera_type %d (0 = perspective, 1 = orthographic, 2 = environment, 3 = realistic)", rd->camera_type);
+    if (rd->camera_type == 3) {
+        if (rd->n_lens_interfaces < 1 || rd->n_lens_interfaces > PG_MAX_LENS_INTERFACES)
+            RC_FAIL("pg_render: realistic camera with %d lens interfaces (1 .. %d)", rd->n_lens_interfaces, PG_MAX_LENS_INTERFACES);
+        for (int i = 0; i < rd->n_lens_interfaces; ++i)
+            if (!(rd->lens_interfaces[i][3] > 0) || !std::isfinite(rd->lens_interfaces[i][3]))
+                RC_FAIL("pg_render: lens interface %d has aperture radius %g (finite and positive)", i, (double)rd->lens_interfaces[i][3]);
+        for (int i = 0; i < 64; ++i)
+            if (!(rd->exit_pupil_bounds[i][0] <= rd->exit_pupil_bounds[i][2] && rd->exit_pupil_bounds[i][1] <= rd->exit_pupil_bounds[i][3]))
+                RC_FAIL("pg_render: exit pupil box %d is empty (min > max)", i);
+        if (!(rd->film_diagonal > 0) || !std::isfinite(rd->film_diagonal)) RC_FAIL("pg_render: realistic camera on a film of diagonal %g", (double)rd->film_diagonal);
+    }
     return PG_OK;
 }
 #undef RC_FAIL

@@ -1416,12 +1416,16 @@ static GpuPathIntegrator *MakeIntegrator() {
     SetFilmFilter(film, filterName, ro.FilterParams);
     ro.FilterParams.ReportUnused();
     ro.FilmParams.ReportUnused();
-    if (ro.CameraName != "perspective" && ro.CameraName != "orthographic" && ro.CameraName != "environment") {
-        Error("Camera \"%s\" is outside this build's closed set (perspective, orthographic, environment).", ro.CameraName.c_str());
+    if (ro.CameraName != "perspective" && ro.CameraName != "orthographic" && ro.CameraName != "environment" && ro.CameraName != "realistic") {
+        Error("Camera \"%s\" is outside this build's closed set (perspective, orthographic, environment, realistic).", ro.CameraName.c_str());
         delete film;
         return nullptr;
     }
-    std::shared_ptr<PerspectiveCamera> camera(CreatePerspectiveCamera(ro.CameraParams, ro.CameraToWorld[0], film, ro.CameraName == "orthographic"));
+    std::shared_ptr<PerspectiveCamera> camera;
+    if (ro.CameraName == "realistic") {
+        camera.reset(CreateRealisticCamera(ro.CameraParams, ro.CameraToWorld[0], film, &ro.refused));
+        if (!camera) { delete film; return nullptr; }  // MakeCamera's "Unable to create camera", api.cpp:1662-1666: no frame
+    } else camera.reset(CreatePerspectiveCamera(ro.CameraParams, ro.CameraToWorld[0], film, ro.CameraName == "orthographic"));
     // AnimatedTransform animatedCam2World(CameraToWorld[0], transformStartTime, CameraToWorld[1], transformEndTime), api.cpp:1725-1730: every
     // camera ray is carried to world space by the transform interpolated at its time (cameras/perspective.cpp:89-91, :139)
     camera->CameraToWorldEnd = ro.CameraToWorld[1];

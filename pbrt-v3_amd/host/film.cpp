@@ -45,6 +45,12 @@ void Film::GetSampleBounds(int out[4]) const {  // film.cpp:80-86
     out[2] = (int)std::ceil((Float)croppedPixelBounds[2] - 0.5f + filterRadius[0]);
     out[3] = (int)std::ceil((Float)croppedPixelBounds[3] - 0.5f + filterRadius[1]);
 }
+void Film::GetPhysicalExtent(Float out[4]) const {  // film.cpp:88-93
+    Float aspect = (Float)fullResolution[1] / (Float)fullResolution[0];
+    Float x = std::sqrt(diagonal * diagonal / (1 + aspect * aspect));
+    Float y = aspect * x;
+    out[0] = -x / 2; out[1] = -y / 2; out[2] = x / 2; out[3] = y / 2;
+}
 void Film::Clear() { for (auto &p : pixels) p = Pixel(); }
 
 // ---- pixel filters: filters/{box,gaussian,mitchell,sinc,triangle}.{h,cpp}, filter.h:50-66 ------------------------
@@ -416,9 +422,11 @@ Film *CreateFilm(const ParamSet &params, Float frx, Float fry) {  // film.cpp:21
         crop[2] = clamp01(PbrtOptions.cropWindow[1][0]); crop[3] = clamp01(PbrtOptions.cropWindow[1][1]);
     }
     Float scale = params.FindOneFloat("scale", 1.);
-    params.FindOneFloat("diagonal", 35.);
+    Float diagonal = params.FindOneFloat("diagonal", 35.);
     Float maxSampleLuminance = params.FindOneFloat("maxsampleluminance", Infinity);
     int res[2] = {xres, yres};
-    return new Film(res, crop, frx, fry, filename, scale, maxSampleLuminance);
+    Film *film = new Film(res, crop, frx, fry, filename, scale, maxSampleLuminance);
+    film->diagonal = diagonal * .001;  // film.cpp:49: a double product rounded once
+    return film;
 }
 }  // namespace pbrt

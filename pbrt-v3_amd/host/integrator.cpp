@@ -435,7 +435,11 @@ void GpuPathIntegrator::FillRenderDesc(PgRenderDesc *rd) const {
     memset(rd, 0, sizeof(*rd));
     rd->abi_version = PG_ABI_VERSION;
     const Film &film = *camera->film;
-    rd->camera_type = camera->environment ? 2 : (camera->orthographic ? 1 : 0);
+    rd->camera_type = camera->realistic ? 3 : (camera->environment ? 2 : (camera->orthographic ? 1 : 0));
+    if (camera->realistic) {  // the lens block (ABI 30) is PgLensSystem field for field
+        static_assert(sizeof(PgLensSystem) == sizeof(PgRenderDesc) - offsetof(PgRenderDesc, n_lens_interfaces), "PgLensSystem mirrors PgRenderDesc's lens block");
+        memcpy(&rd->n_lens_interfaces, &camera->lens, sizeof(PgLensSystem));
+    }
     rd->integrator = volumetric ? 1 : 0;
     rd->camera_medium = cameraMedium;
     memcpy(rd->raster_to_camera, camera->RasterToCamera.GetMatrix().m, 16 * sizeof(float));

@@ -12,6 +12,7 @@
 #include <functional>
 #include <vector>
 #include "../../include/pbrt_gpu.h"
+#include "../csrc/pg_lens.h"  // PgLensSystem: the realistic camera's lens block and its arithmetic, shared with the device
 #include "geometry.h"
 #include "paramset.h"
 
@@ -170,6 +171,8 @@ class Film {
     void ComputeImage(std::vector<Float> *rgb) const;
     void WriteImage() const;
     int fullResolution[2];
+    Float diagonal = 0.035f;  // "diagonal" * .001 (film.cpp:49): metres; the realistic camera's film size
+    void GetPhysicalExtent(Float out[4]) const;  // film.cpp:88-93: pMin.x, pMin.y, pMax.x, pMax.y
     int croppedPixelBounds[4];
     Float filterRadius[2];
     // filterTable (film.cpp:68-77) and whether the general FilmTile path is needed (anything but a box of radius <= 0.5)
@@ -207,8 +210,14 @@ struct PerspectiveCamera {  // ProjectiveCamera (core/camera.h:87-108): cameras/
     bool animated = false;
     Float lensRadius, focalDistance, shutterOpen, shutterClose;
     std::unique_ptr<Film> film;
+    // RealisticCamera (cameras/realistic.cpp): no projection; the focused lens system and its exit pupil boxes (csrc/pg_lens.h)
+    bool realistic = false;
+    PgLensSystem lens = {};
 };
 PerspectiveCamera *CreatePerspectiveCamera(const ParamSet &params, const Transform &cam2world, Film *film, bool orthographic = false);
+// host/realistic.cpp.  nullptr: no camera, hence no frame (an Error has been reported; the film is the caller's to delete); *refused is set where the
+// reference would have ended its process at a CHECK
+PerspectiveCamera *CreateRealisticCamera(const ParamSet &params, const Transform &cam2world, Film *film, bool *refused);
 
 struct HaltonSampler {  // samplers/halton.cpp:65-92
     int samplesPerPixel;
