@@ -578,6 +578,34 @@ static inline int pgh_box_filter_needs_gather(const PgRenderDesc *rd) {
     return (sx >= (float)(xMax + 1) || sy >= (float)(yMax + 1)) ? 1 : 0;
 }
 
+/* DirectLightingIntegrator (integrators/directlighting.cpp), beside a PgRenderDesc whose `integrator` is 0 and whose `max_depth` is the
+ * integrator's "maxdepth": what pg_render_direct needs on top of the frame's description.  Not a part of PgRenderDesc, which no ABI 30
+ * caller sees change. */
+typedef struct PgDirectLightingDesc {
+    int32_t strategy;             /* 0 = UniformSampleAll (the default), 1 = UniformSampleOne; directlighting.cpp:100-113 */
+    int32_t n_lights;             /* must equal the scene's light count */
+    const int32_t *light_samples; /* strategy 0: nLightSamples[j] = sampler.RoundCount(light j's nSamples), directlighting.cpp:49-50; each >= 1 */
+} PgDirectLightingDesc;
+
+/* Can some material of the scene add a SpecularReflection or SpecularTransmission lobe when its BxDFs are built with
+ * allowMultipleLobes = false, as DirectLightingIntegrator::Li builds them (directlighting.cpp:75)?  Li then follows such lobes with
+ * SpecularReflect / SpecularTransmit while depth + 1 < maxdepth (directlighting.cpp:91-95), which pg_render_direct does not trace:
+ * it refuses "maxdepth" >= 2 on a scene for which this returns 1.  Conservative: 1 where it cannot be ruled out.
+ *  - a constant material's BxDF list holds SpecularReflection, SpecularTransmission, or the FresnelSpecular that stands for the two
+ *    lobes the reference adds instead (glass.cpp:62, subsurface.cpp:64, kdsubsurface.cpp:61);
+ *  - a material with textured parameters is of kind mirror, glass or uber (a mix's two materials are materials of the scene themselves);
+ *  - the scene has a subsurface material (its BSSRDF table).
+ * Header-only, like pgh_box_filter_needs_gather(): a front end decides without the device library. */
+static inline int pgh_scene_may_add_specular_lobes(const PgSceneDesc *sd) {
+    int32_t i;
+    if (sd->n_bssrdfs > 0) return 1;
+    for (i = 0; i < sd->n_bxdfs; ++i)
+        if (sd->bxdfs[i].type == PG_BXDF_SPECULAR_R || sd->bxdfs[i].type == PG_BXDF_SPECULAR_T || sd->bxdfs[i].type == PG_BXDF_FRESNEL_SPECULAR) return 1;
+    for (i = 0; i < sd->n_textured; ++i)
+        if (sd->textured[i].kind == PG_KIND_MIRROR || sd->textured[i].kind == PG_KIND_GLASS || sd->textured[i].kind == PG_KIND_UBER) return 1;
+    return 0;
+}
+
 /* One film pixel as accumulated by FilmTile::AddSample (film.h:121-161):
  * RGB contribution sum (tile-local, pre-XYZ) and filter weight sum.          */
 typedef struct PgFilmPixel { float rgb[3]; float weight; } PgFilmPixel;
@@ -666,6 +694,18 @@ int pg_render_tile_count(const PgRenderDesc *desc);
 int pg_render(PgScene *scene, const PgRenderDesc *desc, PgFilmPixel *film,
               PgStraySample *strays, int32_t max_strays, int32_t *n_strays,
               int mem, void *stream);
+
+/* SamplerIntegrator::Render under the DirectLightingIntegrator (integrators/directlighting.cpp) for the shard in desc.  desc is taken as
+ * pg_render takes it -- film, camera, sampler, pixel_bounds, tile_first / tile_step; film, strays and pg_render_tile_count as there --
+ * with max_depth = the integrator's "maxdepth", integrator = 0 and rr_threshold ignored; dl adds the strategy and the lights' sample
+ * counts.  Both descriptions are checked on the host before the device is touched (pg_check_render_desc, then pg_check_direct_desc,
+ * csrc/pg_render_check.h): PG_ERR_INVALID with its text for a frame outside what is built -- strategy 0 under a PixelSampler,
+ * "maxdepth" >= 2 on a scene that can add specular lobes (pgh_scene_may_add_specular_lobes), sample dimensions beyond the tables.
+ * What is rendered is Li without its specular bounces (directlighting.cpp:91-95), which no accepted frame traces: every other frame of the integrator,
+ * bit for bit.  One launch per (light, sample) step over the camera rays' hits; the step count is the sum of light_samples, or 1 for strategy 1.
+ * PgCounters: camera_rays, closest_rays, shadow_rays and mis_rays count what the reference's statistics count; the path integrators' own stay 0. */
+int pg_render_direct(PgScene *scene, const PgRenderDesc *desc, const PgDirectLightingDesc *dl, PgFilmPixel *film,
+                     PgStraySample *strays, int32_t max_strays, int32_t *n_strays, int mem, void *stream);
 
 /* The frame sharded over n devices of one node from ONE host process -- what main/pbrt.cpp:94-100 + tools/imgtool.cpp:190-285
  * do across machines with crop windows.  scenes[r] is the scene created on device r (pg_set_device + pg_scene_create, the

@@ -26,6 +26,9 @@ void pbrt_host_free(PbrtHostScene *s);
 
 const PgSceneDesc *pbrt_host_scene_desc(PbrtHostScene *s);
 void pbrt_host_render_desc(PbrtHostScene *s, PgRenderDesc *out);
+/* Integrator "directlighting": what pg_render_direct takes beside the render description (owned by the scene, valid until
+ * pbrt_host_free); NULL for the path integrators, which render through pg_render. */
+const PgDirectLightingDesc *pbrt_host_direct_desc(PbrtHostScene *s);
 
 /* Film: cropped image size; MergeFilmTile for one shard; final RGB image
  * (row-major, top row first, 3 floats per pixel) as Film::WriteImage computes it. */

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import abi
-from .abi import (PgCounters, PgFilmPixel, PgRenderDesc, PgSceneDesc, PgStraySample, PG_MEM_DEVICE, PG_MEM_HOST,
+from .abi import (PgCounters, PgDirectLightingDesc, PgFilmPixel, PgRenderDesc, PgSceneDesc, PgStraySample, PG_MEM_DEVICE, PG_MEM_HOST,
                   PG_OK)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -57,6 +57,14 @@ def gpu_lib():
     return _gpu
 
 
+def _path_family_only(rd, what):
+    """pg_render and pg_render_sharded trace paths whatever scene a description came from, and a directlighting scene's PgRenderDesc cannot
+    be told from a path frame's (integrator = 0): the binding remembers where the description came from and refuses instead."""
+    if getattr(rd, "direct_lighting", False):
+        raise PbrtGpuError(f"{what}: the description belongs to an Integrator \"directlighting\" scene; render it with render_direct / "
+                           "render_device_direct and HostScene.direct_desc() (render_scene dispatches); no path-traced frame is given in its place")
+
+
 def _check(status, what):
     if status != PG_OK:
         msg = gpu_lib().pg_last_error()
@@ -88,7 +96,14 @@ class HostScene:
         rd = PgRenderDesc()
         host_lib().pbrt_host_render_desc(self._h, C.byref(rd))
         rd.tile_first, rd.tile_step = tile_first, tile_step
+        rd.direct_lighting = bool(host_lib().pbrt_host_direct_desc(self._h))
         return rd
+
+    def direct_desc(self):
+        """Integrator "directlighting": the PgDirectLightingDesc that goes with render_desc() (its light_samples array belongs to this
+        scene: keep the scene alive while the description is in use); None for the path integrators."""
+        p = host_lib().pbrt_host_direct_desc(self._h)
+        return p.contents if p else None
 
     @property
     def film_size(self):
@@ -211,6 +226,7 @@ class GpuScene:
 
     def render(self, rd, max_strays=None, stream=None):
         """Integrator::Render for the shard in rd into host numpy buffers (film, strays)."""
+        _path_family_only(rd, "GpuScene.render")
         n = self.tile_count(rd)
         if max_strays is None:
             max_strays = default_max_strays(rd, n)
@@ -223,8 +239,26 @@ class GpuScene:
 
     def render_device(self, rd, film_ptr, strays_ptr, max_strays, nstrays_ptr, stream=None):
         """Same, into caller-owned device buffers (raw pointers; e.g. torch tensors' data_ptr())."""
+        _path_family_only(rd, "GpuScene.render_device")
         _check(gpu_lib().pg_render(self._h, C.byref(rd), film_ptr, strays_ptr, max_strays, nstrays_ptr, PG_MEM_DEVICE,
                                    stream), "pg_render")
+
+    def render_direct(self, rd, dl, max_strays=None, stream=None):
+        """Integrator::Render under the DirectLightingIntegrator (pg_render_direct): rd as for render(), dl from HostScene.direct_desc()."""
+        n = self.tile_count(rd)
+        if max_strays is None:
+            max_strays = default_max_strays(rd, n)
+        film = np.zeros(n * rd.tile_pixels, FILM_PIXEL_DTYPE)
+        strays = np.zeros(max_strays, STRAY_DTYPE)
+        ns = C.c_int32(0)
+        _check(gpu_lib().pg_render_direct(self._h, C.byref(rd), C.byref(dl), film.ctypes.data, strays.ctypes.data, max_strays, C.byref(ns),
+                                          PG_MEM_HOST, stream), "pg_render_direct")
+        return film, strays[:ns.value]
+
+    def render_device_direct(self, rd, dl, film_ptr, strays_ptr, max_strays, nstrays_ptr, stream=None):
+        """Same, into caller-owned device buffers (raw pointers), as render_device()."""
+        _check(gpu_lib().pg_render_direct(self._h, C.byref(rd), C.byref(dl), film_ptr, strays_ptr, max_strays, nstrays_ptr, PG_MEM_DEVICE,
+                                          stream), "pg_render_direct")
 
     def intersect(self, o, d, tmax):
         """Batched Scene::Intersect on host arrays: returns prim (int32), t, bary (n,3)."""
@@ -266,6 +300,7 @@ def render_sharded(gpu_scenes, rd, max_strays=None):
     """pg_render_sharded: the frame of rd (tile_first 0, tile_step 1) over the devices of gpu_scenes -- one host thread per
     device, the packed shards gathered on the first device by one ncclGather (RCCL) or, where RCCL cannot run, peer copies
     (shard_transport() tells which).  Returns [(shard rd, film, strays)] per rank."""
+    _path_family_only(rd, "render_sharded")
     n = len(gpu_scenes)
     shards = []
     for r in range(n):
@@ -295,7 +330,8 @@ def render_scene(scene, device=0):
     gs = GpuScene(scene.desc, device)
     try:
         rd = scene.render_desc()
-        film, strays = gs.render(rd)
+        dl = scene.direct_desc()
+        film, strays = gs.render(rd) if dl is None else gs.render_direct(rd, dl)
         scene.film_clear()
         scene.film_merge(rd, film, strays)
         return scene.film_image(), gs.counters()

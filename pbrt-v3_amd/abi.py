@@ -131,6 +131,9 @@ class PgSceneDesc(C.Structure):
 
 
 class PgRenderDesc(C.Structure):
+    # Not a field of the C structure: set by HostScene.render_desc() for an Integrator "directlighting" scene, whose description carries
+    # integrator = 0 like a path frame's.  The path entry points of the binding refuse such a description (pbrt_v3_amd._path_family_only).
+    direct_lighting = False
     _fields_ = [("abi_version", C.c_int32), ("integrator", C.c_int32), ("camera_medium", C.c_int32), ("camera_type", C.c_int32),
                 ("raster_to_camera", C.c_float * 16), ("dx_camera", C.c_float * 3), ("dy_camera", C.c_float * 3), ("camera_to_world", C.c_float * 16),
                 ("lens_radius", C.c_float), ("focal_distance", C.c_float),
@@ -150,6 +153,10 @@ class PgRenderDesc(C.Structure):
                 ("n_lens_interfaces", C.c_int32), ("lens_interfaces", (C.c_float * 4) * PG_MAX_LENS_INTERFACES),
                 ("exit_pupil_bounds", (C.c_float * 4) * 64), ("film_physical_extent", C.c_float * 4), ("film_diagonal", C.c_float),
                 ("lens_simple_weighting", C.c_int32)]
+
+
+class PgDirectLightingDesc(C.Structure):
+    _fields_ = [("strategy", C.c_int32), ("n_lights", C.c_int32), ("light_samples", C.POINTER(C.c_int32))]
 
 
 class PgFilmPixel(C.Structure):
@@ -189,6 +196,8 @@ GPU_SYMBOLS = {
     "pg_render_tile_count": (C.c_int, [C.POINTER(PgRenderDesc)]),
     "pg_render": (C.c_int, [C.c_void_p, C.POINTER(PgRenderDesc), C.c_void_p, C.c_void_p, C.c_int32,
                             C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_render_direct": (C.c_int, [C.c_void_p, C.POINTER(PgRenderDesc), C.POINTER(PgDirectLightingDesc), C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_void_p, C.c_int, C.c_void_p]),
     "pg_render_sharded": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(PgRenderDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                     C.c_int32, C.POINTER(C.c_int32)]),
     "pg_shard_transport": (C.c_char_p, []),
@@ -209,6 +218,7 @@ HOST_SYMBOLS = {
     "pbrt_host_free": (None, [C.c_void_p]),
     "pbrt_host_scene_desc": (C.POINTER(PgSceneDesc), [C.c_void_p]),
     "pbrt_host_render_desc": (None, [C.c_void_p, C.POINTER(PgRenderDesc)]),
+    "pbrt_host_direct_desc": (C.POINTER(PgDirectLightingDesc), [C.c_void_p]),
     "pbrt_host_film_size": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pbrt_host_film_clear": (None, [C.c_void_p]),
     "pbrt_host_film_merge": (None, [C.c_void_p, C.POINTER(PgRenderDesc), C.c_void_p, C.c_void_p, C.c_int]),

@@ -79,6 +79,8 @@ struct PgScene {
     PgCounters counters;
     std::vector<hipEvent_t> events;
     bool hasNullMaterial = false;
+    bool maySpecularLobes = false;  // pgh_scene_may_add_specular_lobes of the description (pg_render_direct's checks)
+    DeviceBuffer directAcc;  // pg_render_direct: two float4 per path slot, the accumulators Ld (one light's samples) and Lall (the lights' sum) of pg_direct.h
     // VolPathIntegrator work buffers (sized on the first volpath render)
     int volCapacity = 0;
     int nMedia = 0;
@@ -160,6 +162,7 @@ int pg_scene_create(const PgSceneDesc *desc, PgScene **out) {
     memset(&s->counters, 0, sizeof(s->counters));
     s->matStride = ps.matStride; s->volOrder = ps.volOrder; s->hasNullMaterial = ps.hasNullMaterial; s->nMedia = ps.nMedia;
     s->nVoxelsTotal = ps.nVoxelsTotal; s->poolSlots = ps.poolSlots;
+    s->maySpecularLobes = pgh_scene_may_add_specular_lobes(desc) != 0;
     DScene &d = s->d;
     d = ps.d;
 #define FAIL(code, ...) do { int c_ = setError(code, __VA_ARGS__); pg_scene_destroy(s); return c_; } while (0)
@@ -438,6 +441,8 @@ struct FrameCtx {
     unsigned long long *lightTests = nullptr;
     PgFilmPixel *dFilm = nullptr; PgStraySample *dStrays = nullptr; int *dNStrays = nullptr, maxStrays = 0;  // device film / stray buffers (the caller's when mem == DEVICE)
     BounceLimits lim = {};
+    const PgDirectLightingDesc *direct = nullptr;  // a DirectLightingIntegrator frame (pg_render_direct): stepsDirect instead of the bounce loops
+    float4 *directLd = nullptr, *directAll = nullptr;  // its per-slot accumulators (PgScene::directAcc)
     DeviceBuffer countLog;  // per-bounce queue sizes, copied back after the batch for the ray statistics
     std::vector<int> hostCounts, curQueueOfBounce, blk, vblk;  // (blk / vblk: host copies of the counter blocks of q[] / vq[])
     uint64_t closestRays = 0, shadowRays = 0, cameraRays = 0, closestLaunches = 0, shadowLaunches = 0;
@@ -738,7 +743,82 @@ static int bouncesPath(FrameCtx &c, const std::function<void()> &generate, const
     if (iters > 0) c.cameraRays += queueTotal(c.hostCounts.data(), c.curQueueOfBounce[0]);
     return PG_OK;
 }
-static int tracePaths(FrameCtx &c, const std::function<void()> &generate, const std::function<void()> &film) { return c.vol ? bouncesVolpath(c, generate, film) : bouncesPath(c, generate, film); }
+// The same under DirectLightingIntegrator::Li without its specular bounces (directlighting.cpp:62-95; pg_direct.h).  A "level" is one main queue: the camera
+// rays' hits, then -- scenes with surfaces that have no material -- the hits of the rays re-spawned behind such surfaces, until none is left.  Launch order per
+// level (one stream): for every (light, sample) step direct(step) -> any-hit(its shadow rays) -> closest-hit(its BSDF-sampled rays) -> resolve(step) into the
+// slots' Ld; after a light's last sample fold(Ld / nSamples -> Lall); after the last light fold(Lall -> L); then closest-hit(the re-spawned rays).
+static int stepsDirect(FrameCtx &c, const std::function<void()> &generate, const std::function<void()> &film) {
+    PgScene *s = c.s; const PgRenderDesc *rd = c.rd; const PgDirectLightingDesc *dl = c.direct;
+    const hipStream_t stream = c.stream; RayQueue *const q = c.q;
+    // the steps of one level and the divisions that follow them
+    struct Step { DirectStep ds; float foldLd; bool foldAll; };  // foldLd != 0: after this step Lall += Ld / foldLd (strategy 1: L += Ld / foldLd); foldAll: then L += Lall
+    std::vector<Step> steps;
+    const int nLights = dl->n_lights;
+    if (nLights == 0) steps.push_back({{1, -1, 0, 0, 0}, 0.f, false});  // directlighting.cpp:82: no light sampling at all
+    else if (dl->strategy == 1) steps.push_back({{1, -2, 6, 0, 0}, 1.f / (float)nLights, false});  // Get1D at dimension 5, then uLight, uScattering
+    else
+        for (int j = 0; j < nLights; ++j) {
+            // max_depth 0: no array was requested (directlighting.cpp:53): one Get2D pair per light from the sequential dimensions and no division
+            const int n = rd->max_depth >= 1 ? dl->light_samples[j] : 1;
+            for (int k = 0; k < n; ++k)
+                steps.push_back({{steps.empty() ? 1 : 0, j, 5 + 4 * j, rd->max_depth >= 1 ? n : 0, k}, k == n - 1 ? (float)n : 0.f, k == n - 1 && j == nLights - 1});
+        }
+    const size_t nSteps = steps.size();
+    if (c.countLog.bytes < sizeof(int) * 4 * QSTRIDE * nSteps) HIP_TRY(c.countLog.alloc(sizeof(int) * 4 * QSTRIDE * nSteps));
+    HIP_TRY(hipMemsetAsync(c.directLd, 0, 2 * sizeof(float4) * (size_t)(c.directAll - c.directLd), stream));
+    if (int e = startBatch(c, generate)) return e;
+    int cur = 0;
+    if (int e = c.timer.run(0, stream, [&] { launch_closest(c.d, s->trace, q[cur], c.hits, nullptr, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+    ++c.closestLaunches;
+    DScene dmis = c.d;  // the BSDF-sampled rays' hits, instances and interpolated matrices go behind the main queue's, which every step of a level reads again
+    if (dmis.hitInst) dmis.hitInst += c.nQueue;
+    if (dmis.animXf) dmis.animXf += c.nQueue * PG_XF_STRIDE;
+    PathState acc = c.ps;  // k_resolve adds a step's EstimateDirect to "the path's L by slot": the Ld accumulator
+    acc.L = c.directLd;
+    c.hostCounts.resize(4 * QSTRIDE * nSteps);
+    for (long long level = 0;; ++level) {
+        if (level >= c.lim.maxIters) return setError(PG_ERR_UNSUPPORTED, "camera rays through more than %lld surfaces without a material", (long long)c.lim.maxIters);
+        const int nxt = cur ^ 1;
+        HIP_TRY(hipMemsetAsync(c.counts + nxt * QSTRIDE, 0, QSTRIDE * sizeof(int), stream));
+        for (size_t si = 0; si < nSteps; ++si) {
+            const Step &st = steps[si];
+            HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
+            if (int e = c.timer.run(2, stream, [&] { launch_direct(c.d, c.rp, c.ps, q[cur], c.hits, q[nxt], q[2], q[3], c.lightTests, st.ds, stream); })) return e;
+            ++c.shadeLaunches;
+            if (st.ds.light != -1) {
+                if (int e = c.timer.run(1, stream, [&] { launch_anyhit(c.d, s->trace, q[2], (int *)s->occluded.p, c.cnShadow, (int *)s->cursors2.p, stream); })) return e;
+                ++c.shadowLaunches;
+                if (int e = c.timer.run(0, stream, [&] { launch_closest(dmis, s->trace, q[3], c.hitsMis, nullptr, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+                ++c.closestLaunches;
+                if (int e = c.timer.run(3, stream, [&] {
+                        launch_resolve(c.d, acc, q[cur], q[3], (const int *)s->occluded.p, c.hitsMis, stream, 0, nullptr);
+                        if (st.foldLd != 0.f) launch_direct_fold(c.directLd, dl->strategy == 1 ? c.ps.L : c.directAll, st.foldLd, c.rp.capacity, stream);
+                        if (st.foldAll) launch_direct_fold(c.directAll, c.ps.L, 1.f, c.rp.capacity, stream);
+                    })) return e;
+                ++c.resolveLaunches;
+            }
+            HIP_TRY(hipMemcpyAsync((int *)c.countLog.p + 4 * QSTRIDE * si, c.counts, 4 * QSTRIDE * sizeof(int), hipMemcpyDeviceToDevice, stream));
+        }
+        // this level's queue sizes: the rays the reference's statistics count, and whether a ray was re-spawned
+        HIP_TRY(hipMemcpyAsync(c.hostCounts.data(), c.countLog.p, sizeof(int) * 4 * QSTRIDE * nSteps, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t nMain = queueTotal(c.hostCounts.data(), cur), nNext = queueTotal(c.hostCounts.data(), nxt);
+        c.closestRays += nMain; c.shadeItems += nMain * nSteps;
+        if (level == 0) c.cameraRays += nMain;
+        for (size_t si = 0; si < nSteps; ++si) {
+            if (steps[si].ds.light == -1) continue;
+            const int *blk = c.hostCounts.data() + 4 * QSTRIDE * si;
+            const uint64_t nShadow = queueTotal(blk, 2), nMis = queueTotal(blk, 3);
+            c.shadowRays += nShadow; c.closestRays += nMis; c.misRays += nMis;
+        }
+        if (nNext == 0) break;
+        if (int e = c.timer.run(0, stream, [&] { launch_closest(c.d, s->trace, q[nxt], c.hits, nullptr, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
+        ++c.closestLaunches;
+        cur = nxt;
+    }
+    return c.timer.run(5, stream, film);
+}
+static int tracePaths(FrameCtx &c, const std::function<void()> &generate, const std::function<void()> &film) { if (c.direct) return stepsDirect(c, generate, film); return c.vol ? bouncesVolpath(c, generate, film) : bouncesPath(c, generate, film); }
 
 // The PixelSamplers (stratified, 02sequence, maxmindist) fall back to their tile's RNG stream only for draws beyond their
 // "dimensions" (sampler.cpp:108-134).  PathIntegrator::Li draws at most 1 + 2 maxdepth one-dimensional numbers (time; light choice and
@@ -783,6 +863,10 @@ static int setUpFrame(FrameCtx &c, int capacity) {
     if (s->matLobes.p && s->matHead.p) { c.rp.matPre.lobes = (float4 *)s->matLobes.p; c.rp.matPre.head = (float4 *)s->matHead.p; c.rp.matPre.stride = s->matStride; }
     c.blk.resize(4 * QSTRIDE); c.vblk.resize(2 * QSTRIDE);
     c.lim = pgBounceLimits(c.rd->max_depth, s->hasNullMaterial);
+    if (c.direct) {
+        if (s->directAcc.bytes < 2 * sizeof(float4) * (size_t)capacity) HIP_TRY(s->directAcc.alloc(2 * sizeof(float4) * (size_t)capacity));
+        c.directLd = (float4 *)s->directAcc.p; c.directAll = c.directLd + capacity;
+    }
     if (c.rd->camera_type == 3) {  // the realistic camera: the lens block, zeroed statistics and room for the slots' weights, for this frame only
         const bool diffs = s->d.hasTextured != 0;  // (the camera ray's differentials are read at the first textured hit alone)
         const size_t weightBytes = ((size_t)capacity * sizeof(float) + 255) & ~(size_t)255;
@@ -921,14 +1005,17 @@ static int accountFrame(FrameCtx &c, hipEvent_t evStart, hipEvent_t evStop) {
 // One frame: check, reserve, set up, drive, read back, account.  The description is checked on the host (pg_check_render_desc,
 // pg_render_check.h) before anything is allocated or released.
 static int renderFrame(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays, int32_t *nStrays, int mem,
-                       void *streamPtr) {
+                       void *streamPtr, const PgDirectLightingDesc *dl = nullptr) {
     std::string err;
-    const RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
+    RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
+    facts.nLights = s->d.nLights; facts.maySpecularLobes = s->maySpecularLobes;
     if (int st = pg_check_render_desc(rd, facts, err)) return setError(st, "%s", err.c_str());
-    const bool tsBatched = reserveSampleArrays(s, rd);
+    if (dl) if (int st = pg_check_direct_desc(rd, dl, facts, err)) return setError(st, "%s", err.c_str());
+    // (a DirectLightingIntegrator frame under a PixelSampler draws from its tiles' streams, one camera ray per tile at a time: no arrays ahead)
+    const bool tsBatched = !dl && reserveSampleArrays(s, rd);
     HIP_TRY(hipSetDevice(s->device));
     FrameCtx c;
-    c.s = s; c.rd = rd; c.stream = (hipStream_t)streamPtr; c.vol = rd->integrator == 1;
+    c.s = s; c.rd = rd; c.stream = (hipStream_t)streamPtr; c.vol = rd->integrator == 1; c.direct = dl;
     c.tileSerial = rd->sampler >= PG_SAMPLER_RANDOM && !tsBatched;
     const int nLocalTiles = pgTileCount(rd);
     c.rp.rd = *rd;
@@ -972,6 +1059,16 @@ int pg_render(PgScene *s, const PgRenderDesc *rd, PgFilmPixel *film, PgStraySamp
     PgRenderDesc current;
     rd = pgCurrentRenderDesc(rd, current);
     return withExactFallback(s, [&]() { return renderFrame(s, rd, film, strays, maxStrays, nStrays, mem, streamPtr); });
+}
+
+// DirectLightingIntegrator frames (pg_direct.h): pg_render's frame with the light-sample steps in place of the bounce loops.  Both descriptions are
+// checked on the host before anything is allocated (pg_check_render_desc, then pg_check_direct_desc).
+int pg_render_direct(PgScene *s, const PgRenderDesc *rd, const PgDirectLightingDesc *dl, PgFilmPixel *film, PgStraySample *strays, int32_t maxStrays,
+                     int32_t *nStrays, int mem, void *streamPtr) {
+    if (!s || !rd || !dl || !film || !nStrays || (maxStrays > 0 && !strays)) return setError(PG_ERR_INVALID, "pg_render_direct: null argument");
+    PgRenderDesc current;
+    rd = pgCurrentRenderDesc(rd, current);
+    return withExactFallback(s, [&]() { return renderFrame(s, rd, film, strays, maxStrays, nStrays, mem, streamPtr, dl); });
 }
 
 // ---- the film gather of pg_render_sharded over RCCL (ncclGather, rccl.h:745) ---------------------------------------

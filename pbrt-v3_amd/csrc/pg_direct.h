@@ -1,0 +1,254 @@
+// pg_direct.h -- the DirectLightingIntegrator's kernels (integrators/directlighting.cpp:62-95 without its specular bounces, which pg_render_direct
+// refuses).  Included at the end of pg_kernels.hip: everything here is built from that file's pieces -- the interaction, the BxDF lists and the
+// material evaluators, the light sampling, the queue appends -- and k_resolve itself finishes every EstimateDirect.
+//
+// A camera ray's closest hit stays in its main queue while the frame walks the (light, sample) steps: every step is ONE launch of k_direct over the
+// queue, which rebuilds the hit's interaction and BSDF, draws the step's uLight / uScattering, and leaves a shadow ray, a BSDF-sampled ray and the
+// pending terms at the entry's queue position exactly as k_shade does for the path integrator; the two rays are traced, and k_resolve adds the
+// step's EstimateDirect to a per-slot accumulator.  k_direct_fold then applies the reference's divisions in the reference's order:
+//   UniformSampleAllLights (integrator.cpp:54-83):  Ld = 0; Ld += EstimateDirect (k = 0, 1, ...);  Lall += Ld / nSamples;  ...  L = Le + Lall
+//   UniformSampleOneLight  (integrator.cpp:85-106):  L = Le + EstimateDirect / lightPdf,  lightPdf = Float(1) / nLights
+// Nothing of the path integrators' state in queue order is used: L, the film position and the sampler's state live by slot.
+#ifndef PG_DIRECT_H
+#define PG_DIRECT_H
+
+template <int MODE>
+__global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderParams rp, PathState st, RayQueue qin, const float4 *__restrict__ hits, RayQueue qnext,
+                                                            RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, DirectStep ds) {
+    constexpr bool TEX = MODE == 2;
+    const int i = queue_item<PG_SHADE_BLOCK>(qin);
+    const bool valid = i >= 0;
+    bool pushNext = false, pushShadow = false, pushMis = false;
+    float4 nextO = make_float4(0, 0, 0, 0), nextD = nextO, shadowO = nextO, shadowD = nextO, misO = nextO, misD = nextO;
+    int slot = 0, lightNum = -1;
+    unsigned int nLightTests = 0;
+    float4 pdLight = make_float4(0, 0, 0, 1), pdMis = make_float4(0, 0, 0, 0);
+    float misWeight = 0;
+    if (valid) {
+        const float4 d4 = qin.d[i], h4 = hits[i];
+        slot = __float_as_int(d4.w);
+        const V3 rayD = mk(d4.x, d4.y, d4.z);
+        const int prim = __float_as_int(h4.x);
+        const PgRenderDesc &rd = rp.rd;
+        const float4 L4 = st.L[slot];
+        const float filmY = st.beta[slot].w;
+        const int4 meta = st.meta[slot];
+        const uint64_t index = (uint64_t)(uint32_t)meta.x | ((uint64_t)(uint32_t)meta.y << 32);
+        const bool tileSerial = rd.sampler >= PG_SAMPLER_RANDOM;  // (one camera ray per tile in flight, slot = the tile: its stream is drawn in the reference's order)
+        const bool found = prim >= 0;
+        if (!found) {
+            if (ds.first) {  // directlighting.cpp:70-73: every light's Le(ray), in light order (all but the infinite lights' are zero)
+                Spec L = sp(0);
+                for (int li = 0; li < sc.nLights; ++li)
+                    if (sc.lights[li].type == PG_LIGHT_INFINITE) L = L + env_le(sc, sc.lights[li], rayD);
+                st.L[slot] = make_float4(L.r, L.g, L.b, L4.w);
+            }
+        } else {
+            const Tri tri = load_tri(sc, prim);
+            const PgMaterial mtl = sc.materials[tri.material];
+            const bool surface = mtl.type != PG_MAT_NONE;
+            if (surface ? (ds.first || ds.light != -1) : ds.first != 0) {
+                // ---- the SurfaceInteraction, as k_shade builds it
+                Isect is;
+                float sphU = 0, sphV = 0;
+                V3 sphDpdu = mk(0, 0, 0), sphDpdv = mk(0, 0, 0);
+                const bool onSphere = (tri.flags & PG_PRIM_SPHERE) != 0;
+                int inst = sc.hitInst ? sc.hitInst[i] : -1, inst2 = -1;
+                if constexpr (TEX) nest_decode(sc, inst, inst2);
+                V3 shapeRayD = rayD;
+                if (inst >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst, i), rayD);
+                if (TEX && inst2 >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst2, i, true), shapeRayD);
+                if (onSphere) {
+                    const float4 o4 = qin.o[i];
+                    V3 shapeRayO = mk(o4.x, o4.y, o4.z);
+                    if (inst >= 0) { float dt; instance_ray(inst_w2i(sc, inst, i), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
+                    if (TEX && inst2 >= 0) { float dt; instance_ray(inst_w2i(sc, inst2, i, true), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
+                    const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
+                    is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
+                    is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
+                    if (TEX) { sphU = sh.u; sphV = sh.v; sphDpdu = sh.dpdu; sphDpdv = sh.dpdv; }
+                }
+                if (surface && ds.first) {  // directlighting.cpp:81: L += isect.Le(wo) -- L is zero before it
+                    Spec Le = sp(0);
+                    if (tri.light >= 0) {
+                        const PgLight &l = sc.lights[tri.light];
+                        const V3 nrm = onSphere ? is.n : hit_normal(sc, prim, tri, h4.y, h4.z, h4.w);
+                        if (l.two_sided || dot(nrm, -rayD) > 0) Le = sp3(l.L[0], l.L[1], l.L[2]);
+                    }
+                    st.L[slot] = make_float4(Le.r, Le.g, Le.b, L4.w);
+                }
+                if (!onSphere) is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shapeRayD);
+                if (TEX && inst2 >= 0 && !inst_identity(sc, inst2, i, true)) isect_to_world(inst_i2w(sc, inst2, i, true), inst_w2i(sc, inst2, i, true), is);
+                if (inst >= 0 && !inst_identity(sc, inst, i)) isect_to_world(inst_i2w(sc, inst, i), inst_w2i(sc, inst, i), is);
+                if (!surface) {  // directlighting.cpp:77-78: no BSDF -- Li(isect.SpawnRay(ray.d), ..., depth): the same depth, a ray without differentials
+                    V3 o;
+                    spawn_ray(is, rayD, o);
+                    nextO = make_float4(o.x, o.y, o.z, PG_INF);
+                    nextD = make_float4(rayD.x, rayD.y, rayD.z, __int_as_float(slot));
+                    pushNext = true;
+                    st.meta[slot] = make_int4(meta.x, meta.y, meta.z, meta.w & ~PG_META_HASDIFF);
+                } else if (ds.light != -1) {
+                    // ---- the BSDF: a material's BxDF list, or (MODE 2) ComputeScatteringFunctions with textures
+                    LobeBsdfT<PgBxDF> lb;
+                    PgBxDF lobeStore[TEX ? PG_MAX_BXDFS : 1];
+                    if constexpr (TEX) {
+                        TexHit th;
+                        tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst, inst2, onSphere, sphU, sphV, sphDpdu, sphDpdv, is, meta, L4.w, filmY, tileSerial, false,
+                                      index, th, st.L);
+                        material_bump(sc, tri.material, th, is);
+                        lb.ns = is.ns; lb.ng = is.n;
+                        lb.ss = normalize(is.sdpdu);
+                        lb.ts = cross(lb.ns, lb.ss);
+                        int nl = 0;
+                        float etaL = 1;
+                        MatEval<2>::run(*sc.self, tri.material, th, LobeOutRaw{lobeStore}, nl, etaL, PG_MAX_BXDFS);
+                        lbsdf_bind(lb, lobeStore, nl, etaL);
+                    } else {
+                        lb.ns = is.ns; lb.ng = is.n;
+                        lb.ss = normalize(is.sdpdu);
+                        lb.ts = cross(lb.ns, lb.ss);
+                        lbsdf_bind(lb, sc.bxdfs + mtl.first_bxdf, mtl.n_bxdfs, mtl.bsdf_eta);
+                    }
+                    // ---- the step's numbers: Get1D / Get2D of a PixelSampler's stream, or a GlobalSampler's (sample index, dimension)
+                    float uSel = 0, uL0, uL1, uS0, uS1;
+                    if (tileSerial) {
+                        if (ds.light == -2) uSel = ts_get1d(sc, slot);
+                        ts_get2d(sc, rd.sampler, slot, uL0, uL1);
+                        ts_get2d(sc, rd.sampler, slot, uS0, uS1);
+                    } else {
+                        uint64_t idx = index;
+                        if (ds.arrayN > 0) {
+                            int px, py, sn;
+                            slot_to_pixel(rp, slot, px, py, sn);
+                            idx = sampler_index(sc, rd, px, py, (uint64_t)sn * (uint64_t)ds.arrayN + (uint64_t)ds.arrayK);
+                        }
+                        if (ds.light == -2) uSel = halton_sample(sc, rd, idx, ds.dimBase - 1);
+                        uL0 = halton_sample(sc, rd, idx, ds.dimBase); uL1 = halton_sample(sc, rd, idx, ds.dimBase + 1);
+                        uS0 = halton_sample(sc, rd, idx, ds.dimBase + 2); uS1 = halton_sample(sc, rd, idx, ds.dimBase + 3);
+                    }
+                    lightNum = ds.light;
+                    if (ds.light == -2) { lightNum = (int)(uSel * sc.nLights); if (lightNum > sc.nLights - 1) lightNum = sc.nLights - 1; }  // integrator.cpp:95
+                    // ---- EstimateDirect (integrator.cpp:108-215) with bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR, up to the two rays
+                    const int nonSpecular = PG_BSDF_ALL & ~PG_BSDF_SPECULAR;
+                    const LightHot lh = load_light_hot(sc, lightNum);
+                    const PgLight &light = sc.lights[lightNum];
+                    V3 wi = mk(0, 0, 0);
+                    float lightPdf = 0, scatteringPdf = 0;
+                    LightSample ls;
+                    const Spec Li = light_sample_li_hot<true>(sc, lh, light, is.p, is.pError, is.n, uL0, uL1, wi, lightPdf, ls);
+                    if (lightPdf > 0 && !is_black(Li)) {
+                        const Spec f = lbsdf_f(lb, is.wo, wi, nonSpecular) * absdot(wi, lb.ns);
+                        scatteringPdf = lbsdf_pdf(lb, is.wo, wi, nonSpecular);
+                        if (!is_black(f)) {
+                            const V3 origin = offset_ray_origin(is.p, is.pError, is.n, ls.p - is.p);  // VisibilityTester: p0.SpawnRayTo(p1), interaction.h:73-78
+                            const V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
+                            const V3 shD = target - origin;
+                            shadowO = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
+                            shadowD = make_float4(shD.x, shD.y, shD.z, __int_as_float(slot));
+                            pushShadow = true;
+                            const Spec c = PG_LIGHT_IS_DELTA(lh.type) ? (f * Li) / lightPdf : ((f * Li) * power_heuristic(1, lightPdf, 1, scatteringPdf)) / lightPdf;
+                            pdLight = make_float4(c.r, c.g, c.b, 1);
+                        }
+                    }
+                    if (lh.type == PG_LIGHT_AREA || lh.type == PG_LIGHT_INFINITE) {  // integrator.cpp:164: if (!IsDeltaLight(light.flags))
+                        V3 wi2 = wi;
+                        float sPdf2 = 0;
+                        int sampledType;
+                        Spec f2 = lbsdf_sample_f(lb, is.wo, wi2, uS0, uS1, sPdf2, nonSpecular, sampledType);
+                        f2 = f2 * absdot(wi2, lb.ns);
+                        if (!is_black(f2) && sPdf2 > 0) {
+                            // light.Pdf_Li: an infinite light's from its distribution; an area light's Shape::Pdf by intersecting the light's own shape
+                            float lightPdf2 = 0;
+                            V3 misRo;
+                            spawn_ray(is, wi2, misRo);
+                            if (lh.type == PG_LIGHT_INFINITE) lightPdf2 = env_pdf_li(sc, light, wi2);
+                            else if (lh.tri.flags & PG_PRIM_SPHERE) {  // Sphere::Pdf, sphere.cpp:292-305
+                                const PgSphere &lsph = sc.spheres[__float_as_int(lh.tri.p0.x)];
+                                const bool inside = lsph.shape != PG_SHAPE_SPHERE || sphere_ref_inside(lsph, is.p, is.pError, is.n);
+                                float t;
+                                if (!inside) lightPdf2 = sphere_cone_pdf(lsph, is.p);
+                                else if (sphere_test(lsph, misRo, wi2, PG_INF, t)) {  // Shape::Pdf, shape.cpp:72-87
+                                    const SphereHit sh = sphere_interaction(lsph, misRo, wi2, t);
+                                    float pdf = lensq(is.p - sh.p) / (absdot(sh.n, -wi2) * lh.area);
+                                    if (isinf(pdf)) pdf = 0.f;
+                                    lightPdf2 = pdf;
+                                }
+                            } else {
+                                float t, lb0, lb1, lb2;
+                                ++nLightTests;
+                                if (tri_test(lh.tri.p0, lh.tri.p1, lh.tri.p2, misRo, wi2, PG_INF, t, lb0, lb1, lb2) && !(lh.tri.flags & PG_TRI_BOGUS)) {
+                                    const V3 lp = lh.tri.p0 * lb0 + lh.tri.p1 * lb1 + lh.tri.p2 * lb2;
+                                    const V3 ln = normalize(cross(lh.tri.p0 - lh.tri.p2, lh.tri.p1 - lh.tri.p2));
+                                    float pdf = lensq(is.p - lp) / (absdot(ln, -wi2) * lh.area);
+                                    if (isinf(pdf)) pdf = 0.f;
+                                    lightPdf2 = pdf;
+                                }
+                            }
+                            if (lightPdf2 != 0) {
+                                misO = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
+                                misD = make_float4(wi2.x, wi2.y, wi2.z, __int_as_float(slot));
+                                pushMis = true;
+                                pdMis = make_float4(f2.r, f2.g, f2.b, sPdf2);
+                                misWeight = power_heuristic(1, sPdf2, 1, lightPdf2);
+                            }
+                        }
+                    }
+                }
+                // directlighting.cpp:91-95: while depth + 1 < maxdepth, SpecularReflect and SpecularTransmit each hand BSDF::Sample_f a Get2D
+                // (integrator.cpp:217-295) whether or not the BSDF has a specular lobe.  None has here (pg_check_direct_desc), so both return black --
+                // but a PixelSampler's stream and dimension counters have moved on by two pairs (a GlobalSampler's dimensions are nobody else's)
+                if (surface && ds.first && tileSerial && rd.max_depth >= 2) {
+                    float a, b;
+                    ts_get2d(sc, rd.sampler, slot, a, b);
+                    ts_get2d(sc, rd.sampler, slot, a, b);
+                }
+            }
+        }
+    }
+    const RayQueue outQ[3] = {qnext, qshadow, qmis};
+    const bool outPred[3] = {pushNext, pushShadow, pushMis};
+    int outPos[3];
+    block_push<3, false, PG_SHADE_BLOCK>(outQ, outPred, outPos);
+    if (pushNext) { qnext.o[outPos[0]] = nextO; qnext.d[outPos[0]] = nextD; }
+    if (pushShadow) { qshadow.o[outPos[1]] = shadowO; qshadow.d[outPos[1]] = shadowD; }
+    if (pushMis) { qmis.o[outPos[2]] = misO; qmis.d[outPos[2]] = misD; }
+    if (sc.rayTimes) {  // the spawned rays carry the interaction's time = the ray's (interaction.h:77-95)
+        const float t = valid ? PG_QUEUE_TIMES(sc, qin)[i] : 0.f;
+        if (pushNext) PG_QUEUE_TIMES(sc, qnext)[outPos[0]] = t;
+        if (pushShadow) PG_QUEUE_TIMES(sc, qshadow)[outPos[1]] = t;
+        if (pushMis) PG_QUEUE_TIMES(sc, qmis)[outPos[2]] = t;
+    }
+    if (valid) {  // k_resolve's pending terms, by queue position; its L += beta * (Ld / pdLight.w) is Ld itself here, added to the slot's accumulator
+        st.pdInfo[i] = make_int4(outPos[1], outPos[2], lightNum, ~slot);
+        if (pushShadow || pushMis) {
+            st.pdLight[i] = pdLight;
+            st.pdMis[i] = pdMis;
+            st.pdBeta[i] = make_float4(1, 1, 1, misWeight);
+        }
+    }
+    const unsigned long long nl = wave_sum(nLightTests);
+    if (lane_id() == 0 && nl) atomicAdd(lightTriTests + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE, nl);
+}
+void launch_direct(const DScene &sc, const RenderParams &rp, PathState st, RayQueue qin, const float4 *hits, RayQueue qnext, RayQueue qshadow, RayQueue qmis,
+                   unsigned long long *lightTriTests, const DirectStep &ds, hipStream_t s) {
+    const int nblk = PG_REGIONS * (qin.regionCap / PG_SHADE_BLOCK);
+    if (nblk == 0) return;
+    if (sc.hasTextured || sc.hasNest) hipLaunchKernelGGL((k_direct<2>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, ds);
+    else hipLaunchKernelGGL((k_direct<1>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, ds);
+}
+
+// dst[slot].rgb += src[slot].rgb / divisor, then src[slot].rgb = 0 (the .w fields stay): `L += Ld / nSamples` (integrator.cpp:80),
+// `EstimateDirect(...) / lightPdf` (integrator.cpp:104) and `L += UniformSample...Lights(...)` (directlighting.cpp:84-89, divisor 1).  A division, as the
+// reference's Spectrum::operator/(Float) is.
+__global__ __launch_bounds__(PG_BLOCK) void k_direct_fold(float4 *__restrict__ src, float4 *__restrict__ dst, float divisor, int n) {
+    const int slot = blockIdx.x * PG_BLOCK + threadIdx.x;
+    if (slot >= n) return;
+    const float4 a = src[slot], d = dst[slot];
+    dst[slot] = make_float4(d.x + a.x / divisor, d.y + a.y / divisor, d.z + a.z / divisor, d.w);
+    src[slot] = make_float4(0, 0, 0, a.w);
+}
+void launch_direct_fold(float4 *src, float4 *dst, float divisor, int n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_direct_fold, dim3((n + PG_BLOCK - 1) / PG_BLOCK), dim3(PG_BLOCK), 0, s, src, dst, divisor, n);
+}
+#endif

@@ -456,5 +456,17 @@ void launch_film_general(const RenderParams &rp, PathState st, PgFilmPixel *film
 void launch_light_tables(const DScene &sc, float *table, int nDistributions, hipStream_t s);
 // the distributions of voxels requests[0 .. n) into pool slots firstSlot ..; also publishes voxelSlot[]
 void launch_light_tables_sparse(const DScene &sc, float *pool, const int *requests, int n, int firstSlot, hipStream_t s);
+// ---- the DirectLightingIntegrator's launches (pg_direct.h)
+// One launch of k_direct
+struct DirectStep {
+    int first;    // the queue's first launch: Le at the hit, the lights' Le for an escaped ray, and the re-spawn through a surface without a material
+    int light;    // the light this step samples; -1: none (a scene without lights); -2: UniformSampleOneLight picks it with Get1D
+    int dimBase;  // GlobalSamplers: the dimension of uLight.x; uLight.y and uScattering follow (the light choice of -2 precedes it)
+    int arrayN;   // > 0: the numbers are element arrayK of a sample array of arrayN per pixel sample: sample index GetIndexForSample(s * arrayN + arrayK)
+    int arrayK;   //      (sampler.cpp:136-166); 0: the camera sample's own index
+};
+void launch_direct(const DScene &sc, const RenderParams &rp, PathState st, RayQueue qin, const float4 *hits, RayQueue qnext, RayQueue qshadow, RayQueue qmis,
+                   unsigned long long *lightTriTests, const DirectStep &ds, hipStream_t s);
+void launch_direct_fold(float4 *src, float4 *dst, float divisor, int n, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

@@ -8,6 +8,7 @@
 //   k_resolve    EstimateDirect's visibility / MIS terms once rays are back (integrator.cpp:143-212)
 //   k_film       SamplerIntegrator::Render's scrub + FilmTile::AddSample    (integrator.cpp:294-320, film.h:121-161)
 //   k_light_tables  SpatialLightDistribution::ComputeDistribution per voxel (lightdistrib.cpp:232-300)
+//   k_direct     DirectLightingIntegrator::Li, one (light, sample) step per launch (directlighting.cpp:62-95; pg_direct.h, included at the end)
 //
 // No MFMA: there is no dense contraction on this path; traversal is a
 // latency/bandwidth-bound gather over the node and triangle arrays.
@@ -4201,3 +4202,5 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
     hipLaunchKernelGGL(k_light_tables, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, table, nDistributions);
 }
 
+
+#include "pg_direct.h"  // the kernels of the DirectLightingIntegrator, built from the pieces above

@@ -15,6 +15,9 @@ struct RenderSceneFacts {
     int nMedia = 0;                                               // PgSceneDesc.n_media
     bool hasCmaxmin = false, hasSobol = false, hasPerms = false;  // the scene carries CMaxMinDist / the Sobol' matrices / the Halton permutations
     int nPermDims = 0;                                            // dimensions of the Halton permutation table
+    // pg_check_direct_desc alone:
+    int nLights = 0;                                              // PgSceneDesc.n_lights
+    bool maySpecularLobes = false;                                // pgh_scene_may_add_specular_lobes(the scene's description)
 };
 // the 16x16 tiles of the full-frame tiling that this description's shard (tile_first, tile_step) owns
 inline int pgTileCount(const PgRenderDesc *rd) {
@@ -89,6 +92,41 @@ inline int pg_check_render_desc(const PgRenderDesc *rd, const RenderSceneFacts &
             if (!(rd->exit_pupil_bounds[i][0] <= rd->exit_pupil_bounds[i][2] && rd->exit_pupil_bounds[i][1] <= rd->exit_pupil_bounds[i][3]))
                 RC_FAIL("pg_render: exit pupil box %d is empty (min > max)", i);
         if (!(rd->film_diagonal > 0) || !std::isfinite(rd->film_diagonal)) RC_FAIL("pg_render: realistic camera on a film of diagonal %g", (double)rd->film_diagonal);
+    }
+    return PG_OK;
+}
+// The DirectLightingIntegrator's description beside a frame's (pg_render_direct): called once pg_check_render_desc has passed `rd`.
+// The reference's own limits on a GlobalSampler's dimensions: halton.h:71-76 (PrimeTableSize, lowdiscrepancy.h:52) and sobol.cpp:47-50
+// (NumSobolDimensions, sobolmatrices.h:46) end its process beyond them.
+const long long PG_HALTON_MAX_DIMS = 1000, PG_SOBOL_MAX_DIMS = 1024;
+inline int pg_check_direct_desc(const PgRenderDesc *rd, const PgDirectLightingDesc *dl, const RenderSceneFacts &sc, std::string &err) {
+    if (dl->strategy != 0 && dl->strategy != 1) RC_FAIL("pg_render_direct: strategy %d (0 = all, 1 = one)", dl->strategy);
+    if (dl->n_lights != sc.nLights) RC_FAIL("pg_render_direct: n_lights %d, the scene has %d lights", dl->n_lights, sc.nLights);
+    if (dl->strategy == 0) {
+        if (dl->n_lights > 0 && !dl->light_samples) RC_FAIL("pg_render_direct: strategy 0 (all) needs light_samples, one count per light");
+        for (int j = 0; j < dl->n_lights; ++j)
+            if (dl->light_samples[j] < 1) RC_FAIL("pg_render_direct: light_samples[%d] = %d (each light takes at least one sample)", j, dl->light_samples[j]);
+    }
+    if (rd->integrator != 0) RC_FAIL("pg_render_direct: integrator %d (the frame's description carries 0 here; max_depth is the integrator's \"maxdepth\")", rd->integrator);
+    // UniformSampleAllLights reads sample ARRAYS (integrator.cpp:61-64).  A GlobalSampler's are closed form per element (sampler.cpp:136-166); a
+    // PixelSampler fills them from its tile's RNG stream in StartPixel (stratified.cpp:62-69, zerotwosequence.cpp:62-68, maxmin.cpp:65-75)
+    if (dl->strategy == 0 && rd->sampler >= PG_SAMPLER_RANDOM)
+        RC_FAIL("pg_render_direct: strategy 0 (all) under sampler %d: the PixelSamplers' sample arrays are not built (render with halton or sobol, or with strategy 1)", rd->sampler);
+    // directlighting.cpp:91-95: SpecularReflect + SpecularTransmit while depth + 1 < maxDepth -- a depth-first tree that is not built
+    if (rd->max_depth >= 2 && sc.maySpecularLobes)
+        RC_FAIL("pg_render_direct: maxdepth %d on a scene whose materials can add specular lobes: directlighting's specular bounces are not built (maxdepth <= 1 renders such a scene)", rd->max_depth);
+    if (rd->sampler == PG_SAMPLER_HALTON || rd->sampler == PG_SAMPLER_SOBOL) {
+        // Dimensions 0 .. 4 are the camera sample's.  Strategy 0 with max_depth >= 1: the constructor requested two arrays per light and depth
+        // (directlighting.cpp:53-60), which occupy 5 .. 5 + 4 n_lights max_depth -- StartPixel computes them all -- and those of depth 0 are read;
+        // otherwise the draws are sequential from 5: lightNum, uLight, uScattering (strategy 1), or uLight, uScattering per light (max_depth 0)
+        const bool arrays = dl->strategy == 0 && rd->max_depth >= 1;
+        const long long reached = arrays ? 5 + 4 * (long long)dl->n_lights * rd->max_depth : (dl->strategy == 1 ? 5 + 5 : 5 + 4 * (long long)dl->n_lights);
+        const long long read = dl->strategy == 1 ? 5 + 5 : 5 + 4 * (long long)dl->n_lights;
+        const long long limit = rd->sampler == PG_SAMPLER_HALTON ? PG_HALTON_MAX_DIMS : PG_SOBOL_MAX_DIMS;
+        if (dl->n_lights > 0 && reached > limit)
+            RC_FAIL("pg_render_direct: the frame reaches sample dimension %lld; the reference's %s ends at %lld (it aborts beyond)", reached, rd->sampler == PG_SAMPLER_HALTON ? "Halton sampler" : "Sobol' sampler", limit);
+        if (dl->n_lights > 0 && rd->sampler == PG_SAMPLER_HALTON && read > sc.nPermDims)
+            RC_FAIL("pg_render_direct: Halton table has %d dimensions; %d lights under strategy %d need %lld", sc.nPermDims, dl->n_lights, dl->strategy, read);
     }
     return PG_OK;
 }

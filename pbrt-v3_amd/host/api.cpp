@@ -82,6 +82,7 @@ struct RenderOptions {
     std::map<std::string, std::shared_ptr<ObjectDefinition>> instances;  // api.cpp:129
     std::shared_ptr<ObjectDefinition> currentInstance;
     std::vector<PgLight> lights;           // prim index filled at flatten time
+    std::vector<int> lightSamples;         // Light::nSamples per light ("samples" / "nsamples" of infinite and area lights, 1 otherwise): the directlighting integrator's
     std::vector<size_t> lightPrimSerial;   // serial number of the emitting primitive
     std::vector<PgMaterial> materials;
     std::vector<PgBxDF> bxdfs;  // the materials' BxDF lists, concatenated
@@ -991,6 +992,7 @@ void pbrtLightSource(const std::string &name, const ParamSet &params) {
     PgLight l;
     memset(&l, 0, sizeof(l));
     l.prim = -1;
+    int nSamples = 1;  // Light::nSamples (light.h:87): only the infinite light's constructor is handed another
     RGB sc = params.FindOneSpectrum("scale", RGB{{1.f, 1.f, 1.f}});
     if (name == "point") {
         RGB I = params.FindOneSpectrum("I", RGB{{1.f, 1.f, 1.f}});
@@ -1074,7 +1076,8 @@ void pbrtLightSource(const std::string &name, const ParamSet &params) {
         }
     } else if (name == "infinite" || name == "exinfinite") {  // CreateInfiniteLight, infinite.cpp:176-188; ctor :44-85
         RGB L = params.FindOneSpectrum("L", RGB{{1.f, 1.f, 1.f}});
-        params.FindOneInt("samples", params.FindOneInt("nsamples", 1));
+        nSamples = params.FindOneInt("samples", params.FindOneInt("nsamples", 1));
+        if (PbrtOptions.quickRender) nSamples = std::max(1, nSamples / 4);  // infinite.cpp:183
         std::string texmap = params.FindOneString("mapname", "");
         if (!texmap.empty()) texmap = AbsolutePath(ResolveFilename(texmap));
         l.type = PG_LIGHT_INFINITE;
@@ -1144,6 +1147,7 @@ void pbrtLightSource(const std::string &name, const ParamSet &params) {
     }
     params.ReportUnused();
     renderOptions->lights.push_back(l);
+    renderOptions->lightSamples.push_back(nSamples);
 }
 void pbrtAreaLightSource(const std::string &name, const ParamSet &params) {
     VERIFY_WORLD("AreaLightSource");
@@ -1301,7 +1305,7 @@ void pbrtShape(const std::string &name, const ParamSet &params) {  // api.cpp:13
     if (!sphere && (!mesh || mesh->nTriangles == 0)) return;
     int mtl = GetMaterialForShape(params);
     params.ReportUnused();
-    int firstLight = -1;
+    int firstLight = -1, areaSamples = 1;
     PgLight lightProto;
     memset(&lightProto, 0, sizeof(lightProto));
     if (animated) {
@@ -1314,7 +1318,8 @@ void pbrtShape(const std::string &name, const ParamSet &params) {  // api.cpp:13
             const ParamSet &lp = graphicsState.areaLightParams;
             RGB L = lp.FindOneSpectrum("L", RGB{{1.f, 1.f, 1.f}});
             RGB sc = lp.FindOneSpectrum("scale", RGB{{1.f, 1.f, 1.f}});
-            lp.FindOneInt("samples", lp.FindOneInt("nsamples", 1));
+            areaSamples = lp.FindOneInt("samples", lp.FindOneInt("nsamples", 1));
+            if (PbrtOptions.quickRender) areaSamples = std::max(1, areaSamples / 4);  // diffuse.cpp:143
             lightProto.two_sided = lp.FindOneBool("twosided", false) ? 1 : 0;
             for (int i = 0; i < 3; ++i) lightProto.L[i] = L.c[i] * sc.c[i];
             lp.ReportUnused();
@@ -1337,6 +1342,7 @@ void pbrtShape(const std::string &name, const ParamSet &params) {  // api.cpp:13
             l.prim = -1;
             prim.areaLight = (int)renderOptions->lights.size();
             renderOptions->lights.push_back(l);
+            renderOptions->lightSamples.push_back(areaSamples);
         }
         // api.cpp:1405-1418: to the scene, or to the instance definition being collected
         if (moving) moving->prims.push_back(prim);
@@ -1451,17 +1457,46 @@ static GpuPathIntegrator *MakeIntegrator() {
         return nullptr;
     }
     ro.SamplerParams.ReportUnused();
-    if (ro.IntegratorName != "path" && ro.IntegratorName != "volpath") {
-        Error("Integrator \"%s\" is outside this build's closed set (path, volpath).", ro.IntegratorName.c_str());
+    if (ro.IntegratorName != "path" && ro.IntegratorName != "volpath" && ro.IntegratorName != "directlighting") {
+        Error("Integrator \"%s\" is outside this build's closed set (path, volpath, directlighting).", ro.IntegratorName.c_str());
         return nullptr;
     }
-    GpuPathIntegrator *integrator = CreatePathIntegrator(ro.IntegratorParams, sampler, camera);  // volpath.cpp:191-214 reads the same parameters
+    const bool direct = ro.IntegratorName == "directlighting";
+    GpuPathIntegrator *integrator = direct ? CreateDirectLightingIntegrator(ro.IntegratorParams, sampler, camera)
+                                           : CreatePathIntegrator(ro.IntegratorParams, sampler, camera);  // volpath.cpp:191-214 reads the same parameters
     integrator->volumetric = ro.IntegratorName == "volpath";
+    if (direct) {
+        // DirectLightingIntegrator::Preprocess, directlighting.cpp:46-61: nLightSamples[j] = sampler.RoundCount(light j's nSamples) -- the identity but
+        // for the 02sequence and maxmindist samplers, which round up to a power of two (zerotwosequence.h:59, maxmin.h:61)
+        auto roundUpPow2 = [](int v) { v--; v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16; return v + 1; };  // pbrt.h:369-377
+        for (int n : ro.lightSamples)
+            integrator->lightSamples.push_back((sampler->kind == PG_SAMPLER_ZEROTWO || sampler->kind == PG_SAMPLER_MAXMINDIST) ? roundUpPow2(n) : n);
+        // UniformSampleAllLights reads sample arrays, which a PixelSampler fills from its tile's random stream in StartPixel: not built
+        if (integrator->directStrategy == 0 && sampler->kind >= PG_SAMPLER_RANDOM) {
+            Error("Integrator \"directlighting\" with strategy \"all\" under sampler \"%s\": the sample arrays of the random, stratified, 02sequence and maxmindist "
+                  "samplers are outside this build's closed set (use \"halton\" or \"sobol\", or \"string strategy\" \"one\"); the scene will not be rendered.", sn.c_str());
+            ro.refused = true;
+        }
+        // The GlobalSamplers' dimensions (pg_check_direct_desc's count): the camera sample's five; then strategy "all" requested two arrays per light and
+        // depth (directlighting.cpp:53-60), all of which StartPixel computes (sampler.cpp:136-166), or the draws follow one another.  Beyond its
+        // tables the reference ends its process (halton.h:71-76, sobol.cpp:47-50)
+        const long long nl = (long long)ro.lights.size();
+        const long long reached = integrator->directStrategy == 1 ? 10 : 5 + 4 * nl * std::max(1, integrator->maxDepth);
+        const long long limit = sampler->sobol ? 1024 : 1000;
+        if (sampler->kind == 0 && nl > 0 && reached > limit) {
+            Error("Integrator \"directlighting\": %lld lights at \"maxdepth\" %d reach sample dimension %lld, beyond the %lld of the %s sampler (the reference aborts "
+                  "there); the scene will not be rendered.", nl, integrator->maxDepth, reached, limit, sampler->sobol ? "sobol" : "halton");
+            ro.refused = true;
+        }
+    }
     // A PixelSampler (stratified, 02sequence, maxmindist) whose "dimensions" do not cover a whole path (2 + 3 maxdepth two-dimensional
     // draws) falls back to its tile's ONE random stream from the first bounce on (sampler.cpp:108-134): a path's later numbers then depend on how many
     // all earlier paths of the tile drew, and the device can hold one path per tile in flight -- correct, pinned against the reference, and
     // orders of magnitude slower than the same sampler with enough dimensions.  "random" always draws from the stream.  volpath: no bound.
-    if (sampler->kind > PG_SAMPLER_RANDOM && !integrator->volumetric && sampler->nSampledDimensions < 2 + 3 * (long long)integrator->maxDepth)
+    if (direct) {  // (directlighting frames never generate a PixelSampler's arrays ahead: pg_render_direct renders them tile-serially)
+        if (sampler->kind >= PG_SAMPLER_RANDOM)
+            Warning("Sampler \"%s\" under \"directlighting\": tiles render one camera ray at a time on the device (halton / sobol render the frame as one wavefront).", sn.c_str());
+    } else if (sampler->kind > PG_SAMPLER_RANDOM && !integrator->volumetric && sampler->nSampledDimensions < 2 + 3 * (long long)integrator->maxDepth)
         Warning("Sampler \"%s\" with \"dimensions\" %d samples a path of \"maxdepth\" %d from its tile's random stream after the first bounce: tiles render one "
                 "path at a time on the device. Set \"integer dimensions\" [ %lld ] (2 + 3 maxdepth) or more to render the frame as one wavefront.",
                 sn.c_str(), sampler->nSampledDimensions, integrator->maxDepth, 2 + 3 * (long long)integrator->maxDepth);
@@ -1473,8 +1508,8 @@ static GpuPathIntegrator *MakeIntegrator() {
         CreateMediumInterface(&in, &out);
         integrator->cameraMedium = out;
     }
-    if (ro.haveScatteringMedia && ro.IntegratorName != "volpath")
-        Warning("Scene has scattering media but \"path\" integrator doesn't support volume scattering. Consider using \"volpath\".");
+    if (ro.haveScatteringMedia && ro.IntegratorName != "volpath")  // api.cpp:1699-1705
+        Warning("Scene has scattering media but \"%s\" integrator doesn't support volume scattering. Consider using \"volpath\".", ro.IntegratorName.c_str());
     ro.IntegratorParams.ReportUnused();
     if (ro.lights.empty())
         Warning("No light sources defined in scene; rendering a black image.");
@@ -1534,6 +1569,20 @@ void pbrtWorldEnd() {  // api.cpp:1590-1644
     if (MotionBoundsFailures() != motionFailuresBefore) {  // (the reference's CHECK_LE(*nZeros, 8) ends its process here, transform.cpp:385)
         Error("A rotating motion's derivative has more than 8 zeros in the shutter interval (AnimatedTransform::MotionBounds): its box cannot be the reference's");
         renderOptions->refused = true;
+    }
+    if (integrator && integrator->directLighting && integrator->maxDepth >= 2 && scene) {
+        // directlighting.cpp:91-95: SpecularReflect + SpecularTransmit while depth + 1 < maxdepth.  The same rule as pg_check_direct_desc's
+        PgSceneDesc sd;
+        memset(&sd, 0, sizeof(sd));
+        sd.n_bxdfs = (int)scene->bxdfs.size(); sd.bxdfs = scene->bxdfs.data();
+        sd.n_textured = (int)scene->textured.size(); sd.textured = scene->textured.data();
+        sd.n_bssrdfs = (int)scene->bssrdfs.size();
+        if (pgh_scene_may_add_specular_lobes(&sd)) {
+            Error("Integrator \"directlighting\" with \"maxdepth\" %d on a scene whose materials can add specular lobes (mirror, glass, uber, subsurface): its specular "
+                  "bounces (SpecularReflect / SpecularTransmit) are outside this build's closed set (\"integer maxdepth\" [ 1 ] renders the scene without them); the "
+                  "scene will not be rendered.", integrator->maxDepth);
+            renderOptions->refused = true;
+        }
     }
     if (timing) fprintf(stderr, "pbrt host: MakeScene (BVH build) %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild).count());
     if (renderOptions->refused) {

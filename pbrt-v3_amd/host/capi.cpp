@@ -8,6 +8,7 @@ using namespace pbrt;
 struct PbrtHostScene {
     std::unique_ptr<LoadedScene> loaded;
     FlatScene flat;
+    PgDirectLightingDesc direct;
 };
 
 static PbrtHostScene *finishLoad() {
@@ -15,6 +16,7 @@ static PbrtHostScene *finishLoad() {
     PbrtHostScene *s = new PbrtHostScene;
     s->loaded = std::move(lastLoadedScene);
     s->loaded->integrator->Flatten(*s->loaded->scene, &s->flat);
+    s->loaded->integrator->FillDirectDesc(&s->direct);
     return s;
 }
 static bool g_deviceBVH = false;
@@ -50,6 +52,7 @@ PbrtHostScene *pbrt_host_load_string(const char *text, int quick, const float *c
 void pbrt_host_free(PbrtHostScene *s) { delete s; }
 const PgSceneDesc *pbrt_host_scene_desc(PbrtHostScene *s) { return &s->flat.desc; }
 void pbrt_host_render_desc(PbrtHostScene *s, PgRenderDesc *out) { s->loaded->integrator->FillRenderDesc(out); }
+const PgDirectLightingDesc *pbrt_host_direct_desc(PbrtHostScene *s) { return s->loaded->integrator->directLighting ? &s->direct : nullptr; }
 void pbrt_host_film_size(PbrtHostScene *s, int *w, int *h) {
     const Film &f = *s->loaded->integrator->camera->film;
     *w = f.croppedPixelBounds[2] - f.croppedPixelBounds[0];

@@ -208,11 +208,9 @@ GpuPathIntegrator::GpuPathIntegrator(int maxDepth, std::shared_ptr<PerspectiveCa
     : camera(camera), sampler(sampler), maxDepth(maxDepth), rrThreshold(rrThreshold), lightSampleStrategy(lightSampleStrategy) {
     for (int i = 0; i < 4; ++i) pixelBounds[i] = pb[i];
 }
-GpuPathIntegrator *CreatePathIntegrator(const ParamSet &params, std::shared_ptr<HaltonSampler> sampler,
-                                        std::shared_ptr<PerspectiveCamera> camera) {
-    int maxDepth = params.FindOneInt("maxdepth", 5);
-    int pixelBounds[4];
-    camera->film->GetSampleBounds(pixelBounds);
+// "pixelbounds" as the integrators' factories read it (path.cpp:193-207, directlighting.cpp:114-127)
+static void ReadPixelBounds(const ParamSet &params, const PerspectiveCamera &camera, int pixelBounds[4]) {
+    camera.film->GetSampleBounds(pixelBounds);
     const std::vector<int> *pb = params.FindInt("pixelbounds");
     if (pb) {
         if (pb->size() != 4) Error("Expected four values for \"pixelbounds\" parameter. Got %d.", (int)pb->size());
@@ -225,9 +223,31 @@ GpuPathIntegrator *CreatePathIntegrator(const ParamSet &params, std::shared_ptr<
             if ((pixelBounds[2] - pixelBounds[0]) * (pixelBounds[3] - pixelBounds[1]) == 0) Error("Degenerate \"pixelbounds\" specified.");
         }
     }
+}
+GpuPathIntegrator *CreatePathIntegrator(const ParamSet &params, std::shared_ptr<HaltonSampler> sampler,
+                                        std::shared_ptr<PerspectiveCamera> camera) {
+    int maxDepth = params.FindOneInt("maxdepth", 5);
+    int pixelBounds[4];
+    ReadPixelBounds(params, *camera, pixelBounds);
     Float rrThreshold = params.FindOneFloat("rrthreshold", 1.);
     std::string lightStrategy = params.FindOneString("lightsamplestrategy", "spatial");
     return new GpuPathIntegrator(maxDepth, camera, sampler, pixelBounds, rrThreshold, lightStrategy);
+}
+GpuPathIntegrator *CreateDirectLightingIntegrator(const ParamSet &params, std::shared_ptr<HaltonSampler> sampler,
+                                                  std::shared_ptr<PerspectiveCamera> camera) {
+    int maxDepth = params.FindOneInt("maxdepth", 5);
+    int strategy = 0;
+    std::string st = params.FindOneString("strategy", "all");
+    if (st == "one") strategy = 1;
+    else if (st != "all") Warning("Strategy \"%s\" for direct lighting unknown. Using \"all\".", st.c_str());
+    int pixelBounds[4];
+    ReadPixelBounds(params, *camera, pixelBounds);
+    // (rrThreshold and the light distribution are the path integrators': the description's rr_threshold is ignored by pg_render_direct, and
+    // UniformSampleOneLight is called without a distribution, integrator.cpp:91-98; "uniform" keeps Flatten from reporting an unknown name)
+    GpuPathIntegrator *integrator = new GpuPathIntegrator(maxDepth, camera, sampler, pixelBounds, 1.f, "uniform");
+    integrator->directLighting = true;
+    integrator->directStrategy = strategy;
+    return integrator;
 }
 
 void GpuPathIntegrator::Flatten(const Scene &scene, FlatScene *flat) const {
@@ -382,6 +402,8 @@ void GpuPathIntegrator::Flatten(const Scene &scene, FlatScene *flat) const {
     int nDims = (int)std::min(1000LL, std::max(5LL, 5 + 8 * ((long long)maxDepth + 2)));  // (64-bit: "maxdepth" is the file's to choose)
     if (volumetric) nDims = 1000;  // volpath.cpp:77-78,119-123: medium sampling consumes dimensions on uncounted bounces too
     if (!scene.bssrdfs.empty()) nDims = 1000;  // path.cpp:152-174: a subsurface vertex draws 10 more values (Sample_S, lights at pi, the exit direction)
+    // directlighting: two sample arrays per light (those of depth 0 are read, pg_check_direct_desc), or -- strategy "one", maxdepth 0 -- as many draws in sequence
+    if (directLighting) nDims = (int)std::min(1000LL, std::max((long long)nDims, 5 + 4 * std::max(1LL, (long long)flat->lights.size())));
     ComputeRadicalInversePermutations(nDims, &flat->perms, &flat->permSums);
     PgSceneDesc &d = flat->desc;
     memset(&d, 0, sizeof(d));
@@ -499,6 +521,12 @@ void GpuPathIntegrator::FillRenderDesc(PgRenderDesc *rd) const {
     rd->tile_pixels = rd->filter_general ? (16 + rd->tile_halo[0] + rd->tile_halo[2]) * (16 + rd->tile_halo[1] + rd->tile_halo[3]) : 256;
 }
 
+void GpuPathIntegrator::FillDirectDesc(PgDirectLightingDesc *dl) const {
+    dl->strategy = directStrategy;
+    dl->n_lights = (int)lightSamples.size();
+    dl->light_samples = lightSamples.data();
+}
+
 // The C ABI is bound at run time, the way a pbrt maintainer's plugin loader
 // would bind it; a missing library is a hard error, never a CPU fallback.
 namespace {
@@ -511,6 +539,7 @@ struct GpuApi {
     decltype(&pg_render_tile_count) render_tile_count = nullptr;
     decltype(&pg_render) render = nullptr;
     decltype(&pg_render_sharded) render_sharded = nullptr;
+    decltype(&pg_render_direct) render_direct = nullptr;  // optional: absent from a library older than the directlighting integrator
     decltype(&pg_counters) counters = nullptr;
     decltype(&pg_hlbvh_build) hlbvh_build = nullptr;
     bool Load() {
@@ -527,6 +556,7 @@ struct GpuApi {
 #define BIND(n) n = (decltype(n))dlsym(lib, "pg_" #n); if (!n) { Error("libpbrt_gpu.so lacks symbol pg_" #n); return false; }
         BIND(set_device) BIND(last_error) BIND(scene_create) BIND(scene_destroy) BIND(render_tile_count) BIND(render) BIND(render_sharded) BIND(counters) BIND(hlbvh_build)
 #undef BIND
+        render_direct = (decltype(render_direct))dlsym(lib, "pg_render_direct");
         return true;
     }
 };
@@ -567,6 +597,10 @@ void GpuPathIntegrator::Render(const Scene &scene) {
     Flatten(scene, &flat);
     PgRenderDesc rd;
     FillRenderDesc(&rd);
+    PgDirectLightingDesc dl;
+    FillDirectDesc(&dl);
+    if (directLighting && !gpuApi.render_direct) { Error("libpbrt_gpu.so lacks symbol pg_render_direct: Integrator \"directlighting\" cannot be rendered (there is no fallback to another integrator)."); Fatal(); }
+    if (directLighting && PbrtOptions.devices.size() > 1) { Error("Integrator \"directlighting\" on %d GPUs is outside this build's closed set (pg_render_sharded renders the path integrators only); render it on one.", (int)PbrtOptions.devices.size()); Fatal(); }
     // The devices of this node the frame is sharded over: tile t of the full-frame tiling goes to device t mod N, as the
     // reference shards a frame over machines with crop windows (main/pbrt.cpp:94-100); one host thread per device inside
     // pg_render_sharded, the shards gathered peer-to-peer on the first device.
@@ -609,10 +643,11 @@ void GpuPathIntegrator::Render(const Scene &scene) {
     int st;
     if (n == 1) {
         if (gpuApi.set_device(devices[0]) != PG_OK) { Error("pg_set_device: %s", gpuApi.last_error()); Fatal(); }
-        st = gpuApi.render(dev[0], &rd, filmPtr[0], strayPtr[0], maxStrays, &nStrays[0], PG_MEM_HOST, nullptr);
+        st = directLighting ? gpuApi.render_direct(dev[0], &rd, &dl, filmPtr[0], strayPtr[0], maxStrays, &nStrays[0], PG_MEM_HOST, nullptr)
+                            : gpuApi.render(dev[0], &rd, filmPtr[0], strayPtr[0], maxStrays, &nStrays[0], PG_MEM_HOST, nullptr);
     } else st = gpuApi.render_sharded(dev.data(), n, &rd, filmPtr.data(), strayPtr.data(), maxStrays, nStrays.data());
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (st != PG_OK) { Error("pg_render: %s", gpuApi.last_error()); for (PgScene *d : dev) gpuApi.scene_destroy(d); Fatal(); }
+    if (st != PG_OK) { Error("%s: %s", directLighting ? "pg_render_direct" : "pg_render", gpuApi.last_error()); for (PgScene *d : dev) gpuApi.scene_destroy(d); Fatal(); }
     std::vector<PgCounters> counters((size_t)n);
     for (int r = 0; r < n; ++r) if (gpuApi.counters(dev[r], &counters[r]) != PG_OK) memset(&counters[r], 0, sizeof(PgCounters));
     ReportStatistics(counters, sec);

@@ -300,6 +300,12 @@ class GpuPathIntegrator : public Integrator {
     void Flatten(const Scene &scene, FlatScene *flat) const;
     void FillRenderDesc(PgRenderDesc *rd) const;
     bool volumetric = false;  // VolPathIntegrator (integrators/volpath.cpp) instead of PathIntegrator
+    // DirectLightingIntegrator (integrators/directlighting.cpp) instead: maxDepth is its "maxdepth"; rrThreshold and lightSampleStrategy are unused.
+    // Rendered through pg_render_direct with the description FillDirectDesc gives beside FillRenderDesc's (whose integrator field stays 0)
+    bool directLighting = false;
+    int directStrategy = 0;         // LightStrategy: 0 = UniformSampleAll, 1 = UniformSampleOne
+    std::vector<int> lightSamples;  // nLightSamples (directlighting.cpp:46-51), one per light of the scene
+    void FillDirectDesc(PgDirectLightingDesc *dl) const;
     int cameraMedium = -1;
     std::shared_ptr<PerspectiveCamera> camera;
     std::shared_ptr<HaltonSampler> sampler;
@@ -310,6 +316,8 @@ class GpuPathIntegrator : public Integrator {
 };
 GpuPathIntegrator *CreatePathIntegrator(const ParamSet &params, std::shared_ptr<HaltonSampler> sampler,
                                         std::shared_ptr<PerspectiveCamera> camera);  // path.cpp:190-213
+GpuPathIntegrator *CreateDirectLightingIntegrator(const ParamSet &params, std::shared_ptr<HaltonSampler> sampler,
+                                                  std::shared_ptr<PerspectiveCamera> camera);  // directlighting.cpp:102-135
 
 // Result of a loadOnly parse (Options::loadOnly), consumed by the C API in pbrt_host.h.
 struct LoadedScene {
