@@ -1,6 +1,7 @@
 // pg_direct.h -- the DirectLightingIntegrator's kernels (integrators/directlighting.cpp:62-95 without its specular bounces, which pg_render_direct
-// refuses).  Included at the end of pg_kernels.hip: everything here is built from that file's pieces -- the interaction, the BxDF lists and the
-// material evaluators, the light sampling, the queue appends -- and k_resolve itself finishes every EstimateDirect.
+// refuses).  Included at the end of pg_kernels.hip: everything here is built from that file's pieces -- the interaction (hit_isect), an emitter's
+// L (area_light_l), the BxDF lists and the material evaluators, the light sampling with its shadow ray (shadow_ray_to), light.Pdf_Li of the
+// BSDF-sampled direction (mis_light_pdf), the queue appends -- and k_resolve itself finishes every EstimateDirect.  None of them is restated here.
 //
 // A camera ray's closest hit stays in its main queue while the frame walks the (light, sample) steps: every step is ONE launch of k_direct over the
 // queue, which rebuilds the hit's interaction and BSDF, draws the step's uLight / uScattering, and leaves a shadow ray, a BSDF-sampled ray and the
@@ -48,38 +49,16 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
             const PgMaterial mtl = sc.materials[tri.material];
             const bool surface = mtl.type != PG_MAT_NONE;
             if (surface ? (ds.first || ds.light != -1) : ds.first != 0) {
-                // ---- the SurfaceInteraction, as k_shade builds it
-                Isect is;
-                float sphU = 0, sphV = 0;
-                V3 sphDpdu = mk(0, 0, 0), sphDpdv = mk(0, 0, 0);
-                const bool onSphere = (tri.flags & PG_PRIM_SPHERE) != 0;
+                // ---- the SurfaceInteraction (hit_isect), under the instance's transform or -- MODE 2 -- the two of a hit two levels deep
                 int inst = sc.hitInst ? sc.hitInst[i] : -1, inst2 = -1;
                 if constexpr (TEX) nest_decode(sc, inst, inst2);
-                V3 shapeRayD = rayD;
-                if (inst >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst, i), rayD);
-                if (TEX && inst2 >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst2, i, true), shapeRayD);
-                if (onSphere) {
-                    const float4 o4 = qin.o[i];
-                    V3 shapeRayO = mk(o4.x, o4.y, o4.z);
-                    if (inst >= 0) { float dt; instance_ray(inst_w2i(sc, inst, i), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
-                    if (TEX && inst2 >= 0) { float dt; instance_ray(inst_w2i(sc, inst2, i, true), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
-                    const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
-                    is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
-                    is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
-                    if (TEX) { sphU = sh.u; sphV = sh.v; sphDpdu = sh.dpdu; sphDpdv = sh.dpdv; }
-                }
-                if (surface && ds.first) {  // directlighting.cpp:81: L += isect.Le(wo) -- L is zero before it
-                    Spec Le = sp(0);
-                    if (tri.light >= 0) {
-                        const PgLight &l = sc.lights[tri.light];
-                        const V3 nrm = onSphere ? is.n : hit_normal(sc, prim, tri, h4.y, h4.z, h4.w);
-                        if (l.two_sided || dot(nrm, -rayD) > 0) Le = sp3(l.L[0], l.L[1], l.L[2]);
-                    }
+                const InstXf outer = inst_xf(sc, inst, i), inner = inst_xf(sc, inst2, i, true);
+                QuadricUv quv;
+                Isect is = hit_isect(sc, outer, inner, (tri.flags & PG_PRIM_SPHERE) ? qin.o[i] : make_float4(0, 0, 0, 0), rayD, h4, prim, tri, quv);
+                if (surface && ds.first) {  // directlighting.cpp:81: L += isect.Le(wo) -- L is zero before it; an emitter lies under no instance: is.n is its own normal
+                    const Spec Le = tri.light >= 0 ? area_light_l(sc.lights[tri.light], is.n, -rayD) : sp(0);
                     st.L[slot] = make_float4(Le.r, Le.g, Le.b, L4.w);
                 }
-                if (!onSphere) is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shapeRayD);
-                if (TEX && inst2 >= 0 && !inst_identity(sc, inst2, i, true)) isect_to_world(inst_i2w(sc, inst2, i, true), inst_w2i(sc, inst2, i, true), is);
-                if (inst >= 0 && !inst_identity(sc, inst, i)) isect_to_world(inst_i2w(sc, inst, i), inst_w2i(sc, inst, i), is);
                 if (!surface) {  // directlighting.cpp:77-78: no BSDF -- Li(isect.SpawnRay(ray.d), ..., depth): the same depth, a ray without differentials
                     V3 o;
                     spawn_ray(is, rayD, o);
@@ -93,8 +72,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
                     PgBxDF lobeStore[TEX ? PG_MAX_BXDFS : 1];
                     if constexpr (TEX) {
                         TexHit th;
-                        tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst, inst2, onSphere, sphU, sphV, sphDpdu, sphDpdv, is, meta, L4.w, filmY, tileSerial, false,
-                                      index, th, st.L);
+                        tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, outer, inner, quv, is, meta, L4.w, filmY, tileSerial, false, index, th, st.L);
                         material_bump(sc, tri.material, th, is);
                         lb.ns = is.ns; lb.ng = is.n;
                         lb.ss = normalize(is.sdpdu);
@@ -140,11 +118,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
                         const Spec f = lbsdf_f(lb, is.wo, wi, nonSpecular) * absdot(wi, lb.ns);
                         scatteringPdf = lbsdf_pdf(lb, is.wo, wi, nonSpecular);
                         if (!is_black(f)) {
-                            const V3 origin = offset_ray_origin(is.p, is.pError, is.n, ls.p - is.p);  // VisibilityTester: p0.SpawnRayTo(p1), interaction.h:73-78
-                            const V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
-                            const V3 shD = target - origin;
-                            shadowO = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
-                            shadowD = make_float4(shD.x, shD.y, shD.z, __int_as_float(slot));
+                            shadow_ray_to(is.p, is.pError, is.n, ls, slot, shadowO, shadowD);
                             pushShadow = true;
                             const Spec c = PG_LIGHT_IS_DELTA(lh.type) ? (f * Li) / lightPdf : ((f * Li) * power_heuristic(1, lightPdf, 1, scatteringPdf)) / lightPdf;
                             pdLight = make_float4(c.r, c.g, c.b, 1);
@@ -157,33 +131,12 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
                         Spec f2 = lbsdf_sample_f(lb, is.wo, wi2, uS0, uS1, sPdf2, nonSpecular, sampledType);
                         f2 = f2 * absdot(wi2, lb.ns);
                         if (!is_black(f2) && sPdf2 > 0) {
-                            // light.Pdf_Li: an infinite light's from its distribution; an area light's Shape::Pdf by intersecting the light's own shape
-                            float lightPdf2 = 0;
                             V3 misRo;
                             spawn_ray(is, wi2, misRo);
-                            if (lh.type == PG_LIGHT_INFINITE) lightPdf2 = env_pdf_li(sc, light, wi2);
-                            else if (lh.tri.flags & PG_PRIM_SPHERE) {  // Sphere::Pdf, sphere.cpp:292-305
-                                const PgSphere &lsph = sc.spheres[__float_as_int(lh.tri.p0.x)];
-                                const bool inside = lsph.shape != PG_SHAPE_SPHERE || sphere_ref_inside(lsph, is.p, is.pError, is.n);
-                                float t;
-                                if (!inside) lightPdf2 = sphere_cone_pdf(lsph, is.p);
-                                else if (sphere_test(lsph, misRo, wi2, PG_INF, t)) {  // Shape::Pdf, shape.cpp:72-87
-                                    const SphereHit sh = sphere_interaction(lsph, misRo, wi2, t);
-                                    float pdf = lensq(is.p - sh.p) / (absdot(sh.n, -wi2) * lh.area);
-                                    if (isinf(pdf)) pdf = 0.f;
-                                    lightPdf2 = pdf;
-                                }
-                            } else {
-                                float t, lb0, lb1, lb2;
-                                ++nLightTests;
-                                if (tri_test(lh.tri.p0, lh.tri.p1, lh.tri.p2, misRo, wi2, PG_INF, t, lb0, lb1, lb2) && !(lh.tri.flags & PG_TRI_BOGUS)) {
-                                    const V3 lp = lh.tri.p0 * lb0 + lh.tri.p1 * lb1 + lh.tri.p2 * lb2;
-                                    const V3 ln = normalize(cross(lh.tri.p0 - lh.tri.p2, lh.tri.p1 - lh.tri.p2));
-                                    float pdf = lensq(is.p - lp) / (absdot(ln, -wi2) * lh.area);
-                                    if (isinf(pdf)) pdf = 0.f;
-                                    lightPdf2 = pdf;
-                                }
-                            }
+                            int lightPrim;
+                            bool inside;
+                            mis_light_of(sc, lh, lightNum, is.p, is.pError, is.n, lightPrim, inside);
+                            const float lightPdf2 = mis_light_pdf<true>(sc, lightPrim, lh.area, inside, is.p, misRo, wi2, nLightTests);
                             if (lightPdf2 != 0) {
                                 misO = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
                                 misD = make_float4(wi2.x, wi2.y, wi2.z, __int_as_float(slot));

@@ -2161,14 +2161,52 @@ PG_DEV void prim_interface(const DScene &sc, int prim, int rayMedium, int &mIn, 
     else mIn = mOut = rayMedium;
 }
 
-// InstanceToWorld, its inverse and IsIdentity of the instance closest-hit result `i` was reached through: the instance's own or -- a moving one --
-// PrimitiveToWorld.Interpolate(r.time), which k_trace<.., XP_ANIM> computed for the accepted hit's ray and left at animXf[i] (pg_motion.h)
-// (inner: the TransformedPrimitive INSIDE the object of a hit two levels deep, DScene::hasNest: its matrices wait in the buffer's second half)
-PG_DEV const float *inst_i2w(const DScene &sc, int inst, int i, bool inner = false) { const PgInstance &in = sc.instances[inst]; return in.animated ? sc.animXf + (size_t)PG_XF_STRIDE * ((inner ? (size_t)sc.nestXfOff : 0) + i) : in.i2w; }
-PG_DEV const float *inst_w2i(const DScene &sc, int inst, int i, bool inner = false) { const PgInstance &in = sc.instances[inst]; return in.animated ? sc.animXf + (size_t)PG_XF_STRIDE * ((inner ? (size_t)sc.nestXfOff : 0) + i) + 16 : in.w2i; }
-PG_DEV bool inst_identity(const DScene &sc, int inst, int i, bool inner = false) { const PgInstance &in = sc.instances[inst]; return in.animated ? sc.animXf[(size_t)PG_XF_STRIDE * ((inner ? (size_t)sc.nestXfOff : 0) + i) + 32] != 0.f : in.identity != 0; }
+// ---- what every kernel that meets a closest hit shares: the hit's transforms, its SurfaceInteraction, an emitter's L there, and the two rays of
+// EstimateDirect's light sample and BSDF sample.  One implementation each: the films are the reference's bit for bit, and two copies of a formula
+// are two chances to round differently.
+
+// One transform above a closest hit: InstanceToWorld, its inverse and IsIdentity of instance `inst` (< 0: none) -- the instance's own or, a moving one's,
+// PrimitiveToWorld.Interpolate(r.time) as pg_motion.h left it in record off + i of `kept`.  Made once per hit: `outer` is the object instance's, `inner` the
+// TransformedPrimitive's INSIDE the object of a hit two levels deep (DScene::hasNest).  It holds the two indices, not the addresses: those are formed where a
+// matrix is read -- both sources are global memory --, so that no pointer is live across the interaction's arithmetic.  `kept` must exist whenever an instance
+// is animated (moving() does not test it; k_sss_exit once fell back to the instance's own matrices under `animated && hitXf`): DScene::animXf and
+// SssState::hitXf are both allocated exactly for a scene with motion (pg_abi.hip, `hasMotion`)
+struct InstXf {
+    const PgInstance *instances; const float *kept; int off;  // (uniform over a launch)
+    int inst, i;
+    PG_DEV bool some() const { return inst >= 0; }
+    PG_DEV const float *moving() const { return instances[inst].animated ? kept + (size_t)PG_XF_STRIDE * ((size_t)off + i) : nullptr; }
+    PG_DEV const float *i2w() const { const float *xf = moving(); return xf ? xf : instances[inst].i2w; }
+    PG_DEV const float *w2i() const { const float *xf = moving(); return xf ? xf + 16 : instances[inst].w2i; }
+    PG_DEV bool identity() const { const float *xf = moving(); return xf ? xf[32] != 0.f : instances[inst].identity != 0; }
+};
+// of the instance closest-hit result `i` was reached through: k_trace<.., XP_ANIM> computed a moving one's matrices for the accepted hit's ray and left them
+// at animXf[i] -- the inner transform's in the buffer's second half
+PG_DEV InstXf inst_xf(const DScene &sc, int inst, int i, bool inner = false) { return InstXf{sc.instances, sc.animXf, inner ? sc.nestXfOff : 0, inst, i}; }
 // DScene::hasNest: a closest hit's instance word is outer + nInstances * (inner + 1); inner = -1 for a hit one level deep
 PG_DEV void nest_decode(const DScene &sc, int &inst, int &inst2) { inst2 = -1; if (sc.hasNest && inst >= 0) { inst2 = inst / sc.nInstances - 1; inst = inst % sc.nInstances; } }
+// The ray a hit under these transforms was computed on (primitive.cpp:80-82: the outer transform first): its direction, which every interaction's wo
+// comes from ...
+PG_DEV V3 shape_ray_dir(const InstXf &outer, const InstXf &inner, V3 rayD) {
+    V3 d = rayD;
+    if (outer.some()) d = m4_vec(outer.w2i(), rayD);
+    if (inner.some()) d = m4_vec(inner.w2i(), d);
+    return d;
+}
+// ... and the whole ray, which a quadric's interaction is computed from (instance_ray: the very operations of k_trace's, pg_sphere.h)
+PG_DEV void shape_ray(const InstXf &outer, const InstXf &inner, float4 o4, V3 rayD, V3 &shapeRayO, V3 &shapeRayD) {
+    shapeRayO = mk(o4.x, o4.y, o4.z);
+    shapeRayD = rayD;
+    if (outer.some()) { float dt; instance_ray(outer.w2i(), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
+    if (inner.some()) { float dt; instance_ray(inner.w2i(), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
+}
+// Sphere::Intersect's SurfaceInteraction (sphere.cpp:149-152): the shading geometry is the quadric's own
+PG_DEV Isect sphere_isect(const SphereHit &sh) {
+    Isect is;
+    is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
+    is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
+    return is;
+}
 // InterpolatedPrimToWorld(*isect) of a hit reached through an object instance, transform.cpp:262-297
 PG_DEV void isect_to_world(const float *i2w, const float *w2i, Isect &is) {
     Isect w;
@@ -2182,14 +2220,99 @@ PG_DEV void isect_to_world(const float *i2w, const float *w2i, Isect &is) {
     if (dot(w.ns, w.n) < 0.f) w.ns = -w.ns;  // Faceforward(shading.n, n)
     is = w;
 }
+// on the way out the inner transform first (TransformedPrimitive::Intersect returns through itself twice); an identity is skipped as the
+// reference skips it (primitive.cpp:85: if (!InterpolatedPrimToWorld.IsIdentity()))
+PG_DEV void isect_to_world(const InstXf &outer, const InstXf &inner, Isect &is) {
+    if (inner.some() && !inner.identity()) isect_to_world(inner.i2w(), inner.w2i(), is);
+    if (outer.some() && !outer.identity()) isect_to_world(outer.i2w(), outer.w2i(), is);
+}
+// A quadric hit's (u, v) and geometric dpdu / dpdv, in the shape's space: what textures read besides the interaction (tex_hit_setup)
+struct QuadricUv { bool on; float u, v; V3 dpdu, dpdv; };  // (on: the hit is on a quadric at all)
+// The SurfaceInteraction of closest hit h4 on primitive `prim`, found by ray (o4, rayD) under these transforms: the three stages above in one
+PG_DEV Isect hit_isect(const DScene &sc, const InstXf &outer, const InstXf &inner, float4 o4, V3 rayD, float4 h4, int prim, const Tri &tri, QuadricUv &quv) {
+    Isect is;
+    quv.on = (tri.flags & PG_PRIM_SPHERE) != 0;
+    quv.u = quv.v = 0; quv.dpdu = quv.dpdv = mk(0, 0, 0);
+    if (quv.on) {  // the hit record of a sphere carries tHit: Sphere::Intersect's interaction from the ray and the root
+        V3 shapeRayO, shapeRayD;
+        shape_ray(outer, inner, o4, rayD, shapeRayO, shapeRayD);
+        const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
+        is = sphere_isect(sh);
+        quv.u = sh.u; quv.v = sh.v; quv.dpdu = sh.dpdu; quv.dpdv = sh.dpdv;
+    } else is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shape_ray_dir(outer, inner, rayD));
+    isect_to_world(outer, inner, is);
+    return is;
+}
+// DiffuseAreaLight::L(intr, w) (diffuse.h:56-58) with the emitter's geometric normal n
+PG_DEV Spec area_light_l(const PgLight &l, V3 n, V3 w) { return (l.two_sided || dot(n, w) > 0) ? sp3(l.L[0], l.L[1], l.L[2]) : sp(0); }
+// ... at closest hit h4 of ray (o4, rayD) on the emitter's primitive, back along the ray (integrator.cpp:204 lightIsect.Le(-wi)): the kernels that meet
+// the hit without building its interaction.  An emitter lies under no instance (api.cpp:1408-1409: an object definition's shapes take no area light), so the ray is the
+// shape's.  SPHERES: the scene may have quadrics at all (DScene::ext)
+template <bool SPHERES>
+PG_DEV Spec area_light_le(const DScene &sc, const PgLight &l, int prim, const Tri &tri, float4 h4, float4 o4, V3 rayD) {
+    V3 nrm;
+    if (SPHERES && (tri.flags & PG_PRIM_SPHERE)) nrm = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], mk(o4.x, o4.y, o4.z), rayD, h4.y).n;
+    else nrm = hit_normal(sc, prim, tri, h4.y, h4.z, h4.w);
+    return area_light_l(l, nrm, -rayD);
+}
+// VisibilityTester's ray from (p, pError, n) to the light sample: p0.SpawnRayTo(p1), interaction.h:73-78 -- as a shadow-queue record (tag: what the
+// queue's consumer finds the vertex by); returns the ray's direction
+PG_DEV V3 shadow_ray_to(V3 p, V3 pError, V3 n, const LightSample &ls, int tag, float4 &o4, float4 &d4) {
+    const V3 origin = offset_ray_origin(p, pError, n, ls.p - p);
+    const V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
+    const V3 d = target - origin;
+    o4 = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
+    d4 = make_float4(d.x, d.y, d.z, __int_as_float(tag));
+    return d;
+}
+// light.Pdf_Li(ref, wi) of EstimateDirect's BSDF-sampled direction (integrator.cpp:175-178), for the ray (ro, wi) spawned at refP: an infinite light's
+// from its distribution (lightPrim = -1 - its number: no geometry to test); an area light's Shape::Pdf, which intersects the light's own shape
+// (shape.cpp:72-87, diffuse.cpp:83-87) -- one triangle test counted in nLightTests, whose hit on a degenerate triangle (PG_TRI_BOGUS) the reference's
+// Triangle::Intersect refuses --, or Sphere::Pdf (sphere.cpp:292-305): the cone's for a reference point outside (`inside`: sphere_ref_inside, or a partial sphere)
+template <bool EXT>
+PG_DEV float mis_light_pdf(const DScene &sc, int lightPrim, float lightArea, bool inside, V3 refP, V3 ro, V3 wi, unsigned int &nLightTests) {
+    float lightPdf = 0;
+    if (EXT && lightPrim < 0) lightPdf = env_pdf_li(sc, sc.lights[-1 - lightPrim], wi);
+    const Tri lt = load_tri(sc, lightPrim < 0 ? 0 : lightPrim);
+    float t, lb0, lb1, lb2;
+    if (EXT && lightPrim >= 0 && (lt.flags & PG_PRIM_SPHERE)) {
+        const PgSphere &ls = sc.spheres[__float_as_int(lt.p0.x)];
+        if (!inside) lightPdf = sphere_cone_pdf(ls, refP);
+        else if (sphere_test(ls, ro, wi, PG_INF, t)) {  // Shape::Pdf, shape.cpp:72-87
+            const SphereHit sh = sphere_interaction(ls, ro, wi, t);
+            float pdf = lensq(refP - sh.p) / (absdot(sh.n, -wi) * lightArea);
+            if (isinf(pdf)) pdf = 0.f;
+            lightPdf = pdf;
+        }
+    } else {
+        if (lightPrim >= 0) ++nLightTests;
+        if (lightPrim >= 0 && tri_test(lt.p0, lt.p1, lt.p2, ro, wi, PG_INF, t, lb0, lb1, lb2) && !(lt.flags & PG_TRI_BOGUS)) {
+            const V3 lp = lt.p0 * lb0 + lt.p1 * lb1 + lt.p2 * lb2;
+            const V3 ln = normalize(cross(lt.p0 - lt.p2, lt.p1 - lt.p2));
+            float pdf = lensq(refP - lp) / (absdot(ln, -wi) * lightArea);
+            if (isinf(pdf)) pdf = 0.f;
+            lightPdf = pdf;
+        }
+    }
+    return lightPdf;
+}
+// what mis_light_pdf needs of the sampled light: (lightPrim, inside) for the reference point (p, pError, n)
+PG_DEV void mis_light_of(const DScene &sc, const LightHot &lh, int lightNum, V3 p, V3 pError, V3 n, int &lightPrim, bool &inside) {
+    lightPrim = lh.type == PG_LIGHT_INFINITE ? -1 - lightNum : lh.prim;
+    inside = false;
+    if (lh.type == PG_LIGHT_AREA && (lh.tri.flags & PG_PRIM_SPHERE)) {
+        const PgSphere &lsph = sc.spheres[__float_as_int(lh.tri.p0.x)];
+        inside = lsph.shape != PG_SHAPE_SPHERE || sphere_ref_inside(lsph, p, pError, n);
+    }
+}
 // What textures read of the SurfaceInteraction at main-queue entry i: (u, v), p and ComputeDifferentials' outputs
-// (interaction.cpp:101-147).  sph*: a quadric hit's (u, v) and geometric dpdu / dpdv; filmX / filmY: the camera sample's pFilm
-PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQueue &qin, int i, int slot, int prim, const Tri &tri, float4 h4, V3 rayD, int inst, int inst2,
-                          bool onSphere, float sphU, float sphV, V3 sphDpdu, V3 sphDpdv, const Isect &is, int4 meta, float filmX, float filmY,
+// (interaction.cpp:101-147).  quv: a quadric hit's (u, v) and geometric dpdu / dpdv; filmX / filmY: the camera sample's pFilm
+PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQueue &qin, int i, int slot, int prim, const Tri &tri, float4 h4, V3 rayD, const InstXf &outer,
+                          const InstXf &inner, const QuadricUv &quv, const Isect &is, int4 meta, float filmX, float filmY,
                           bool tileSerial, bool pixelArrays, uint64_t index, TexHit &th, const float4 *stL) {
     th.p = is.p;
     V3 gdpdu, gdpdv;  // the geometric dpdu / dpdv (not the shading ones)
-    if (onSphere) { th.u = sphU; th.v = sphV; gdpdu = sphDpdu; gdpdv = sphDpdv; }
+    if (quv.on) { th.u = quv.u; th.v = quv.v; gdpdu = quv.dpdu; gdpdv = quv.dpdv; }
     else {
         float uv[6];
         load_uv(sc, prim, tri.flags, uv);
@@ -2197,8 +2320,8 @@ PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQue
         th.u = h4.y * uv[0] + h4.z * uv[2] + h4.w * uv[4];  // uvHit, triangle.cpp:332
         th.v = h4.y * uv[1] + h4.z * uv[3] + h4.w * uv[5];
     }
-    if (inst2 >= 0 && !inst_identity(sc, inst2, i, true)) { gdpdu = m4_vec(inst_i2w(sc, inst2, i, true), gdpdu); gdpdv = m4_vec(inst_i2w(sc, inst2, i, true), gdpdv); }  // (the inner transform first)
-    if (inst >= 0 && !inst_identity(sc, inst, i)) { gdpdu = m4_vec(inst_i2w(sc, inst, i), gdpdu); gdpdv = m4_vec(inst_i2w(sc, inst, i), gdpdv); }
+    if (inner.some() && !inner.identity()) { gdpdu = m4_vec(inner.i2w(), gdpdu); gdpdv = m4_vec(inner.i2w(), gdpdv); }  // (the inner transform first)
+    if (outer.some() && !outer.identity()) { gdpdu = m4_vec(outer.i2w(), gdpdu); gdpdv = m4_vec(outer.i2w(), gdpdv); }
     th.dpdx = th.dpdy = mk(0, 0, 0);
     th.dudx = th.dvdx = th.dudy = th.dvdy = 0;
     if (meta.w & PG_META_HASDIFF) {  // SurfaceInteraction::ComputeDifferentials, interaction.cpp:101-147
@@ -2252,6 +2375,13 @@ PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQue
             }
         }
     }
+}
+// (the same from the hit's instance words and a quadric's values apart, for k_shade, which holds no InstXf across its vertex)
+PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQueue &qin, int i, int slot, int prim, const Tri &tri, float4 h4, V3 rayD, int inst, int inst2,
+                          bool onSphere, float sphU, float sphV, V3 sphDpdu, V3 sphDpdv, const Isect &is, int4 meta, float filmX, float filmY,
+                          bool tileSerial, bool pixelArrays, uint64_t index, TexHit &th, const float4 *stL) {
+    const QuadricUv quv = {onSphere, sphU, sphV, sphDpdu, sphDpdv};
+    tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst_xf(sc, inst, i), inst_xf(sc, inst2, i, true), quv, is, meta, filmX, filmY, tileSerial, pixelArrays, index, th, stL);
 }
 // Material::Bump (material.cpp:46-85) of the material whose BSDF this is: its own bump map, or -- through mix materials, whose
 // BSDF is their first material's -- the first material's
@@ -2486,26 +2616,23 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
         // outer instance's, then the inner TransformedPrimitive's on the way in; InterpolatedPrimToWorld of the inner, then of the outer, on the way out
         int inst2 = -1;
         if constexpr (TEX) nest_decode(sc, inst, inst2);
-        V3 shapeRayD = rayD;
-        if (inst >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst, i), rayD);
-        if (TEX && inst2 >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst2, i, true), shapeRayD);
+        // (the interaction is hit_isect's, in its stages: the quadric's here, where Le needs its normal; the triangle's and the way to world space below, at the
+        // vertices still alive.  No InstXf is held across the vertex: each stage names the transforms again, and textures take the instance words -- held
+        // in two structures, the MODE 2 volpath instantiations took four more registers, past 256)
+        V3 shapeRayD = shape_ray_dir(inst_xf(sc, inst, i), inst_xf(sc, inst2, i, true), rayD);
         if (onSphere) {  // the hit record of a sphere carries tHit: Sphere::Intersect's interaction from the ray and the root
-            const float4 o4 = qin.o[i];
+            const float4 o4 = qin.o[i];  // (the next three lines mirror shape_ray, on top of the direction above)
             V3 shapeRayO = mk(o4.x, o4.y, o4.z);
-            if (inst >= 0) { float dt; instance_ray(inst_w2i(sc, inst, i), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
-            if (TEX && inst2 >= 0) { float dt; instance_ray(inst_w2i(sc, inst2, i, true), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
+            if (inst >= 0) { float dt; instance_ray(inst_xf(sc, inst, i).w2i(), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
+            if (TEX && inst2 >= 0) { float dt; instance_ray(inst_xf(sc, inst2, i, true).w2i(), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
             const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
-            is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
-            is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
+            is = sphere_isect(sh);
             if (TEX) { sphU = sh.u; sphV = sh.v; sphDpdu = sh.dpdu; sphDpdv = sh.dpdv; }
         }
         // path.cpp:91-102 emitted light at the vertex (volpath.cpp:103-110: only when no medium interaction was sampled)
         if (phaseB || (VOL && (volDead || inMedium))) {
         } else if ((bounces == 0 || specularBounce) && found && tri.light >= 0) {
-            const PgLight &l = sc.lights[tri.light];
-            V3 nrm = onSphere ? is.n : hit_normal(sc, prim, tri, h4.y, h4.z, h4.w);
-            Spec Le = (l.two_sided || dot(nrm, -rayD) > 0) ? sp3(l.L[0], l.L[1], l.L[2]) : sp(0);
-            L = L + beta * Le;
+            L = L + beta * area_light_l(sc.lights[tri.light], onSphere ? is.n : hit_normal(sc, prim, tri, h4.y, h4.z, h4.w), -rayD);
         } else if ((bounces == 0 || specularBounce) && found) L = L + beta * sp(0);
         else if (EXT && (bounces == 0 || specularBounce) && !found && sc.hasInfinite) {  // path.cpp:96-100: every infinite light's Le(ray)
             for (int li = 0; li < sc.nLights; ++li)
@@ -2556,11 +2683,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                         if (lightPdf > 0 && !is_black(Li)) {
                             const float ph = phase_hg(dot(wo, wi), g);  // integrator.cpp:135-141
                             if (ph != 0) {
-                                V3 origin = offset_ray_origin(mediumP, zero, zero, ls.p - mediumP);
-                                V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
-                                const V3 shD = target - origin;
-                                s_ray[1][0][tid] = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
-                                s_ray[1][1][tid] = make_float4(shD.x, shD.y, shD.z, __int_as_float(pdi));  // (transmittance rays find their terms by pdi)
+                                shadow_ray_to(mediumP, zero, zero, ls, pdi, s_ray[1][0][tid], s_ray[1][1][tid]);  // (transmittance rays find their terms by pdi)
                                 pushShadow = true;
                                 const bool isDelta = PG_LIGHT_IS_DELTA(light.type);
                                 volWeight = isDelta ? -1.f : power_heuristic(1, lightPdf, 1, ph);
@@ -2613,8 +2736,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
         }
         if (alive && !handled) {
             if (!onSphere) is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shapeRayD);
-            if (TEX && inst2 >= 0 && !inst_identity(sc, inst2, i, true)) isect_to_world(inst_i2w(sc, inst2, i, true), inst_w2i(sc, inst2, i, true), is);
-            if (inst >= 0 && !inst_identity(sc, inst, i)) isect_to_world(inst_i2w(sc, inst, i), inst_w2i(sc, inst, i), is);
+            isect_to_world(inst_xf(sc, inst, i), inst_xf(sc, inst2, i, true), is);
             const PgMaterial &m = mtl;
             int mIn = 0, mOut = 0;  // VOL: isect.mediumInterface
             if constexpr (VOL) prim_interface(sc, prim, med, mIn, mOut);
@@ -2765,12 +2887,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                             if constexpr (EXT) { f = lbsdf_f(lb, is.wo, wi, nonSpecular) * absdot(wi, shNs); scatteringPdf = lbsdf_pdf(lb, is.wo, wi, nonSpecular); }
                             else { f = bsdf_f(bsdf, is.wo, wi) * absdot(wi, shNs); scatteringPdf = bsdf_pdf(bsdf, is.wo, wi); }
                             if (!is_black(f)) {
-                                // VisibilityTester: p0.SpawnRayTo(p1), interaction.h:73-78
-                                V3 origin = offset_ray_origin(is.p, is.pError, is.n, ls.p - is.p);
-                                V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
-                                const V3 shD = target - origin;
-                                s_ray[1][0][tid] = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
-                                s_ray[1][1][tid] = make_float4(shD.x, shD.y, shD.z, __int_as_float(VOL ? pdi : slot));
+                                [[maybe_unused]] const V3 shD = shadow_ray_to(is.p, is.pError, is.n, ls, VOL ? pdi : slot, s_ray[1][0][tid], s_ray[1][1][tid]);
                                 pushShadow = true;
                                 // delta lights take no MIS weight (integrator.cpp:155-160)
                                 const bool isDelta = PG_LIGHT_IS_DELTA(lh.type);
@@ -2809,6 +2926,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                             spawn_ray(is, wi2, misRo);
                             misWi = wi2; misF = f2; misPdf = sPdf2; misP = is.p;
                             if constexpr (VOL) misMedium = dot(wi2, is.n) > 0 ? mOut : mIn;
+                            // (the next lines mirror mis_light_of, with the EXT guards that keep the infinite light and the sphere out of MODE 0)
                             misLightPrim = (EXT && lh.type == PG_LIGHT_INFINITE) ? -1 - lightNum : lh.prim; misLightArea = lh.area;
                             if (EXT && lh.type == PG_LIGHT_AREA && (lh.tri.flags & PG_PRIM_SPHERE)) {  // only the sphere overrides Shape::Pdf (with its cone pdf, from outside)
                                 const PgSphere &lsph = sc.spheres[__float_as_int(lh.tri.p0.x)];
@@ -2918,30 +3036,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
         rp.retryList[atomicAdd(&sc.voxelCounters[1], 1)] = shade_position(rp, qin);
     }
     if (misCand) {
-        // light.Pdf_Li -> Shape::Pdf(ref, wi): intersect the light's own triangle (shape.cpp:72-87, diffuse.cpp:83-87)
-        float lightPdf2 = 0;
-        if (EXT && misLightPrim < 0) lightPdf2 = env_pdf_li(sc, sc.lights[-1 - misLightPrim], misWi);  // infinite light: no geometry to test
-        Tri lt = load_tri(sc, misLightPrim < 0 ? 0 : misLightPrim);
-        float t, lb0, lb1, lb2;
-        if (EXT && misLightPrim >= 0 && (lt.flags & PG_PRIM_SPHERE)) {  // Sphere::Pdf, sphere.cpp:292-305
-            const PgSphere &ls = sc.spheres[__float_as_int(lt.p0.x)];
-            if (!misInside) lightPdf2 = sphere_cone_pdf(ls, misP);
-            else if (sphere_test(ls, misRo, misWi, PG_INF, t)) {  // Shape::Pdf, shape.cpp:72-87
-                const SphereHit sh = sphere_interaction(ls, misRo, misWi, t);
-                float pdf = lensq(misP - sh.p) / (absdot(sh.n, -misWi) * misLightArea);
-                if (isinf(pdf)) pdf = 0.f;
-                lightPdf2 = pdf;
-            }
-        } else {
-            if (misLightPrim >= 0) ++nLightTests;
-            if (misLightPrim >= 0 && tri_test(lt.p0, lt.p1, lt.p2, misRo, misWi, PG_INF, t, lb0, lb1, lb2) && !(lt.flags & PG_TRI_BOGUS)) {
-                V3 lp = lt.p0 * lb0 + lt.p1 * lb1 + lt.p2 * lb2;
-                V3 ln = normalize(cross(lt.p0 - lt.p2, lt.p1 - lt.p2));
-                float pdf = lensq(misP - lp) / (absdot(ln, -misWi) * misLightArea);
-                if (isinf(pdf)) pdf = 0.f;
-                lightPdf2 = pdf;
-            }
-        }
+        const float lightPdf2 = mis_light_pdf<EXT>(sc, misLightPrim, misLightArea, misInside, misP, misRo, misWi, nLightTests);
         if (lightPdf2 != 0) {
             s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
             s_ray[2][1][tid] = make_float4(misWi.x, misWi.y, misWi.z, __int_as_float(VOL ? pdi : slot));
@@ -3008,7 +3103,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
     }
 }
 // Material::ComputeScatteringFunctions ahead of the shading launch, for the main-queue entries whose hit has a material with
-// textured parameters: the interaction (as k_shade builds it), what textures read of it (tex_hit_setup), Material::Bump and the
+// textured parameters: the interaction (hit_isect), what textures read of it (tex_hit_setup), Material::Bump and the
 // material's BxDF list, written to rp.matPre at the entry's index; k_shade<3, .> takes them from there and is the BxDF-list kernel
 // otherwise.  Why two launches: evaluated inside the shading kernel (k_shade<2, .>) the texture / material evaluators' registers and
 // call frames come on top of a path vertex's whole state -- 251 VGPRs, two waves per SIMD, the list of up to 8 x 120 B in scratch --
@@ -3045,27 +3140,14 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, PG_MATERIAL_WAVES) void k_material(
     }
     const bool tileSerial = rd.sampler >= PG_SAMPLER_RANDOM && !sc.tsBatched, pixelArrays = sc.tsBatched != 0;
     const uint64_t index = (uint64_t)(uint32_t)meta.x | ((uint64_t)(uint32_t)meta.y << 32);
-    Isect is;
-    float sphU = 0, sphV = 0;
-    V3 sphDpdu = mk(0, 0, 0), sphDpdv = mk(0, 0, 0);
-    const bool onSphere = (tri.flags & PG_PRIM_SPHERE) != 0;
-    const int inst = sc.hitInst ? sc.hitInst[i] : -1;
-    V3 shapeRayD = rayD;
-    if (inst >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst, i), rayD);
-    if (onSphere) {
-        const float4 o4 = qin.o[i];
-        V3 shapeRayO = mk(o4.x, o4.y, o4.z);
-        if (inst >= 0) { float dt; instance_ray(inst_w2i(sc, inst, i), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
-        const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
-        is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
-        is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
-        sphU = sh.u; sphV = sh.v; sphDpdu = sh.dpdu; sphDpdv = sh.dpdv;
-    } else is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shapeRayD);
-    if (inst >= 0 && !inst_identity(sc, inst, i)) isect_to_world(inst_i2w(sc, inst, i), inst_w2i(sc, inst, i), is);
+    // (the scenes whose hits can lie under two transforms are shaded by k_shade<2>, without this launch: one level here)
+    const InstXf outer = inst_xf(sc, sc.hitInst ? sc.hitInst[i] : -1, i), inner = inst_xf(sc, -1, i, true);
+    QuadricUv quv;
+    Isect is = hit_isect(sc, outer, inner, (tri.flags & PG_PRIM_SPHERE) ? qin.o[i] : make_float4(0, 0, 0, 0), rayD, h4, prim, tri, quv);
     float filmX = 0, filmY = 0;  // the camera sample's pFilm, for the camera ray's differentials
     if (meta.w & PG_META_HASDIFF) { filmX = bySlot ? st.L[slot].w : qsIn.L[i].w; filmY = bySlot ? st.beta[slot].w : qsIn.beta[i].w; }
     TexHit th;
-    tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst, -1, onSphere, sphU, sphV, sphDpdu, sphDpdv, is, meta, filmX, filmY, tileSerial, pixelArrays, index, th, st.L);
+    tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, outer, inner, quv, is, meta, filmX, filmY, tileSerial, pixelArrays, index, th, st.L);
     material_bump<1>(sc, tri.material, th, is);
     int nl = 0;
     float etaL = 1;
@@ -3238,15 +3320,9 @@ __global__ __launch_bounds__(PG_BLOCK) void k_resolve(DScene sc, PathState st, R
         if (prim >= 0) {
             Tri t = load_tri(sc, prim);
             if (t.light == info.z) {  // lightIsect.primitive->GetAreaLight() == &light
-                const PgLight &l = sc.lights[t.light];
                 const float4 d4 = qmis.d[info.y];
-                V3 wi = mk(d4.x, d4.y, d4.z);
-                V3 nrm;
-                if (EXT && (t.flags & PG_PRIM_SPHERE)) {
-                    const float4 o4 = qmis.o[info.y];
-                    nrm = sphere_interaction(sc.spheres[__float_as_int(t.p0.x)], mk(o4.x, o4.y, o4.z), wi, h.y).n;
-                } else nrm = hit_normal(sc, prim, t, h.y, h.z, h.w);
-                Spec Li = (l.two_sided || dot(nrm, -wi) > 0) ? sp3(l.L[0], l.L[1], l.L[2]) : sp(0);
+                const bool onSphere = EXT && (t.flags & PG_PRIM_SPHERE);
+                const Spec Li = area_light_le<EXT>(sc, sc.lights[t.light], prim, t, h, onSphere ? qmis.o[info.y] : d4, mk(d4.x, d4.y, d4.z));
                 if (!is_black(Li)) Ld = Ld + ((((sp3(pm.x, pm.y, pm.z) * Li) * sp(1.f)) * pb.w) / pm.w);
             }
         } else if (EXT && sc.lights[info.z].type == PG_LIGHT_INFINITE) {  // integrator.cpp:207-208: no surface hit: Li = light.Le(ray)
@@ -3281,38 +3357,16 @@ void launch_resolve(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis,
 // are loops of Scene::Intersect calls that step through surfaces without a material; here every loop iteration is one
 // closest-hit launch over the queue of rays still under way followed by this kernel, which finishes a ray or re-spawns it.
 // ===========================================================================
-// p, pError and n of the SurfaceInteraction of a closest hit (Triangle::Intersect / Sphere::Intersect, then the instance's
-// InterpolatedPrimToWorld), as k_shade builds them
+// p, pError and n of hit_isect's SurfaceInteraction: all that stepping over a surface needs of it (the rest of the interaction is left to the compiler's
+// dead-code elimination: nothing else of it is read)
 // NEST: the caller can meet hits under two transforms (k_through; the probe chains cannot: scenes with BSSRDF materials and such hits are refused)
 template <bool NEST>
 PG_DEV void through_point(const DScene &sc, int ri, float4 o4, V3 rayD, float4 h4, int prim, const Tri &tri, V3 &p, V3 &pError, V3 &n) {
     int inst = sc.hitInst ? sc.hitInst[ri] : -1, inst2 = -1;
     if constexpr (NEST) nest_decode(sc, inst, inst2);
-    V3 shapeRayD = rayD;
-    if (inst >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst, ri), rayD);
-    if (inst2 >= 0) shapeRayD = m4_vec(inst_w2i(sc, inst2, ri, true), shapeRayD);
-    if (tri.flags & PG_PRIM_SPHERE) {
-        V3 shapeRayO = mk(o4.x, o4.y, o4.z);
-        if (inst >= 0) { float dt; instance_ray(inst_w2i(sc, inst, ri), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
-        if (inst2 >= 0) { float dt; instance_ray(inst_w2i(sc, inst2, ri, true), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
-        const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
-        p = sh.p; pError = sh.pError; n = sh.n;
-    } else {
-        const Isect is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shapeRayD);
-        p = is.p; pError = is.pError; n = is.n;
-    }
-    if (inst2 >= 0 && !inst_identity(sc, inst2, ri, true)) {
-        V3 pe;
-        p = m4_point_err2(inst_i2w(sc, inst2, ri, true), p, pError, pe);
-        pError = pe;
-        n = normalize(m4_normal(inst_w2i(sc, inst2, ri, true), n));
-    }
-    if (inst >= 0 && !inst_identity(sc, inst, ri)) {
-        V3 pe;
-        p = m4_point_err2(inst_i2w(sc, inst, ri), p, pError, pe);
-        pError = pe;
-        n = normalize(m4_normal(inst_w2i(sc, inst, ri), n));
-    }
+    QuadricUv quv;
+    const Isect is = hit_isect(sc, inst_xf(sc, inst, ri), inst_xf(sc, inst2, ri, true), o4, rayD, h4, prim, tri, quv);
+    p = is.p; pError = is.pError; n = is.n;
 }
 // GRID: a segment inside a GridDensityMedium is attenuated by ratio tracking (grid.cpp:88-120), whose numbers come from the path's
 // sampler: they are drawn here, at the path's current dimension / stream position, which st.meta[slot] keeps for the shading
@@ -3356,13 +3410,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_through(DScene sc, PathState st, V
                 const int lightNum = st.pdInfo[slot].z;
                 Spec Li = sp(0);
                 if (surface) {
-                    if (tri.light == lightNum) {
-                        const PgLight &l = sc.lights[tri.light];
-                        V3 nrm;
-                        if (tri.flags & PG_PRIM_SPHERE) nrm = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], mk(o4.x, o4.y, o4.z), rayD, h4.y).n;
-                        else nrm = hit_normal(sc, prim, tri, h4.y, h4.z, h4.w);
-                        if (l.two_sided || dot(nrm, -rayD) > 0) Li = sp3(l.L[0], l.L[1], l.L[2]);
-                    }
+                    if (tri.light == lightNum) Li = area_light_le<true>(sc, sc.lights[tri.light], prim, tri, h4, o4, rayD);
                 } else if (sc.lights[lightNum].type == PG_LIGHT_INFINITE) Li = env_le(sc, sc.lights[lightNum], rayD);
                 vs.misLi[slot] = make_float4(Li.r, Li.g, Li.b, 0);
             } else if (surface) {
@@ -3371,23 +3419,17 @@ __global__ __launch_bounds__(PG_BLOCK) void k_through(DScene sc, PathState st, V
                 through_point<true>(sc, ri, o4, rayD, h4, prim, tri, p, pError, n);
                 int mIn, mOut;
                 prim_interface(sc, prim, med, mIn, mOut);
-                V3 origin, d;
-                float tMax;
-                if (KIND == 0) {
+                V3 d = rayD;
+                if (KIND == 0) {  // on towards the light sample the vertex kept
                     const float4 a = vs.p1[0][slot], b = vs.p1[1][slot], c = vs.p1[2][slot];
-                    const V3 lp = mk(a.x, a.y, a.z), lpe = mk(b.x, b.y, b.z), ln = mk(c.x, c.y, c.z);
-                    origin = offset_ray_origin(p, pError, n, lp - p);  // interaction.h:73-78
-                    const V3 target = offset_ray_origin(lp, lpe, ln, origin - lp);
-                    d = target - origin;
-                    tMax = 1 - PG_SHADOW_EPS;
+                    const LightSample ls = {mk(a.x, a.y, a.z), mk(c.x, c.y, c.z), mk(b.x, b.y, b.z)};
+                    d = shadow_ray_to(p, pError, n, ls, slot, no, nd);
                 } else {
-                    origin = offset_ray_origin(p, pError, n, rayD);
-                    d = rayD;
-                    tMax = PG_INF;
+                    const V3 origin = offset_ray_origin(p, pError, n, rayD);
+                    no = make_float4(origin.x, origin.y, origin.z, PG_INF);
+                    nd = make_float4(d.x, d.y, d.z, __int_as_float(slot));
                 }
                 med = dot(d, n) > 0 ? mOut : mIn;
-                no = make_float4(origin.x, origin.y, origin.z, tMax);
-                nd = make_float4(d.x, d.y, d.z, __int_as_float(slot));
                 push = true;
             }
         }
@@ -3637,53 +3679,12 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
         const int prim = __float_as_int(h4.x);
         int inst = sss.hitInst[slot], inst2;
         nest_decode(sc, inst, inst2);  // (DScene::hasNest: the chosen hit may lie under two transforms)
-        const float *i2wIn = nullptr, *w2iIn = nullptr;  // the inner TransformedPrimitive's, as below
-        bool innerIdentity = true;
-        if (inst2 >= 0) {
-            const PgInstance &in2 = sc.instances[inst2];
-            const bool moving2 = in2.animated && sss.hitXf;
-            const float *xf2 = sss.hitXf + (size_t)PG_XF_STRIDE * ((size_t)sss.hitXfNest + slot);
-            i2wIn = moving2 ? xf2 : in2.i2w;
-            w2iIn = moving2 ? xf2 + 16 : in2.w2i;
-            innerIdentity = moving2 ? xf2[32] != 0.f : in2.identity != 0;
-        }
-        // the chosen hit's instance transform: the instance's own, or -- a moving instance -- what k_sss_probe kept of k_trace's interpolation
-        const float *i2w = nullptr, *w2i = nullptr;
-        bool instIdentity = true;
-        if (inst >= 0) {
-            const PgInstance &in = sc.instances[inst];
-            const bool moving = in.animated && sss.hitXf;
-            i2w = moving ? sss.hitXf + (size_t)PG_XF_STRIDE * slot : in.i2w;
-            w2i = moving ? sss.hitXf + (size_t)PG_XF_STRIDE * slot + 16 : in.w2i;
-            instIdentity = moving ? sss.hitXf[(size_t)PG_XF_STRIDE * slot + 32] != 0.f : in.identity != 0;
-        }
+        // (a moving instance's matrices: what k_sss_probe kept by slot of k_trace's interpolation for the probe ray that found the hit)
+        const InstXf outer = {sc.instances, sss.hitXf, 0, inst, slot}, inner = {sc.instances, sss.hitXf, sss.hitXfNest, inst2, slot};
         const V3 rayD = mk(d4.x, d4.y, d4.z);
         const Tri tri = load_tri(sc, prim);
-        Isect is;
-        V3 shapeRayD = rayD;
-        if (inst >= 0) shapeRayD = m4_vec(w2i, rayD);
-        if (inst2 >= 0) shapeRayD = m4_vec(w2iIn, shapeRayD);
-        if (tri.flags & PG_PRIM_SPHERE) {
-            V3 shapeRayO = mk(o4.x, o4.y, o4.z);
-            if (inst >= 0) { float dt; instance_ray(w2i, shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
-            if (inst2 >= 0) { float dt; instance_ray(w2iIn, shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
-            const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
-            is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
-            is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
-        } else is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shapeRayD);
-        if (inst2 >= 0 && !innerIdentity) isect_to_world(i2wIn, w2iIn, is);  // (the inner transform first)
-        if (inst >= 0 && !instIdentity) {  // InterpolatedPrimToWorld(*isect), transform.cpp:262-297
-            Isect w;
-            w.p = m4_point_err2(i2w, is.p, is.pError, w.pError);
-            w.n = normalize(m4_normal(w2i, is.n));
-            w.wo = normalize(m4_vec(i2w, is.wo));
-            w.sdpdu = m4_vec(i2w, is.sdpdu);
-            w.sdpdv = m4_vec(i2w, is.sdpdv);
-            w.sdndu = m4_normal(w2i, is.sdndu); w.sdndv = m4_normal(w2i, is.sdndv);
-            w.ns = normalize(m4_normal(w2i, is.ns));
-            if (dot(w.ns, w.n) < 0.f) w.ns = -w.ns;
-            is = w;
-        }
+        QuadricUv quv;
+        Isect is = hit_isect(sc, outer, inner, o4, rayD, h4, prim, tri, quv);
         // ---- Sp(pi) = Sr(|po - pi|) and Pdf_Sp(pi) / nFound (bssrdf.cpp:322-327), beta *= S / pdf (path.cpp:158)
         const float4 po4 = sss.po[slot], f0 = sss.frame[0][slot], f1 = sss.frame[1][slot], f2 = sss.frame[2][slot];
         const V3 poP = mk(po4.x, po4.y, po4.z);
@@ -3734,11 +3735,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
                         const Spec f = ad_f(ab, is.wo, wi, nonSpecular) * absdot(wi, ab.ns);
                         scatteringPdf = ad_pdf(ab, is.wo, wi, nonSpecular);
                         if (!is_black(f)) {
-                            const V3 origin = offset_ray_origin(is.p, is.pError, is.n, ls.p - is.p);
-                            const V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
-                            const V3 shD = target - origin;
-                            s_ray[1][0][tid] = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
-                            s_ray[1][1][tid] = make_float4(shD.x, shD.y, shD.z, __int_as_float(slot));
+                            [[maybe_unused]] const V3 shD = shadow_ray_to(is.p, is.pError, is.n, ls, slot, s_ray[1][0][tid], s_ray[1][1][tid]);
                             pushShadow = true;
                             const bool isDelta = PG_LIGHT_IS_DELTA(lh.type);
                             if constexpr (VOL) {
@@ -3766,11 +3763,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
                         misCand = true;
                         spawn_ray(is, wi2, misRo);
                         misWi = wi2; misF = fm; misPdf = sPdf2;
-                        misLightPrim = lh.type == PG_LIGHT_INFINITE ? -1 - lightNum : lh.prim; misLightArea = lh.area;
-                        if (lh.type == PG_LIGHT_AREA && (lh.tri.flags & PG_PRIM_SPHERE)) {
-                            const PgSphere &lsph = sc.spheres[__float_as_int(lh.tri.p0.x)];
-                            misInside = lsph.shape != PG_SHAPE_SPHERE || sphere_ref_inside(lsph, is.p, is.pError, is.n);
-                        }
+                        misLightArea = lh.area;
+                        mis_light_of(sc, lh, lightNum, is.p, is.pError, is.n, misLightPrim, misInside);
                     }
                     pdLight.w = lightSelPdf;
                     st.pdLight[pdi] = pdLight;
@@ -3779,30 +3773,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
             }
             int misMedium = 0;
             if (VOL && misCand) misMedium = dot(misWi, is.n) > 0 ? mOut : mIn;
-            if (misCand) {  // light.Pdf_Li(pi, wi) of the BSDF-sampled direction (integrator.cpp:175-178): as at the end of k_shade
-                float lightPdf2 = 0;
-                if (misLightPrim < 0) lightPdf2 = env_pdf_li(sc, sc.lights[-1 - misLightPrim], misWi);
-                const Tri lt = load_tri(sc, misLightPrim < 0 ? 0 : misLightPrim);
-                float t, lb0, lb1, lb2;
-                if (misLightPrim >= 0 && (lt.flags & PG_PRIM_SPHERE)) {
-                    const PgSphere &lsp = sc.spheres[__float_as_int(lt.p0.x)];
-                    if (!misInside) lightPdf2 = sphere_cone_pdf(lsp, is.p);
-                    else if (sphere_test(lsp, misRo, misWi, PG_INF, t)) {
-                        const SphereHit sh = sphere_interaction(lsp, misRo, misWi, t);
-                        float pdf2 = lensq(is.p - sh.p) / (absdot(sh.n, -misWi) * misLightArea);
-                        if (isinf(pdf2)) pdf2 = 0.f;
-                        lightPdf2 = pdf2;
-                    }
-                } else {
-                    if (misLightPrim >= 0) ++nLightTests;
-                    if (misLightPrim >= 0 && tri_test(lt.p0, lt.p1, lt.p2, misRo, misWi, PG_INF, t, lb0, lb1, lb2) && !(lt.flags & PG_TRI_BOGUS)) {
-                        const V3 lp = lt.p0 * lb0 + lt.p1 * lb1 + lt.p2 * lb2;
-                        const V3 ln = normalize(cross(lt.p0 - lt.p2, lt.p1 - lt.p2));
-                        float pdf2 = lensq(is.p - lp) / (absdot(ln, -misWi) * misLightArea);
-                        if (isinf(pdf2)) pdf2 = 0.f;
-                        lightPdf2 = pdf2;
-                    }
-                }
+            if (misCand) {
+                const float lightPdf2 = mis_light_pdf<true>(sc, misLightPrim, misLightArea, misInside, is.p, misRo, misWi, nLightTests);
                 if (lightPdf2 != 0) {
                     s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
                     s_ray[2][1][tid] = make_float4(misWi.x, misWi.y, misWi.z, __int_as_float(slot));

@@ -24,11 +24,11 @@ def emulated(tmp_path_factory):
 
 
 def test_direct_lighting_on_the_emulated_device(emulated):
-    """Scenes a, b, c, d, f, h, i and j: the reference's image in every bit and its ray counters; then the refusals through the entry point."""
+    """Scenes a, b, c, d, f, h, i, j, o, p and q: the reference's image in every bit and its ray counters; then the refusals through the entry point."""
     env = dict(os.environ, PBRT_GPU_LIB=emulated, PBRT_EMULATED_DEVICE="1")
-    select = "(bit_for_bit and (a_defaults or b_four or c_three or d_one or f_textures or h_specular or i_depth or j_null)) or refused"
+    select = "(bit_for_bit and (a_defaults or b_four or c_three or d_one or f_textures or h_specular or i_depth or j_null or o_sphere or p_sphere or q_instances)) or refused"
     p = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_directlighting.py", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "-k", select], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=1800)
     tail = p.stdout[-3000:] + p.stderr[-1500:]
     assert p.returncode == 0, tail
-    assert "9 passed" in tail and "failed" not in tail, tail
+    assert "12 passed" in tail and "failed" not in tail, tail

@@ -32,7 +32,7 @@ def image_of(scene, rd, film, strays):
 
 
 def test_fixtures_exist():
-    assert len(NAMES) == 17 and all(os.path.exists(os.path.join(DIRECT, n + ".pfm")) for n in NAMES)
+    assert len(NAMES) == 20 and all(os.path.exists(os.path.join(DIRECT, n + ".pfm")) for n in NAMES)
 
 
 @pytest.mark.parametrize("name", NAMES)

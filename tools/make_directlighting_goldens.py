@@ -81,8 +81,24 @@ def scenes():
     n = direct(BASE, '"string strategy" "one"', 24, 24)
     n = n.replace('Camera "perspective" "float fov" [ 39.3 ]', 'Camera "realistic" "string lensfile" "../realistic/lens_singlet.dat" "float focusdistance" [ 800 ] "float aperturediameter" [ 8 ]')
     out["n_realistic_one"] = n.replace('"string filename"', '"float diagonal" [ 35 ] "string filename"')
+    # a sphere as the area light and hits under an object instance: the interaction, Sphere::Sample / Sphere::Pdf and InterpolatedPrimToWorld at k_direct's vertices
+    quad = ('  Shape "trianglemesh" "integer indices" [ 0 1 2 0 2 3 ]\n'
+            '    "point P" [ 343 548.7 227   343 548.7 332   213 548.7 332   213 548.7 227 ]\n')
+    # (o) every shaded point lies outside the sphere: the cone of Sphere::Sample (sphere.cpp:243-290) and of Sphere::Pdf (sphere.cpp:292-305)
+    o = material(direct(BASE, '"string strategy" "all"', area='"integer samples" [ 2 ]'), quad, '  Translate 278 440 280\n  Shape "sphere" "float radius" [ 45 ]\n')
+    out["o_sphere_light_outside"] = o
+    # (p) every shaded point lies inside the sphere (tests/golden/sphere_enclosing.pbrt): Sphere::Pdf falls back to Shape::Pdf, which intersects the sphere (shape.cpp:72-87)
+    out["p_sphere_light_enclosing"] = material(direct(BASE, '"string strategy" "one"'), "# light\n", 'AttributeBegin\n  Translate 278 273 100\n  ReverseOrientation\n'
+                                               '  AreaLightSource "diffuse" "rgb L" [ 0.5 0.6 0.8 ]\n  Shape "sphere" "float radius" [ 1500 ]\nAttributeEnd\n# light\n')
+    # (q) the boxes and a sphere as one object, placed twice under a rotation and a non-uniform scale: the instance-space ray and InterpolatedPrimToWorld (transform.cpp:262-297)
+    q = material(direct(BASE), "# short box\n", 'ObjectBegin "boxes"\n# short box\n')
+    q = material(q, "WorldEnd\n", 'AttributeBegin\n  Translate 186 225 168\n  Shape "sphere" "float radius" [ 60 ]\nAttributeEnd\nObjectEnd\n'
+                 'AttributeBegin\n  Translate 30 0 40\n  Rotate 12 0 1 0\n  Scale 0.5 0.8 0.45\n  ObjectInstance "boxes"\nAttributeEnd\n'
+                 'AttributeBegin\n  Translate 290 0 240\n  Rotate -25 0 1 0\n  Scale 0.45 0.6 0.5\n  ObjectInstance "boxes"\nAttributeEnd\nWorldEnd\n')
+    out["q_instances"] = q
     for name, text in out.items():
         assert 'Integrator "directlighting"' in text, name
+    assert "trianglemesh" not in o.split("# light")[1].split("AttributeEnd")[0] and out["p_sphere_light_enclosing"].count("AreaLightSource") == 2 and q.count("ObjectInstance") == 2
     assert "cropwindow" in out["k_gaussian_crop_bounds"] and 'Camera "realistic"' in out["n_realistic_one"] and "fov\" [ 60 ]" in out["e_five_kinds_of_light"]
     return out
 
