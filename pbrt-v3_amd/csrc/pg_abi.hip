@@ -74,6 +74,10 @@ struct PgScene {
     hipEvent_t evShaded = nullptr, evShadowed = nullptr;
     bool cullTripped = false;  // the last call raised k_trace's cull guard (checkCullGuard)
     bool overlapShadow = false;  // PG_OVERLAP_SHADOW=1: any-hit launch on a second stream beside the closest-hit launch (per-kernel times then overlap)
+    // PathIntegrator frames of scenes without BSSRDF materials: a vertex's direct lighting is added by the shading launch of the path's next vertex
+    // (QueueState::pend) and k_resolve runs over the listed vertices only.  PG_RESOLVE=pass: the full-queue k_resolve launch per bounce instead
+    bool resolveFused = true;
+    DeviceBuffer qsPend[2], pendList;  // QueueState::pend of the two main queues; PendJoin::list
     // test-path buffers
     DeviceBuffer tO, tD, tT, tPrim, tHit, tOcc, tCount;
     PgCounters counters;
@@ -223,6 +227,7 @@ int pg_scene_create(const PgSceneDesc *desc, PgScene **out) {
     HIP_TRY_S(hipEventCreateWithFlags(&s->evShaded, hipEventDisableTiming));
     HIP_TRY_S(hipEventCreateWithFlags(&s->evShadowed, hipEventDisableTiming));
     if (const char *e = getenv("PG_OVERLAP_SHADOW")) s->overlapShadow = atoi(e) != 0;
+    if (const char *e = getenv("PG_RESOLVE")) s->resolveFused = strcmp(e, "pass") != 0;
     HIP_TRY_S(s->cullGuard.alloc(sizeof(int) * 2 + 8 * sizeof(unsigned long long)));  // the guard word (+ the counters of the PG_TRACE_STATS experiment build)
     HIP_TRY_S(hipMemset(s->cullGuard.p, 0, s->cullGuard.bytes));
     HIP_TRY_S(s->lightTests.alloc(sizeof(unsigned long long) * PG_LIGHT_TEST_SHARDS * PG_LIGHT_TEST_STRIDE));
@@ -310,7 +315,7 @@ static int ensureWorkBuffers(PgScene *s, int capacity, size_t n) {
     if (s->d.sparseLights) HIP_TRY(s->retryList.alloc(n * sizeof(int)));
     // (scenes with moving instances: one float per entry behind `d`, the rays' times: PG_QUEUE_TIMES)
     for (int i = 0; i < 4; ++i) { HIP_TRY(s->qo[i].alloc(n * sizeof(float4))); HIP_TRY(s->qd[i].alloc(n * (sizeof(float4) + (s->d.hasMotion ? sizeof(float) : 0)))); }
-    HIP_TRY(s->counts.alloc(4 * PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));
+    HIP_TRY(s->counts.alloc(5 * PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));  // the four queues' counters, then PendJoin::listCounts
     // (grid media: a third part -- the transmittance rays must leave the main rays' hits alone for the second shading phase)
     const size_t hitParts = s->d.nGrids > 0 ? 3 : 2;
     HIP_TRY(s->hitsMain.alloc(hitParts * n * sizeof(float4)));
@@ -364,7 +369,7 @@ static int ensureVolBuffers(PgScene *s, int capacity, size_t n, VolState &vs, Ra
 // PathIntegrator, and VolPathIntegrator on scenes without BSSRDF materials or grid media (whose probe-chain / two-phase kernels find a
 // path's state by its slot): L / beta / meta (/ the ray's medium) in queue order beside each main queue.  (The kernels are compiled for one
 // or the other: k_shade's QSTATE.)
-static int ensureQueueState(PgScene *s, int capacity, size_t n, bool vol, PathState &ps) {
+static int ensureQueueState(PgScene *s, int capacity, size_t n, bool vol, bool direct, PathState &ps) {
     const bool volQ = vol && s->d.nBssrdfs == 0 && s->d.nGrids == 0;
     if (vol && !volQ) return PG_OK;
     if (s->qsCapacity < capacity) {
@@ -372,8 +377,13 @@ static int ensureQueueState(PgScene *s, int capacity, size_t n, bool vol, PathSt
         s->qsCapacity = capacity;
     }
     if (volQ && s->qsMedium[0].bytes < n * sizeof(int)) for (int i = 0; i < 2; ++i) HIP_TRY(s->qsMedium[i].alloc(n * sizeof(int)));
+    const bool pendQ = !vol && !direct && s->resolveFused && s->d.nBssrdfs == 0;  // (bouncesPath's frames)
+    if (pendQ && s->pendList.bytes < n * sizeof(int)) {
+        for (int i = 0; i < 2; ++i) HIP_TRY(s->qsPend[i].alloc(n * sizeof(float4)));
+        HIP_TRY(s->pendList.alloc(n * sizeof(int)));
+    }
     for (int i = 0; i < 2; ++i) { ps.qs[i].L = (float4 *)s->qsL[i].p; ps.qs[i].beta = (float4 *)s->qsBeta[i].p; ps.qs[i].meta = (int4 *)s->qsMeta[i].p;
-                                  ps.qs[i].medium = volQ ? (int *)s->qsMedium[i].p : nullptr; }
+                                  ps.qs[i].medium = volQ ? (int *)s->qsMedium[i].p : nullptr; ps.qs[i].pend = pendQ ? (float4 *)s->qsPend[i].p : nullptr; }
     return PG_OK;
 }
 // Subsurface scattering: per-slot state of the BSSRDF branch with its job queue, and in sssP the two probe queues
@@ -655,14 +665,18 @@ static int bouncesPath(FrameCtx &c, const std::function<void()> &generate, const
     if (int e = c.timer.run(0, stream, [&] { launch_closest(c.d, s->trace, q[cur], c.hits, nullptr, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
     ++c.closestLaunches;
     const SssState *sssArg = c.sssOn ? &c.sq : nullptr;
+    // (no QueueState::pend: PG_RESOLVE=pass, or BSSRDF materials, whose exit vertices k_sss_exit shades: k_resolve over the whole queue)
+    PendJoin pj = {(const int *)s->occluded.p, nullptr, nullptr, false};
+    if (c.ps.qs[0].pend && !c.sssOn) { pj.listCounts = c.counts + 4 * QSTRIDE; pj.list = (int *)s->pendList.p; }
     int iters = 0;
     for (int bounce = 0; bounce < c.lim.maxIters; ++bounce, ++iters) {
         const int nxt = cur ^ 1;
         HIP_TRY(hipMemsetAsync(c.counts + nxt * QSTRIDE, 0, QSTRIDE * sizeof(int), stream));
-        HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
+        HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, (pj.list ? 3 : 2) * QSTRIDE * sizeof(int), stream));  // (and the list of this bounce's launch)
         if (c.sssOn) HIP_TRY(hipMemsetAsync(c.sq.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
         c.rp.order = c.d.primClass ? (const int *)s->shadeOrder.p : nullptr;
-        auto shade = [&] { launch_shade(c.d, c.rp, c.ps, q[cur], c.hits, q[nxt], q[2], q[3], c.lightTests, stream, cur, sssArg); };
+        pj.first = bounce == 0;
+        auto shade = [&] { launch_shade(c.d, c.rp, c.ps, q[cur], c.hits, q[nxt], q[2], q[3], c.lightTests, stream, cur, sssArg, pj); };
         if (int e = c.timer.run(2, stream, [&] { launch_shade_order(c.d, q[cur], c.hits, (int *)s->shadeOrder.p, stream); shade(); })) return e;
         ++c.shadeLaunches; noteShading(c, c.d, false, sssArg != nullptr, false);
         if (int e = settleLightTables(c, shade)) return e;
@@ -685,7 +699,10 @@ static int bouncesPath(FrameCtx &c, const std::function<void()> &generate, const
             if (int e = c.timer.run(0, stream, [&] { launch_closest2(c.d, s->trace, q[nxt], q[3], c.hits, (int)c.nQueue, c.cnClosest, c.cursors, c.cullGuard, stream); })) return e;
             ++c.closestLaunches;
             if (overlap) HIP_TRY(hipStreamWaitEvent(stream, s->evShadowed, 0));
-            if (int e = c.timer.run(3, stream, [&] { launch_resolve(c.d, c.ps, q[cur], q[3], (const int *)s->occluded.p, c.hitsMis, stream, cur, c.lightTests); })) return e;
+            if (int e = c.timer.run(3, stream, [&] {
+                    if (pj.list) launch_resolve_list(c.d, c.ps, q[cur], q[3], pj, c.hitsMis, stream, cur, c.lightTests);
+                    else launch_resolve(c.d, c.ps, q[cur], q[3], (const int *)s->occluded.p, c.hitsMis, stream, cur, c.lightTests);
+                })) return e;
             ++c.resolveLaunches;
         }
         // log this bounce's queue sizes
@@ -848,7 +865,7 @@ static int setUpFrame(FrameCtx &c, int capacity) {
     c.nQueue = queueEntries(s, capacity);
     if (int e = ensureWorkBuffers(s, capacity, c.nQueue)) return e;
     if (c.vol) if (int e = ensureVolBuffers(s, capacity, c.nQueue, c.vs, c.vq)) return e;
-    if (int e = ensureQueueState(s, capacity, c.nQueue, c.vol, c.ps)) return e;
+    if (int e = ensureQueueState(s, capacity, c.nQueue, c.vol, c.direct != nullptr, c.ps)) return e;
     c.sssOn = s->d.nBssrdfs > 0;
     if (c.sssOn) if (int e = ensureSssBuffers(s, capacity, c.nQueue, c.sq, c.sssP)) return e;
     c.d = s->d;

@@ -217,7 +217,17 @@ struct QueueState {
     float4 *beta;  // (beta.rgb, pFilm.y)
     int4 *meta;    // as PathState::meta
     int *medium;   // volpath: the ray's medium (index + 1, 0 = none), as VolState::medium; nullptr under PathIntegrator
+    // PathIntegrator without BSSRDF materials: the direct lighting of the vertex BEFORE this entry's, which the shading launch that consumes the
+    // entry adds to L once the shadow ray is back -- (beta * ((0 + pdLight.rgb) / lightSelectPdf), code as int bits).  code >= 0: the shadow
+    // ray's position in its queue (added unless occluded[code]); -1: a light was chosen but no shadow ray left (one of totalPaths, zero
+    // radiance); -2: nothing to add, nothing to count.  nullptr: every vertex waits for the full-queue k_resolve (PG_RESOLVE=pass, volpath)
+    float4 *pend;
 };
+// What k_shade needs beside QueueState::pend to join a vertex's direct lighting without the full-queue resolve pass: the any-hit answers of the
+// previous bounce, and the list of this launch's vertices that still need k_resolve's arithmetic (a MIS ray left, or the path ends here):
+// their queue positions, appended by region like a queue's entries (listCounts: PG_REGIONS counters, PG_COUNT_STRIDE ints apart; region r owns
+// list[r * regionCap ..] with the queues' regionCap); k_resolve_list runs over them.  first: the launch over the camera rays (no entry carries a pend)
+struct PendJoin { const int *occluded; int *listCounts; int *list; bool first; };
 
 // Per-path state, indexed by slot.
 struct PathState {
@@ -431,7 +441,8 @@ inline int pg_shade_mode(const DScene &sc, const RenderParams &rp, bool vol, boo
     return (vol || sc.ext) ? 1 : 0;
 }
 void launch_shade(const DScene &sc, const RenderParams &rp, PathState st, RayQueue qin, const float4 *hits, RayQueue qnext,
-                  RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, hipStream_t s, int cur = 0, const SssState *sss = nullptr);
+                  RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, hipStream_t s, int cur = 0, const SssState *sss = nullptr,
+                  PendJoin pj = PendJoin{});  // pj.list == nullptr: pending terms for the full-queue launch_resolve, as under volpath
 // Subsurface scattering: one step of the probe chains (pass 1: count the hits on the material; pass 2: stop at the chosen one) over
 // the rays of qin (results at hits[i], instances at sc.hitInst[i]), continued rays to qout; then the exit vertices of the jobs of
 // sss.qjob: Pdf_Sp / Sr, direct lighting (shadow / MIS rays, pending terms at the job's queue index) and the next ray (appended to qnext)
@@ -440,6 +451,9 @@ void launch_sss_exit(const DScene &sc, const RenderParams &rp, PathState st, Sss
                      unsigned long long *lightTriTests, hipStream_t s, int nxt, bool vol, VolState vs, int phase = 0, float4 *exitVertex = nullptr);
 void launch_resolve(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis, const int *occluded, const float4 *misHits, hipStream_t s,
                     int cur, unsigned long long *stats = nullptr);
+// the same over the queue positions a launch_shade with a PendJoin listed (the grid strides over the device-side count)
+void launch_resolve_list(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis, PendJoin pj, const float4 *misHits, hipStream_t s,
+                         int cur, unsigned long long *stats);
 // VolPathIntegrator: the shading step with medium sampling (hitT = the hits' ray parameters), one step of the through rays of
 // `kind` (results of qin at hits[hitBase + i]; continued rays go to qout), and EstimateDirect's sums with transmittance
 // gridVertex / phase: scenes with a grid medium shade a vertex in two launches (phase 1, transmittance rays, resolve, phase 2); 0 = one pass

@@ -66,11 +66,11 @@ PG_DEV void block_push(const RayQueue *q, const bool *pred, int *pos, int bin0 =
         int total = 0;
 #pragma unroll
         for (int w = 0; w < NW; ++w) total += s_cnt[k][w];
-        static_assert(NQ <= 3, "block_push: at most three queues");
-        int *const c0 = q[0].counts, *const c1 = q[NQ > 1 ? 1 : 0].counts, *const c2 = q[NQ > 2 ? 2 : 0].counts;
-        const int cap0 = q[0].regionCap, cap1 = q[NQ > 1 ? 1 : 0].regionCap, cap2 = q[NQ > 2 ? 2 : 0].regionCap;
-        int *const cnt = k == 0 ? c0 : (k == 1 ? c1 : c2);
-        const int cap = k == 0 ? cap0 : (k == 1 ? cap1 : cap2);
+        static_assert(NQ <= 4, "block_push: at most four queues");
+        int *const c0 = q[0].counts, *const c1 = q[NQ > 1 ? 1 : 0].counts, *const c2 = q[NQ > 2 ? 2 : 0].counts, *const c3 = q[NQ > 3 ? 3 : 0].counts;
+        const int cap0 = q[0].regionCap, cap1 = q[NQ > 1 ? 1 : 0].regionCap, cap2 = q[NQ > 2 ? 2 : 0].regionCap, cap3 = q[NQ > 3 ? 3 : 0].regionCap;
+        int *const cnt = k == 0 ? c0 : (k == 1 ? c1 : (k == 2 ? c2 : c3));
+        const int cap = k == 0 ? cap0 : (k == 1 ? cap1 : (k == 2 ? cap2 : cap3));
         const int r = blockIdx.x & (PG_REGIONS - 1);
         s_base[k] = total ? r * cap + atomicAdd(&cnt[r * PG_COUNT_STRIDE], total) : 0;
     }
@@ -2454,7 +2454,7 @@ struct GridShade { float4 *vertex; int phase; };  // vertex[slot] = (medium inte
 template <int MODE, bool VOL, bool SSS = false, bool GRID = false>
 __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MODE == 1 || MODE == 3) && PG_SHADE_MIN_WAVES > 0) ? PG_SHADE_MIN_WAVES : (MODE == 2 ? (VOL ? PG_SHADE2V_WAVES : PG_SHADE2_WAVES) : 1))) void k_shade(DScene sc, RenderParams rp, PathState st, RayQueue qin, const float4 *__restrict__ hits,
                                                      RayQueue qnext, RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, VolState vs,
-                                                     const float *__restrict__ hitT, QueueState qsIn, QueueState qsOut, SssState sss, GridShade gsh) {
+                                                     const float *__restrict__ hitT, QueueState qsIn, QueueState qsOut, SssState sss, GridShade gsh, PendJoin pj) {
     // MODE 3: MODE 1 over the lists k_material left for the hits on materials with textured parameters (rp.matPre)
     constexpr bool EXT = MODE >= 1, TEX = MODE == 2, PRE = MODE == 3;
     static_assert(!PRE || (!SSS && !GRID), "materials evaluated ahead: the plain path / volpath kernels");
@@ -2466,6 +2466,9 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
     // path state and pending terms in queue order (see PathState); volpath: unless the scene has BSSRDF materials or a grid medium, whose
     // kernels (the probe chains, the two shading phases) find a path's state by its slot
     constexpr bool QSTATE = !VOL || (!SSS && !GRID);
+    // PathIntegrator without BSSRDF materials: a vertex's direct lighting travels to the path's next vertex as QueueState::pend (qsOut.pend != nullptr) and
+    // the previous vertex's is added here (qsIn.pend != nullptr); the launch lists the vertices that need k_resolve's arithmetic (PendJoin)
+    constexpr bool PENDQ = !VOL && !SSS;
     int i;
     if (rp.retryCount > 0) {  // second pass over the entries that waited for a light-distribution voxel (the list holds their POSITIONS in the shading order)
         const int j = blockIdx.x * PG_SHADE_BLOCK + threadIdx.x;
@@ -2515,7 +2518,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
         const PgRenderDesc &rd = rp.rd;
         float4 L4, B4;
         int4 meta;
-        if constexpr (QSTATE) { L4 = qsIn.L[i]; B4 = qsIn.beta[i]; meta = qsIn.meta[i]; }
+        float4 P4 = make_float4(0, 0, 0, __int_as_float(-2));
+        if constexpr (QSTATE) { L4 = qsIn.L[i]; B4 = qsIn.beta[i]; meta = qsIn.meta[i]; if constexpr (PENDQ) { if (qsIn.pend) P4 = qsIn.pend[i]; } }
         else { L4 = st.L[slot]; B4 = st.beta[slot]; meta = st.meta[slot]; }
         Spec L = sp3(L4.x, L4.y, L4.z), beta = sp3(B4.x, B4.y, B4.z);
         const uint64_t index = (uint64_t)(uint32_t)meta.x | ((uint64_t)(uint32_t)meta.y << 32);
@@ -2601,6 +2605,10 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
             }
             volDead = is_black(beta);  // volpath.cpp:78
         }
+        // PENDQ: whether the previous vertex's shadow ray was occluded -- every lane loads (entry 0 where nothing waits), without a branch and beside the
+        // triangle's loads: inside a branch the answer was a round trip of its own in front of them, +19 % on the kernel (profiles/shade_resolve_fused_ab.txt)
+        int pendOcc = 1;
+        if constexpr (PENDQ) { const int code = __float_as_int(P4.w); pendOcc = pj.occluded[code < 0 ? 0 : code]; }
         Tri tri;
         if (found) tri = load_tri(sc, prim);
         // the hit's material record, fetched as soon as its index is known (one round trip, overlapped with the interaction's
@@ -2628,6 +2636,15 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
             const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
             is = sphere_isect(sh);
             if (TEX) { sphU = sh.u; sphV = sh.v; sphDpdu = sh.dpdu; sphDpdv = sh.dpdv; }
+        }
+        // the previous vertex's direct lighting, now that its shadow ray is back: L += beta * Ld / lightPdf (path.cpp:122-126) BEFORE this vertex's Le, as
+        // the reference adds them; what k_resolve counts is noted for the end of the kernel (0x4000: one of totalPaths, 0x8000: of zeroRadiancePaths)
+        if constexpr (PENDQ) {
+            const int code = __float_as_int(P4.w);
+            const bool apply = code >= 0 && !pendOcc;
+            const Spec add = sp3(P4.x, P4.y, P4.z);
+            L = sp3(apply ? L.r + add.r : L.r, apply ? L.g + add.g : L.g, apply ? L.b + add.b : L.b);
+            s_stat[tid] = (unsigned short)(bounces | (code == -2 ? 0 : (apply && !is_black(add) ? 0x4000 : 0xc000)));
         }
         // path.cpp:91-102 emitted light at the vertex (volpath.cpp:103-110: only when no medium interaction was sampled)
         if (phaseB || (VOL && (volDead || inMedium))) {
@@ -2906,9 +2923,11 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                         }
                         // pending terms of this vertex, consumed by k_resolve (pdMis and the MIS weight follow below) -- stored HERE: held until after the
                         // BSDF sample below they were five registers at the kernel's peak (tools/reg_pressure.py: lbsdf_sample_f's microfacet terms)
+                        // (PENDQ with a pend to write: they wait in the MIS ray's LDS slot instead -- free until the end of the kernel, where most vertices
+                        // turn them into one float4 for the next queue entry and the listed ones store them for k_resolve_list)
                         pdLight.w = lightSelPdf;
-                        st.pdLight[pdi] = pdLight;
-                        st.pdBeta[pdi] = make_float4(beta.r, beta.g, beta.b, 0.f);
+                        if (PENDQ && qsOut.pend) { s_ray[2][0][tid] = pdLight; s_ray[2][1][tid] = make_float4(beta.r, beta.g, beta.b, 0.f); }
+                        else { st.pdLight[pdi] = pdLight; st.pdBeta[pdi] = make_float4(beta.r, beta.g, beta.b, 0.f); }
                         // (beta waits in LDS, where it goes at the end anyway, while the BSDF is sampled: three more registers off the same peak)
                         if constexpr (!TEX) { float *sb = reinterpret_cast<float *>(&s_state[1][tid]); sb[0] = beta.r; sb[1] = beta.g; sb[2] = beta.b; }
                         // BSDF sampling half of MIS (integrator.cpp:164-212): sample now, while the BSDF is live; the
@@ -3038,19 +3057,28 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
     if (misCand) {
         const float lightPdf2 = mis_light_pdf<EXT>(sc, misLightPrim, misLightArea, misInside, misP, misRo, misWi, nLightTests);
         if (lightPdf2 != 0) {
+            if (PENDQ && qsOut.pend) {  // a listed vertex: the terms staged in this slot go to k_resolve_list's records before the ray takes it
+                const float4 pb = s_ray[2][1][tid];
+                st.pdLight[pdi] = s_ray[2][0][tid];
+                st.pdBeta[pdi] = make_float4(pb.x, pb.y, pb.z, power_heuristic(1, misPdf, 1, lightPdf2));
+            } else st.pdBeta[pdi].w = power_heuristic(1, misPdf, 1, lightPdf2);
             s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
             s_ray[2][1][tid] = make_float4(misWi.x, misWi.y, misWi.z, __int_as_float(VOL ? pdi : slot));
             pushMis = true;
             st.pdMis[pdi] = make_float4(misF.r, misF.g, misF.b, misPdf);
-            st.pdBeta[pdi].w = power_heuristic(1, misPdf, 1, lightPdf2);
             if constexpr (VOL) vs.trAcc[1][pdi] = make_float4(1, 1, 1, __int_as_float(misMedium));
         }
     }
-    const RayQueue outQ[3] = {qnext, qshadow, qmis};
-    const bool outPred[3] = {pushNext, pushShadow, pushMis};
-    int outPos[3];
-    block_push<3, true, PG_SHADE_BLOCK>(outQ, outPred, outPos, nextBin);
+    // PENDQ: the vertices that need k_resolve's arithmetic (a MIS ray left, or the path ends here with something to add or count) append their positions to
+    // the launch's list as to a fourth queue: by region, in the block's one exchange
+    constexpr int NOUT = PENDQ ? 4 : 3;
+    const bool listed = PENDQ && qsOut.pend && valid && !deferred && (pushMis || (!pushNext && lightNum != -1));
+    const RayQueue outQ[4] = {qnext, qshadow, qmis, RayQueue{nullptr, nullptr, pj.listCounts, qin.regionCap}};
+    const bool outPred[4] = {pushNext, pushShadow, pushMis, listed};
+    int outPos[4];
+    block_push<NOUT, true, PG_SHADE_BLOCK>(outQ, outPred, outPos, nextBin);
     const int posNext = outPos[0], posShadow = outPos[1], posMis = outPos[2];
+    if (listed) pj.list[outPos[3]] = pdi;
     if (pushNext) { qnext.o[posNext] = s_ray[0][0][tid]; qnext.d[posNext] = s_ray[0][1][tid]; }
     if (pushShadow) { qshadow.o[posShadow] = s_ray[1][0][tid]; qshadow.d[posShadow] = s_ray[1][1][tid]; }
     if (pushMis) { qmis.o[posMis] = s_ray[2][0][tid]; qmis.d[posMis] = s_ray[2][1][tid]; }
@@ -3068,7 +3096,20 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                 qsOut.meta[posNext] = make_int4(__float_as_int(m4.x), __float_as_int(m4.y), __float_as_int(m4.z), __float_as_int(m4.w));
                 if constexpr (VOL) qsOut.medium[posNext] = newMed;
             } else st.L[slot] = s_state[0][tid];
-            st.pdInfo[pdi] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
+            if (PENDQ && qsOut.pend) {
+                if (pushNext) {
+                    float4 p4 = make_float4(0, 0, 0, __int_as_float(pushMis || lightNum == -1 ? -2 : -1));
+                    if (pushShadow && !pushMis) {  // k_resolve's operations in k_resolve's order, up to the one bit the any-hit launch still owes
+                        const float4 pl = s_ray[2][0][tid], pb = s_ray[2][1][tid];
+                        Spec Ld = sp(0);
+                        Ld = Ld + sp3(pl.x, pl.y, pl.z);
+                        const Spec add = sp3(pb.x, pb.y, pb.z) * (Ld / pl.w);
+                        p4 = make_float4(add.r, add.g, add.b, __int_as_float(posShadow));
+                    }
+                    qsOut.pend[posNext] = p4;
+                } else if (pushShadow && !pushMis) { st.pdLight[pdi] = s_ray[2][0][tid]; st.pdBeta[pdi] = s_ray[2][1][tid]; }
+                if (listed) st.pdInfo[pdi] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
+            } else st.pdInfo[pdi] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
         }
     } else if (valid && !deferred && !phaseB) st.pdInfo[slot] = make_int4(posShadow, posMis, lightNum, VOL ? __float_as_int(volWeight) : 0);
     if constexpr (SSS) {
@@ -3096,6 +3137,12 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
         if constexpr (GRID) ended = ended && (phaseA ? vertexKind == 0 : vertexKind != 0);
         const int code = valid ? s_stat[tid] : 0;
         stats_path_end(lightTriTests, ended, code & 0x3fff);
+        if constexpr (PENDQ) {  // what k_resolve counted for the previous vertex (a deferred vertex is shaded again by the retry launch)
+            if (qsIn.pend) {
+                stats_count(lightTriTests, PG_STAT_PATHS, !deferred && (code & 0x4000));
+                stats_count(lightTriTests, PG_STAT_PATHS_ZERO, !deferred && (code & 0x8000));
+            }
+        }
         if constexpr (VOL) {  // (a deferred vertex is shaded again by the retry launch)
             stats_count(lightTriTests, PG_STAT_VOLUME, !deferred && (code & 0x4000));
             stats_count(lightTriTests, PG_STAT_SURFACE, !deferred && (code & 0x8000));
@@ -3249,24 +3296,26 @@ void launch_shade_order_vol(const DScene &sc, const RenderParams &rp, PathState 
     else launch_shade_order(sc, qin, hits, order, s);
 }
 void launch_shade(const DScene &sc, const RenderParams &rp, PathState st, RayQueue qin, const float4 *hits, RayQueue qnext,
-                  RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, hipStream_t s, int cur, const SssState *sss) {
+                  RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, hipStream_t s, int cur, const SssState *sss, PendJoin pj) {
     int nblk = rp.retryCount > 0 ? (rp.retryCount + PG_SHADE_BLOCK - 1) / PG_SHADE_BLOCK : PG_REGIONS * (qin.regionCap / PG_SHADE_BLOCK);
     if (nblk == 0) return;
     const VolState vs = {};
     const float *noT = nullptr;
-    const QueueState qi = st.qs[cur], qo = st.qs[cur ^ 1];
+    QueueState qi = st.qs[cur], qo = st.qs[cur ^ 1];
+    if (!pj.list || sss) qi.pend = qo.pend = nullptr;  // every vertex's pending terms for the full-queue launch_resolve
+    if (pj.first) qi.pend = nullptr;                   // camera rays: nothing waits
     const SssState none = {};
     const GridShade gsh = {nullptr, 0};
     const int mode = pg_shade_mode(sc, rp, false, sss != nullptr, false);  // (the branches below are that function's cases)
     if (sss && sc.nBssrdfs > 0) {  // materials with a BSSRDF are BxDF-list materials: the general kernels
-        if (mode == 2) hipLaunchKernelGGL((k_shade<2, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, *sss, gsh);
-        else hipLaunchKernelGGL((k_shade<1, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, *sss, gsh);
+        if (mode == 2) hipLaunchKernelGGL((k_shade<2, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, *sss, gsh, pj);
+        else hipLaunchKernelGGL((k_shade<1, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, *sss, gsh, pj);
     } else if (mode == 3) {  // materials first (not again for the entries a sparse light table sent back: theirs are there)
         if (rp.retryCount == 0) launch_material(sc, rp, st, vs, qin, hits, noT, qi, false, s);
-        hipLaunchKernelGGL((k_shade<3, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh);
-    } else if (mode == 2) hipLaunchKernelGGL((k_shade<2, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh);
-    else if (mode == 1) hipLaunchKernelGGL((k_shade<1, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh);
-    else hipLaunchKernelGGL((k_shade<0, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh);
+        hipLaunchKernelGGL((k_shade<3, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh, pj);
+    } else if (mode == 2) hipLaunchKernelGGL((k_shade<2, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh, pj);
+    else if (mode == 1) hipLaunchKernelGGL((k_shade<1, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh, pj);
+    else hipLaunchKernelGGL((k_shade<0, false>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, noT, qi, qo, none, gsh, pj);
 }
 void launch_shade_vol(const DScene &sc, const RenderParams &rp, PathState st, VolState vs, RayQueue qin, const float4 *hits, const float *hitT,
                       RayQueue qnext, RayQueue qshadow, RayQueue qmis, unsigned long long *lightTriTests, hipStream_t s, const SssState *sss,
@@ -3279,16 +3328,16 @@ void launch_shade_vol(const DScene &sc, const RenderParams &rp, PathState st, Vo
     const GridShade gsh = {gridVertex, phase};
     const int mode = pg_shade_mode(sc, rp, true, sss != nullptr, phase != 0);
     if (phase != 0 && sss && sc.nBssrdfs > 0) {  // a grid medium AND BSSRDF materials: the second phase hands a path that goes on through a BSSRDF to the probe chains
-        if (mode == 2) hipLaunchKernelGGL((k_shade<2, true, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh);
-        else hipLaunchKernelGGL((k_shade<1, true, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh);
+        if (mode == 2) hipLaunchKernelGGL((k_shade<2, true, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh, PendJoin{});
+        else hipLaunchKernelGGL((k_shade<1, true, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh, PendJoin{});
     } else if (phase != 0) {  // a scene with a grid medium: the two-phase kernels
-        if (mode == 2) hipLaunchKernelGGL((k_shade<2, true, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, nosss, gsh);
-        else hipLaunchKernelGGL((k_shade<1, true, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, nosss, gsh);
+        if (mode == 2) hipLaunchKernelGGL((k_shade<2, true, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, nosss, gsh, PendJoin{});
+        else hipLaunchKernelGGL((k_shade<1, true, false, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, nosss, gsh, PendJoin{});
     } else if (sss && sc.nBssrdfs > 0) {
-        if (mode == 2) hipLaunchKernelGGL((k_shade<2, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh);
-        else hipLaunchKernelGGL((k_shade<1, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh);
+        if (mode == 2) hipLaunchKernelGGL((k_shade<2, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh, PendJoin{});
+        else hipLaunchKernelGGL((k_shade<1, true, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, none, none, *sss, gsh, PendJoin{});
     } else {
-#define PG_LAUNCH_VOL(MODE_) hipLaunchKernelGGL((k_shade<MODE_, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, qi, qo, nosss, gsh)
+#define PG_LAUNCH_VOL(MODE_) hipLaunchKernelGGL((k_shade<MODE_, true>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, vs, hitT, qi, qo, nosss, gsh, PendJoin{})
         if (mode == 3) {
             if (rp.retryCount == 0) launch_material(sc, rp, st, vs, qin, hits, hitT, qi, true, s);
             PG_LAUNCH_VOL(3);
@@ -3300,21 +3349,22 @@ void launch_shade_vol(const DScene &sc, const RenderParams &rp, PathState st, Vo
 
 // EstimateDirect's two "Add ... contribution" steps (integrator.cpp:143-161, 196-212) and
 // L += beta * Ld / lightPdf (integrator.cpp:104, path.cpp:122-126), once both rays are back.
+// One vertex: i = the queue position its pending terms lie at, or -1 (every lane of the block calls it: the statistics are counted per wave)
 template <bool EXT>
-__global__ __launch_bounds__(PG_BLOCK) void k_resolve(DScene sc, PathState st, RayQueue qin, RayQueue qmis, const int *__restrict__ occluded,
-                                                       const float4 *__restrict__ misHits, QueueState qsNext, unsigned long long *stats) {
+PG_DEV void resolve_entry(const DScene &sc, const PathState &st, int i, const RayQueue &qmis, const int *__restrict__ occluded,
+                          const float4 *__restrict__ misHits, const QueueState &qsNext, unsigned long long *stats) {
     // stats != nullptr: the launch over a bounce's main queue counts "Zero-radiance paths" (path.cpp:119-126): a vertex whose pdInfo names a light
     // (k_shade chose one: its BSDF has non-specular BxDFs) is one of totalPaths, and one of zeroRadiancePaths when its Ld comes out black
-    const int i = queue_item<>(qin);
     int4 info = make_int4(-1, -1, -1, 0);
     if (i >= 0) info = st.pdInfo[i];  // the pending terms lie in queue order (PathState)
     const bool counted = stats && i >= 0 && info.z != -1;
     bool black = true;
     if (i >= 0 && !(info.x < 0 && info.y < 0)) {  // (else Ld == 0: L += beta * 0 leaves L unchanged)
-    const float4 pl = st.pdLight[i], pm = st.pdMis[i], pb = st.pdBeta[i];
+    const float4 pl = st.pdLight[i], pb = st.pdBeta[i];
     Spec Ld = sp(0);
     if (info.x >= 0 && !occluded[info.x]) Ld = Ld + sp3(pl.x, pl.y, pl.z);
     if (info.y >= 0) {
+        const float4 pm = st.pdMis[i];  // (written for the vertices with a MIS ray only)
         const float4 h = misHits[info.y];
         const int prim = __float_as_int(h.x);
         if (prim >= 0) {
@@ -3343,6 +3393,32 @@ __global__ __launch_bounds__(PG_BLOCK) void k_resolve(DScene sc, PathState st, R
         stats_count(stats, PG_STAT_PATHS, counted);
         stats_count(stats, PG_STAT_PATHS_ZERO, counted && black);
     }
+}
+template <bool EXT>
+__global__ __launch_bounds__(PG_BLOCK) void k_resolve(DScene sc, PathState st, RayQueue qin, RayQueue qmis, const int *__restrict__ occluded,
+                                                       const float4 *__restrict__ misHits, QueueState qsNext, unsigned long long *stats) {
+    resolve_entry<EXT>(sc, st, queue_item<>(qin), qmis, occluded, misHits, qsNext, stats);
+}
+// The same over the vertices k_shade listed (PendJoin): the few with a MIS ray and the paths that ended with something to add or count.  Every other
+// vertex's direct lighting is added by the shading launch of the path's next vertex (QueueState::pend).
+template <bool EXT>
+__global__ __launch_bounds__(PG_BLOCK) void k_resolve_list(DScene sc, PathState st, RayQueue qmis, PendJoin pj, const float4 *__restrict__ misHits,
+                                                            QueueState qsNext, unsigned long long *stats, int regionCap) {
+    // block b strides over region b & 7 of the list (uniform over the block: resolve_entry counts per wave)
+    const int r = blockIdx.x & (PG_REGIONS - 1), n = pj.listCounts[r * PG_COUNT_STRIDE];
+    for (int base = (blockIdx.x >> 3) * PG_BLOCK; base < n; base += (gridDim.x >> 3) * PG_BLOCK) {
+        const int k = base + threadIdx.x;
+        resolve_entry<EXT>(sc, st, k < n ? pj.list[r * regionCap + k] : -1, qmis, pj.occluded, misHits, qsNext, stats);
+    }
+}
+void launch_resolve_list(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis, PendJoin pj, const float4 *misHits, hipStream_t s,
+                         int cur, unsigned long long *stats) {
+    // (the list is a few per cent of the queue: the blocks stride over their region instead of a grid for the queue's capacity that would mostly find nothing)
+    int nblk = PG_REGIONS * (qin.regionCap / PG_BLOCK);
+    if (nblk == 0) return;
+    if (nblk > PG_REGIONS * 256) nblk = PG_REGIONS * 256;
+    if (sc.ext) hipLaunchKernelGGL(k_resolve_list<true>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, st, qmis, pj, misHits, st.qs[cur ^ 1], stats, qin.regionCap);
+    else hipLaunchKernelGGL(k_resolve_list<false>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, st, qmis, pj, misHits, st.qs[cur ^ 1], stats, qin.regionCap);
 }
 void launch_resolve(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis, const int *occluded, const float4 *misHits, hipStream_t s,
                     int cur, unsigned long long *stats) {
