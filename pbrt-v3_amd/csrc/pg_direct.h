@@ -1,5 +1,5 @@
 // pg_direct.h -- the DirectLightingIntegrator's kernels (integrators/directlighting.cpp:62-95 without its specular bounces, which pg_render_direct
-// refuses).  Included at the end of pg_kernels.hip: everything here is built from that file's pieces -- the interaction (hit_isect), an emitter's
+// refuses).  Included at the end of pg_kernels.hip: everything here is built from the pieces that file includes -- the interaction (hit_isect), an emitter's
 // L (area_light_l), the BxDF lists and the material evaluators, the light sampling with its shadow ray (shadow_ray_to), light.Pdf_Li of the
 // BSDF-sampled direction (mis_light_pdf), the queue appends -- and k_resolve itself finishes every EstimateDirect.  None of them is restated here.
 //

@@ -321,7 +321,7 @@ __host__ __device__ inline void pg_pack_lobe_scales(const PgBxDF &b, float *q) {
 // of the 240 its slot took, profiles/r06k_*.)  stride = the planes the scene's longest list needs (PgScene: counted per material kind,
 // <= PG_MAX_BXDFS lobes, two records per lobe of a mix).  lobes == nullptr: the scene has no such material, or the buffers did not fit
 // -- the shading kernel then evaluates materials itself (k_shade<2, .>).
-struct MatPre { float4 *lobes; float4 *head; int stride; };  // lobes: packed 48-B records (LobeBsdfT, pg_kernels.hip), `stride` planes
+struct MatPre { float4 *lobes; float4 *head; int stride; };  // lobes: packed 48-B records (LobeBsdfT, pg_bxdf.h), `stride` planes
 
 #define PG_META_SPECULAR 0x10000
 #define PG_META_DONE 0x20000

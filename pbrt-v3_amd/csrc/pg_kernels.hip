@@ -12,6 +12,12 @@
 //
 // No MFMA: there is no dense contraction on this path; traversal is a
 // latency/bandwidth-bound gather over the node and triangle arrays.
+//
+// This file holds the kernels and their launch_* wrappers only.  The device functions they are built from live in headers, by subject:
+// pg_queue.h (queue append, statistics), pg_triangle.h (Tri, Isect, make_isect), pg_sampler.h, pg_camera.h, pg_bxdf.h (Bsdf, LobeBsdfT),
+// pg_material.h (MatEval), pg_light.h, pg_medium.h and pg_hit.h (the interaction of any hit; included last, it uses the others) -- beside
+// pg_device.h, pg_sphere.h, pg_texture.h, pg_motion.h, pg_bssrdf.h, pg_grid.h and pg_lens.h.  A helper of a single kernel (resolve_entry,
+// through_point, AdapterBsdf) stays with its kernel, and so do halton_batch and sample_discrete, below the includes.
 #include "pg_device.h"
 #include "pg_sphere.h"
 #include "pg_kernels.h"
@@ -20,203 +26,18 @@
 #include "pg_bssrdf.h"
 #include "pg_grid.h"
 #include "pg_lens.h"
+#include "pg_queue.h"
+#include "pg_triangle.h"
+#include "pg_sampler.h"
+#include "pg_camera.h"
+#include "pg_bxdf.h"
+#include "pg_material.h"
+#include "pg_light.h"
+#include "pg_medium.h"
+#include "pg_hit.h"
 
-#define PG_BLOCK 256
-// threads per block of the shading kernel: its blocks meet at two barriers around the queue append, so a block is only as fast
-// as its slowest wave -- measured on the GPU
-#ifndef PG_SHADE_BLOCK
-#define PG_SHADE_BLOCK 128
-#endif
-PG_DEV int lane_id() { return __lane_id(); }
-
-// Queue append, aggregated per block: every wave ballots its pushes, the block sums them through LDS and ONE lane per
-// queue does the atomicAdd on the block's region counter (region = blockIdx.x % 8); lanes get consecutive entries in
-// (wave, lane) order.  NQ queues are appended to in one exchange (two barriers).  Must be reached by all threads.
-// Consumers and producers share one mapping: block b owns entries [(b>>3)*256, +256) of region b & 7.
-// With BINNED, queue 0's entries are additionally grouped by `bin0` (0..7) inside the block's range: k_shade bins the next
-// bounce's rays by direction octant, so the 64 consecutive rays a traversal wave picks up come from one tile AND mostly
-// one octant (same near/far child order, same subtrees) instead of four to eight.
-template <int NQ, bool BINNED, int BLOCK = PG_BLOCK>
-PG_DEV void block_push(const RayQueue *q, const bool *pred, int *pos, int bin0 = 0) {
-    constexpr int NW = BLOCK / 64;
-    __shared__ int s_cnt[NQ][NW];
-    __shared__ int s_base[NQ];
-    __shared__ int s_bin[BINNED ? 8 : 1][NW];
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    unsigned long long mask[NQ];
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-        mask[k] = __ballot(pred[k]);
-        if (lane == 0) s_cnt[k][wave] = __popcll(mask[k]);
-    }
-    unsigned long long binMask = 0;
-    if (BINNED) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long m = __ballot(pred[0] && bin0 == b);
-            if (lane == 0) s_bin[b][wave] = __popcll(m);
-            if (bin0 == b) binMask = m;
-        }
-    }
-    __syncthreads();
-    // lanes 0 .. NQ-1 reserve the NQ queues' entries with ONE atomic instruction (one round trip to the counters instead of
-    // NQ dependent ones); the queue's fields are picked by compare-and-select on named copies so that they stay in registers
-    if (threadIdx.x < NQ) {
-        const int k = threadIdx.x;
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) total += s_cnt[k][w];
-        static_assert(NQ <= 4, "block_push: at most four queues");
-        int *const c0 = q[0].counts, *const c1 = q[NQ > 1 ? 1 : 0].counts, *const c2 = q[NQ > 2 ? 2 : 0].counts, *const c3 = q[NQ > 3 ? 3 : 0].counts;
-        const int cap0 = q[0].regionCap, cap1 = q[NQ > 1 ? 1 : 0].regionCap, cap2 = q[NQ > 2 ? 2 : 0].regionCap, cap3 = q[NQ > 3 ? 3 : 0].regionCap;
-        int *const cnt = k == 0 ? c0 : (k == 1 ? c1 : (k == 2 ? c2 : c3));
-        const int cap = k == 0 ? cap0 : (k == 1 ? cap1 : (k == 2 ? cap2 : cap3));
-        const int r = blockIdx.x & (PG_REGIONS - 1);
-        s_base[k] = total ? r * cap + atomicAdd(&cnt[r * PG_COUNT_STRIDE], total) : 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-        int off = s_base[k];
-        if (BINNED && k == 0) {
-            for (int b = 0; b < 8; ++b)
-                for (int w = 0; w < NW; ++w)
-                    if (b < bin0 || (b == bin0 && w < wave)) off += s_bin[b][w];
-            pos[k] = pred[k] ? off + __popcll(binMask & ((1ull << lane) - 1ull)) : -1;
-        } else {
-            for (int w = 0; w < wave; ++w) off += s_cnt[k][w];
-            pos[k] = pred[k] ? off + __popcll(mask[k] & ((1ull << lane) - 1ull)) : -1;
-        }
-    }
-}
-// The queue entry this thread consumes (or -1): block b walks region b & 7.
-template <int BLOCK = PG_BLOCK>
-PG_DEV int queue_item(const RayQueue &q) {
-    const int r = blockIdx.x & (PG_REGIONS - 1);
-    const int j = (blockIdx.x >> 3) * BLOCK + threadIdx.x;
-    return j < q.counts[r * PG_COUNT_STRIDE] ? r * q.regionCap + j : -1;
-}
-
-// A shading thread's POSITION in its launch's order (the index queue_item gave it, before RenderParams::order maps it to an entry; a
-// retry launch reads it back from the retry list): recomputed from the block and thread indices where it is needed, not kept in a register.
-PG_DEV int shade_position(const RenderParams &rp, const RayQueue &q) {
-    if (rp.retryCount > 0) return rp.retryList[blockIdx.x * PG_SHADE_BLOCK + threadIdx.x];
-    return (blockIdx.x & (PG_REGIONS - 1)) * q.regionCap + (blockIdx.x >> 3) * PG_SHADE_BLOCK + threadIdx.x;
-}
-
-PG_DEV unsigned long long wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// ReportValue(pathLength, bounces) of the Li calls that end in this wave (path.cpp:186, volpath.cpp:187): every lane of the block calls it
-PG_DEV void stats_path_end(unsigned long long *shards, bool ended, int len) {
-    const unsigned long long m = __ballot(ended);
-    if (m == 0) return;
-    const unsigned long long sum = wave_sum(ended ? (unsigned long long)len : 0ull);
-    int mn = ended ? len : 0xffff, mx = ended ? len : -1;
-    for (int off = 32; off > 0; off >>= 1) { const int a = __shfl_down(mn, off), b = __shfl_down(mx, off); mn = a < mn ? a : mn; mx = b > mx ? b : mx; }
-    if (lane_id() == 0) {
-        unsigned long long *sh = shards + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE;
-        atomicAdd(sh + PG_STAT_LEN_SUM, sum); atomicAdd(sh + PG_STAT_LEN_COUNT, (unsigned long long)__popcll(m));
-        atomicMax(sh + PG_STAT_LEN_MINC, (unsigned long long)(0xffff - mn)); atomicMax(sh + PG_STAT_LEN_MAXP, (unsigned long long)(mx + 1));
-    }
-}
-// a counter of the same shards raised by the number of lanes for which `pred` holds
-PG_DEV void stats_count(unsigned long long *shards, int word, bool pred) {  // (the lanes that are active call it: the first of them for which pred holds adds)
-    const unsigned long long m = __ballot(pred);
-    if (m != 0 && lane_id() == __ffsll(m) - 1) atomicAdd(shards + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE + word, (unsigned long long)__popcll(m));
-}
-
-struct Tri { V3 p0, p1, p2; uint32_t flags; int material, light; };
-PG_DEV Tri load_tri(const DScene &sc, int prim) {
-    float4 a = sc.tris[PG_TRI_STRIDE * prim], b = sc.tris[PG_TRI_STRIDE * prim + 1], c = sc.tris[PG_TRI_STRIDE * prim + 2];
-    Tri t;
-    t.p0 = mk(a.x, a.y, a.z); t.p1 = mk(b.x, b.y, b.z); t.p2 = mk(c.x, c.y, c.z);
-    t.flags = __float_as_uint(a.w); t.material = __float_as_int(b.w); t.light = __float_as_int(c.w);
-    return t;
-}
-
-// ===========================================================================
-// Sampler
-// ===========================================================================
-PG_DEV uint64_t inverse_radical_inverse(uint32_t base, uint64_t inverse, int nDigits) {  // lowdiscrepancy.h:80-91
-    uint64_t index = 0;
-    for (int i = 0; i < nDigits; ++i) {
-        uint64_t digit = inverse % base;
-        inverse /= base;
-        index = index * base + digit;
-    }
-    return index;
-}
-PG_DEV int pmod(int a, int b) { int r = a - (a / b) * b; return (r < 0) ? r + b : r; }  // pbrt.h:314-317
-
-// HaltonSampler::GetIndexForSample, halton.cpp:96-117
-PG_DEV uint64_t halton_index(const PgRenderDesc &rd, int px, int py, uint64_t sampleNum) {
-    uint64_t offsetForCurrentPixel = 0;
-    if (rd.sample_stride > 1) {
-        int pm0 = pmod(px, 128), pm1 = pmod(py, 128);
-        uint64_t dimOffset0 = inverse_radical_inverse(2, pm0, rd.base_exponents[0]);
-        uint64_t dimOffset1 = inverse_radical_inverse(3, pm1, rd.base_exponents[1]);
-        offsetForCurrentPixel += dimOffset0 * (uint64_t)(rd.sample_stride / rd.base_scales[0]) * (uint64_t)rd.mult_inverse[0];
-        offsetForCurrentPixel += dimOffset1 * (uint64_t)(rd.sample_stride / rd.base_scales[1]) * (uint64_t)rd.mult_inverse[1];
-        offsetForCurrentPixel %= (uint64_t)rd.sample_stride;
-    }
-    return offsetForCurrentPixel + sampleNum * (uint64_t)rd.sample_stride;
-}
-// HaltonSampler::SampleDimension, halton.cpp:119-127
-// SobolSampler (samplers/sobol.cpp:41-59): SobolIntervalToIndex and SobolSampleFloat, lowdiscrepancy.h:229-273
-PG_DEV uint64_t sobol_interval_to_index(const DScene &sc, uint32_t m, uint64_t frame, int px, int py) {
-    if (m == 0) return 0;
-    const uint32_t m2 = m << 1;
-    uint64_t index = frame << m2;
-    uint64_t delta = 0;
-    for (int c = 0; frame; frame >>= 1, ++c)
-        if (frame & 1) delta ^= sc.vdcSobol[(m - 1) * 52 + c];
-    uint64_t b = (((uint64_t)((uint32_t)px) << m) | ((uint32_t)py)) ^ delta;
-    for (int c = 0; b; b >>= 1, ++c)
-        if (b & 1) index ^= sc.vdcSobolInv[(m - 1) * 52 + c];
-    return index;
-}
-PG_DEV float sobol_sample(const DScene &sc, uint64_t a, int dim) {
-    if (dim > 1023) dim = 1023;  // NumSobolDimensions; the reference aborts beyond (sobol.cpp:47-50)
-    uint32_t v = 0;
-    for (int i = dim * 52; a != 0; a >>= 1, i++)
-        if (a & 1) v ^= sc.sobolMatrices[i];
-    return pmin(v * 0x1p-32f, PG_ONE_MINUS_EPS);
-}
-// GlobalSampler::GetIndexForSample of the configured sampler (halton.cpp:96-117, sobol.cpp:41-44)
-PG_DEV uint64_t sampler_index(const DScene &sc, const PgRenderDesc &rd, int px, int py, uint64_t sampleNum) {
-    if (rd.sampler == 1) return sobol_interval_to_index(sc, (uint32_t)rd.sobol_log2_resolution, sampleNum, px - rd.sample_bounds[0], py - rd.sample_bounds[1]);
-    return halton_index(rd, px, py, sampleNum);
-}
-// SampleDimension of the configured sampler for any dimension >= 2 (dimensions 0 and 1, the film position, are drawn by
-// k_generate alone: SobolSampler remaps them with the current pixel, sobol.cpp:53-56)
-PG_DEV float halton_sample(const DScene &sc, const PgRenderDesc &rd, uint64_t index, int dim) {
-    if (rd.sampler == 1) return sobol_sample(sc, index, dim);
-    if (rd.sample_at_pixel_center && (dim == 0 || dim == 1)) return 0.5f;
-    if (dim == 0) return radical_inverse_base2(index >> rd.base_exponents[0]);
-    if (dim == 1) return radical_inverse(3, index / (uint64_t)rd.base_scales[1]);
-    if (dim >= sc.nPermDims) dim = sc.nPermDims - 1;  // host sizes the table from maxdepth; halton.h:71-76 aborts here
-    if ((index >> 32) != 0) return scrambled_radical_inverse((uint32_t)sc.primes[dim], sc.perms + sc.permSums[dim], index);
-    // 32-bit index: scrambled_radical_inverse's loop with the division done by multiplication (DScene::haltonDims)
-    const int4 hd = sc.haltonDims[2 * dim], hc = sc.haltonDims[2 * dim + 1];
-    const uint32_t base = (uint32_t)hd.x, mul = (uint32_t)hd.z, sh = (uint32_t)hd.w - 1u;
-    const uint16_t *perm = sc.perms + hd.y;
-    const float invBase = __int_as_float(hc.x);  // 1.f / (float)base
-    uint64_t reversedDigits = 0;
-    float invBaseN = 1;
-    uint32_t a32 = (uint32_t)index;
-    while (a32) {
-        const uint32_t t = __umulhi(mul, a32);
-        const uint32_t next = (t + ((a32 - t) >> 1)) >> sh;
-        reversedDigits = reversedDigits * base + perm[a32 - next * base];
-        invBaseN *= invBase;
-        a32 = next;
-    }
-    return pmin(invBaseN * ((float)reversedDigits + __int_as_float(hc.y) /* invBase * perm[0] / (1 - invBase) */), PG_ONE_MINUS_EPS);
-}
-
+// ---- the two device functions that stay here: each holds an empty `asm volatile` register-scheduling barrier, which the emulated-device
+// build (tests/emu/build_emulated.py) drops from this file by text, and only the kernels below call them ----------------------------
 // The N Halton dimensions dim0 .. dim0+N-1 of one sample index at once (HaltonSampler::SampleDimension for each, halton.cpp:119-127
 // + ScrambledRadicalInverse, lowdiscrepancy.cpp:405-424): the digit loops of the N dimensions run side by side, so the N
 // permutation-table loads of a digit position are in flight together and the wave waits once per digit position instead of
@@ -266,95 +87,42 @@ PG_DEV void halton_batch(const DScene &sc, uint32_t a0, int dim0, float *out) {
     for (int j = 0; j < N; ++j)
         out[j] = pmin(invBaseN[j] * ((float)rev[j] + tail[j]), PG_ONE_MINUS_EPS);
 }
+// Distribution1D::SampleDiscrete, sampling.h:90-100 + FindInterval pbrt.h:403-415
+PG_DEV int sample_discrete(const float *tab, int n, float u, float &pdf) {
+    if (n <= 3) {
+        // a table of at most 8 floats (func[n], cdf[n+1], funcInt) is fetched in ONE round trip and searched in registers; the
+        // general path below meets it with three or four dependent loads (funcInt, the cdf entries of the search, func)
+        float row[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) row[k] = k < 2 * n + 2 ? tab[k] : 0.f;
+        asm volatile("" : "+v"(row[0]), "+v"(row[1]), "+v"(row[2]), "+v"(row[3]), "+v"(row[4]), "+v"(row[5]), "+v"(row[6]), "+v"(row[7]));
+        auto at = [&](int k) { return k == 0 ? row[0] : (k == 1 ? row[1] : (k == 2 ? row[2] : (k == 3 ? row[3] : (k == 4 ? row[4] : (k == 5 ? row[5] : (k == 6 ? row[6] : row[7])))))); };
+        const float funcInt = at(2 * n + 1);
+        int size = n + 1, first = 0, len = size;
+        while (len > 0) {
+            int half = len >> 1, middle = first + half;
+            if (at(n + middle) <= u) { first = middle + 1; len -= half + 1; }
+            else len = half;
+        }
+        int offset = first - 1;
+        offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
+        pdf = (funcInt > 0) ? at(offset) / (funcInt * n) : 0;
+        return offset;
+    }
+    const float *func = tab, *cdf = tab + n;
+    float funcInt = tab[2 * n + 1];
+    int size = n + 1, first = 0, len = size;
+    while (len > 0) {
+        int half = len >> 1, middle = first + half;
+        if (cdf[middle] <= u) { first = middle + 1; len -= half + 1; }
+        else len = half;
+    }
+    int offset = first - 1;
+    offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
+    pdf = (funcInt > 0) ? func[offset] / (funcInt * n) : 0;
+    return offset;
+}
 
-// ---- the samplers that draw from one RNG stream per tile (RandomSampler; the PixelSamplers, sampler.cpp:100-134) ------------
-PG_DEV uint32_t rng_u32(TileSamplerState &t) {  // RNG::UniformUInt32, rng.h:137-143
-    const unsigned long long oldstate = t.state;
-    ++t.draws;
-    t.state = oldstate * 0x5851f42d4c957f2dULL + t.inc;
-    const uint32_t xorshifted = (uint32_t)(((oldstate >> 18u) ^ oldstate) >> 27u);
-    const uint32_t rot = (uint32_t)(oldstate >> 59u);
-    return (xorshifted >> rot) | (xorshifted << ((~rot + 1u) & 31));
-}
-// the state after `delta` more UniformUInt32 calls (each is one step of the 64-bit LCG): O(log delta), as PCG's advance()
-PG_DEV void rng_advance(TileSamplerState &t, unsigned long long delta) {
-    unsigned long long accMult = 1, accPlus = 0, curMult = 0x5851f42d4c957f2dULL, curPlus = t.inc;
-    for (; delta > 0; delta >>= 1) {
-        if (delta & 1) { accMult *= curMult; accPlus = accPlus * curMult + curPlus; }
-        curPlus = (curMult + 1) * curPlus;
-        curMult *= curMult;
-    }
-    t.state = accMult * t.state + accPlus;
-}
-PG_DEV uint32_t rng_u32b(TileSamplerState &t, uint32_t b) {  // rng.h:68-74
-    const uint32_t threshold = (~b + 1u) % b;
-    for (;;) { const uint32_t r = rng_u32(t); if (r >= threshold) return r % b; }
-}
-PG_DEV float rng_float(TileSamplerState &t) { return pmin(PG_ONE_MINUS_EPS, (float)rng_u32(t) * 0x1p-32f); }  // rng.h:75-82
-PG_DEV float ts_get1d(const DScene &sc, int tile) {  // PixelSampler::Get1D (RandomSampler: tsDims = 0)
-    TileSamplerState &t = sc.ts[tile];
-    if (t.cur1D < sc.tsDims) return sc.ts1[((size_t)tile * sc.tsDims + t.cur1D++) * sc.tsSpp + t.sampleIndex];
-    return rng_float(t);
-}
-PG_DEV void ts_get2d(const DScene &sc, int kind, int tile, float &a, float &b) {  // PixelSampler::Get2D
-    TileSamplerState &t = sc.ts[tile];
-    if (t.cur2D < sc.tsDims) {
-        const float *p = sc.ts2 + (((size_t)tile * sc.tsDims + t.cur2D++) * sc.tsSpp + t.sampleIndex) * 2;
-        a = p[0]; b = p[1];
-    } else if (kind == PG_SAMPLER_RANDOM) { a = rng_float(t); b = rng_float(t); }  // random.cpp:50-54: braced list, left to right
-    else { b = rng_float(t); a = rng_float(t); }  // `Point2f(rng.UniformFloat(), rng.UniformFloat())` as the reference build (g++) evaluates it: y first
-}
-// tsBatched (DScene): PixelSampler::Get1D / Get2D of sample `sample` of pixel `pixel`; dim = current2DDimension << 6 | current1DDimension
-PG_DEV float tsb_get1d(const DScene &sc, int pixel, int sample, int &dim) {
-    const int c = dim & 63;
-    if (c >= sc.tsDims) { atomicOr(sc.tsOverflow, 1); return 0.5f; }
-    dim += 1;
-    return sc.ts1[((size_t)pixel * sc.tsDims + c) * sc.tsSpp + sample];
-}
-PG_DEV void tsb_get2d(const DScene &sc, int pixel, int sample, int &dim, float &a, float &b) {
-    const int c = dim >> 6;
-    if (c >= sc.tsDims) { atomicOr(sc.tsOverflow, 1); a = b = 0.5f; return; }
-    dim += 64;
-    const float *p = sc.ts2 + (((size_t)pixel * sc.tsDims + c) * sc.tsSpp + sample) * 2;
-    a = p[0]; b = p[1];
-}
-PG_DEV void ts_shuffle(float *samp, int count, int width, TileSamplerState &t) {  // Shuffle, sampling.h:151-157
-    for (int i = 0; i < count; ++i) {
-        const int other = i + (int)rng_u32b(t, (uint32_t)(count - i));
-        for (int j = 0; j < width; ++j) { const float v = samp[width * i + j]; samp[width * i + j] = samp[width * other + j]; samp[width * other + j] = v; }
-    }
-}
-PG_DEV void ts_van_der_corput(int n, float *samples, TileSamplerState &t) {  // VanDerCorput(1, n, ...), lowdiscrepancy.h:154-207
-    uint32_t v = rng_u32(t);
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {  // GrayCodeSample, C[k] = 1 << (31 - k)
-        samples[i] = pmin((float)v * 0x1p-32f, PG_ONE_MINUS_EPS);
-        v ^= 0x80000000u >> __builtin_ctz(i + 1);
-    }
-    for (int i = 0; i < n; ++i) ts_shuffle(samples + i, 1, 1, t);  // a one-element shuffle still draws a number
-    ts_shuffle(samples, n, 1, t);
-}
-PG_DEV void ts_sobol2d(int n, float *samples, TileSamplerState &t) {  // Sobol2D(1, n, ...), lowdiscrepancy.h:209-236
-    uint32_t v0 = rng_u32(t), v1 = rng_u32(t);
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
-        samples[2 * i] = pmin((float)v0 * 0x1p-32f, PG_ONE_MINUS_EPS);
-        samples[2 * i + 1] = pmin((float)v1 * 0x1p-32f, PG_ONE_MINUS_EPS);
-        const int k = __builtin_ctz(i + 1);
-        v0 ^= 0x80000000u >> k;
-        uint32_t c = 0x80000000u;  // CSobol[1][k]: c_0 = 2^31, c_j = c_(j-1) ^ (c_(j-1) >> 1)
-        for (int j = 0; j < k; ++j) c ^= c >> 1;
-        v1 ^= c;
-    }
-    for (int i = 0; i < n; ++i) ts_shuffle(samples + 2 * i, 1, 2, t);
-    ts_shuffle(samples, n, 2, t);
-}
-// a tile's global index, pixel (lx, ly) of it and whether that pixel exists (tiles at the image edge are clipped)
-PG_DEV bool ts_tile_pixel(const RenderParams &rp, int local, int lx, int ly, int &t, int &px, int &py) {
-    t = rp.rd->tile_first + local * rp.rd->tile_step;
-    const int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    px = rp.rd->sample_bounds[0] + tx * 16 + lx;
-    py = rp.rd->sample_bounds[1] + ty * 16 + ly;
-    return px < rp.rd->sample_bounds[2] && py < rp.rd->sample_bounds[3];
-}
 // tileSampler = sampler->Clone(seed), seed = tile.y * nTiles.x + tile.x (integrator.cpp:247-248); RNG::SetSequence, rng.h:129-135
 __global__ void k_ts_init(DScene sc, RenderParams rp) {
     const int local = blockIdx.x * blockDim.x + threadIdx.x;
@@ -366,51 +134,6 @@ __global__ void k_ts_init(DScene sc, RenderParams rp) {
     rng_u32(t);
     t.cur1D = t.cur2D = t.sampleIndex = t.active = 0; t.lens0 = t.lens1 = 0; t.px = t.py = 0; t.draws = 0; t.time = 0;
     sc.ts[local] = t;
-}
-// <Sampler>::StartPixel for pixel (lx, ly) of every tile: the pixel's sample arrays from the tile's stream -- also for pixels
-// outside the integrator's pixel bounds, which are then skipped (integrator.cpp:264-273)
-PG_DEV void ts_start_pixel(const DScene &sc, const PgRenderDesc &rd, TileSamplerState &t, float *s1, float *s2) {
-    {
-        const int n = sc.tsSpp, nd = sc.tsDims;
-        if (rd.sampler == PG_SAMPLER_STRATIFIED) {  // stratified.cpp:43-70, sampling.cpp:42-60
-            const int nx = rd.strat_samples[0], ny = rd.strat_samples[1];
-            for (int i = 0; i < nd; ++i) {
-                float *p = s1 + (size_t)i * n;
-                const float invNSamples = 1.f / (float)n;
-                for (int k = 0; k < n; ++k) { const float delta = rd.strat_jitter ? rng_float(t) : 0.5f; p[k] = pmin(((float)k + delta) * invNSamples, PG_ONE_MINUS_EPS); }
-                ts_shuffle(p, n, 1, t);
-            }
-            for (int i = 0; i < nd; ++i) {
-                float *p = s2 + (size_t)i * n * 2;
-                const float dx = 1.f / (float)nx, dy = 1.f / (float)ny;
-                for (int y = 0; y < ny; ++y)
-                    for (int x = 0; x < nx; ++x) {
-                        const float jx = rd.strat_jitter ? rng_float(t) : 0.5f;
-                        const float jy = rd.strat_jitter ? rng_float(t) : 0.5f;
-                        p[2 * (y * nx + x)] = pmin(((float)x + jx) * dx, PG_ONE_MINUS_EPS);
-                        p[2 * (y * nx + x) + 1] = pmin(((float)y + jy) * dy, PG_ONE_MINUS_EPS);
-                    }
-                ts_shuffle(p, n, 2, t);
-            }
-        } else if (rd.sampler == PG_SAMPLER_ZEROTWO) {  // zerotwosequence.cpp:53-69
-            for (int i = 0; i < nd; ++i) ts_van_der_corput(n, s1 + (size_t)i * n, t);
-            for (int i = 0; i < nd; ++i) ts_sobol2d(n, s2 + (size_t)i * n * 2, t);
-        } else if (rd.sampler == PG_SAMPLER_MAXMINDIST) {  // maxmin.cpp:43-69
-            int cIndex = 0;
-            while ((1 << (cIndex + 1)) <= n) ++cIndex;  // Log2Int(samplesPerPixel)
-            const uint32_t *CPixel = sc.cmaxmin + 32 * cIndex;
-            const float invSPP = 1.f / (float)n;
-            for (int i = 0; i < n; ++i) {
-                uint32_t v = 0, a = (uint32_t)i;
-                for (int k = 0; a != 0; ++k, a >>= 1) if (a & 1) v ^= CPixel[k];  // MultiplyGenerator, lowdiscrepancy.h:93-98
-                s2[2 * i] = (float)i * invSPP;
-                s2[2 * i + 1] = pmin((float)v * 0x1p-32f, PG_ONE_MINUS_EPS);
-            }
-            ts_shuffle(s2, n, 2, t);
-            for (int i = 0; i < nd; ++i) ts_van_der_corput(n, s1 + (size_t)i * n, t);
-            for (int i = 1; i < nd; ++i) ts_sobol2d(n, s2 + (size_t)i * n * 2, t);
-        }  // RandomSampler::StartPixel only fills requested sample arrays: none
-    }
 }
 __global__ void k_ts_start_pixel(DScene sc, RenderParams rp, int lx, int ly) {
     const int local = blockIdx.x * blockDim.x + threadIdx.x;
@@ -495,208 +218,6 @@ void launch_ts_start_pixel(const DScene &sc, const RenderParams &rp, int lx, int
     hipLaunchKernelGGL(k_ts_start_pixel, dim3((rp.nTilesBatch + 63) / 64), dim3(64), 0, s, sc, rp, lx, ly);
 }
 
-// ===========================================================================
-// Camera ray generation: one lane per (pixel, sample) slot
-// ===========================================================================
-PG_DEV V3 xform_point(const float *m, V3 p) {  // transform.h:219-231
-    float x = p.x, y = p.y, z = p.z;
-    float xp = m[0] * x + m[1] * y + m[2] * z + m[3];
-    float yp = m[4] * x + m[5] * y + m[6] * z + m[7];
-    float zp = m[8] * x + m[9] * y + m[10] * z + m[11];
-    float wp = m[12] * x + m[13] * y + m[14] * z + m[15];
-    if (wp == 1) return mk(xp, yp, zp);
-    float inv = 1.f / wp;
-    return mk(inv * xp, inv * yp, inv * zp);
-}
-PG_DEV void xform_ray(const float *m, V3 &o, V3 &d, float &tMax) {  // transform.h:249-262,277-300
-    float x = o.x, y = o.y, z = o.z;
-    float xp = (m[0] * x + m[1] * y) + (m[2] * z + m[3]);
-    float yp = (m[4] * x + m[5] * y) + (m[6] * z + m[7]);
-    float zp = (m[8] * x + m[9] * y) + (m[10] * z + m[11]);
-    float wp = (m[12] * x + m[13] * y) + (m[14] * z + m[15]);
-    float xAbsSum = (fabsf(m[0] * x) + fabsf(m[1] * y) + fabsf(m[2] * z) + fabsf(m[3]));
-    float yAbsSum = (fabsf(m[4] * x) + fabsf(m[5] * y) + fabsf(m[6] * z) + fabsf(m[7]));
-    float zAbsSum = (fabsf(m[8] * x) + fabsf(m[9] * y) + fabsf(m[10] * z) + fabsf(m[11]));
-    V3 oError = mk(xAbsSum, yAbsSum, zAbsSum) * pgamma(3);
-    V3 on;
-    if (wp == 1) on = mk(xp, yp, zp);
-    else { float inv = 1.f / wp; on = mk(inv * xp, inv * yp, inv * zp); }
-    float dx = d.x, dy = d.y, dz = d.z;
-    V3 dn = mk(m[0] * dx + m[1] * dy + m[2] * dz, m[4] * dx + m[5] * dy + m[6] * dz, m[8] * dx + m[9] * dy + m[10] * dz);
-    float lengthSquared = lensq(dn);
-    if (lengthSquared > 0) {
-        float dt = dot(vabs(dn), oError) / lengthSquared;
-        on = on + dn * dt;
-        tMax -= dt;
-    }
-    o = on; d = dn;
-}
-
-// slot -> (local tile, sample-in-batch, pixel-in-tile); a wave is 64 pixels of one tile for one sample
-PG_DEV bool slot_to_pixel(const RenderParams &rp, int slot, int &px, int &py, int &sn) {
-    int pix = slot & 255;
-    int rest = slot >> 8;
-    int sIdx = rest % rp.sCount;
-    int tileInBatch = rest / rp.sCount;
-    int local = rp.tileLocal0 + tileInBatch;
-    int t = rp.rd->tile_first + local * rp.rd->tile_step;
-    int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    px = rp.rd->sample_bounds[0] + tx * 16 + (pix & 15);
-    py = rp.rd->sample_bounds[1] + ty * 16 + (pix >> 4);
-    sn = rp.s0 + sIdx;
-    if (px >= rp.rd->sample_bounds[2] || py >= rp.rd->sample_bounds[3]) return false;
-    // InsideExclusive(pixel, pixelBounds), integrator.cpp:273
-    return px >= rp.rd->pixel_bounds[0] && px < rp.rd->pixel_bounds[2] && py >= rp.rd->pixel_bounds[1] && py < rp.rd->pixel_bounds[3];
-}
-
-// The matrix AnimatedTransform CameraToWorld carries a ray of time `time` to world space with (AnimatedTransform::operator()(Ray),
-// transform.cpp:1171-1181): the start transform up to startTime, the end transform from endTime on, in between Interpolate (pg_motion.h)
-// -- only .m is formed: a ray is transformed by m alone (transform.h:249-262), so Transform(scale)'s inverse is never looked at.
-PG_DEV void camera_matrix_at(const PgRenderDesc &rd, float time, float *m) {
-    if (!rd.camera_animated || time <= rd.camera_time[0]) { for (int k = 0; k < 16; ++k) m[k] = rd.camera_to_world[k]; return; }
-    if (time >= rd.camera_time[1]) { for (int k = 0; k < 16; ++k) m[k] = rd.camera_to_world_end[k]; return; }
-    const float dt = (time - rd.camera_time[0]) / (rd.camera_time[1] - rd.camera_time[0]);
-    interpolate_trs<false>(rd.camera_T, rd.camera_R, rd.camera_S, dt, m, nullptr);
-}
-// CameraSample::time -> the ray's time, perspective.cpp:90 / :121: Lerp(sample.time, shutterOpen, shutterClose)
-PG_DEV float camera_time(const PgRenderDesc &rd, float u) { return (1 - u) * rd.shutter_open + u * rd.shutter_close; }
-// Camera::GenerateRay: PerspectiveCamera (perspective.cpp:95-115,141), OrthographicCamera (orthographic.cpp:68-93,115) and
-// EnvironmentCamera (environment.cpp:43-56), ending in CameraToWorld(ray) -- c2w: the matrix of the ray's time (camera_matrix_at).
-// (l0, l1) = CameraSample::pLens.
-PG_DEV void camera_ray(const PgRenderDesc &rd, const float *c2w, float pFilmX, float pFilmY, float l0, float l1, V3 &o, V3 &d, float &tMax) {
-    V3 pCamera = xform_point(rd.raster_to_camera, mk(pFilmX, pFilmY, 0));
-    o = mk(0, 0, 0);
-    d = normalize(mk(pCamera.x, pCamera.y, pCamera.z));
-    tMax = PG_INF;
-    if (rd.camera_type == 1) { o = pCamera; d = mk(0, 0, 1); }  // OrthographicCamera, orthographic.cpp:76-78
-    if (rd.camera_type == 2) {  // EnvironmentCamera::GenerateRay, environment.cpp:43-56
-        const float theta = PG_PI * pFilmY / rd.full_res[1];
-        const float phi = 2 * PG_PI * pFilmX / rd.full_res[0];
-        float sT, cT, sP, cP;
-        pg_sincosf(theta, &sT, &cT);
-        pg_sincosf(phi, &sP, &cP);
-        o = mk(0, 0, 0);
-        d = mk((float)sT * (float)cP, (float)cT, (float)sT * (float)sP);
-    }
-    if (rd.lens_radius > 0) {
-        float lx, ly;
-        concentric_sample_disk(l0, l1, lx, ly);
-        lx = rd.lens_radius * lx; ly = rd.lens_radius * ly;
-        float ft = rd.focal_distance / d.z;
-        V3 pFocus = o + d * ft;
-        o = mk(lx, ly, 0);
-        d = normalize(pFocus - o);
-    }
-    xform_ray(c2w, o, d, tMax);
-}
-// The camera ray's differentials (GenerateRayDifferential: perspective.cpp:117-140, orthographic.cpp:95-113, the finite
-// difference of camera.cpp:52-93 for the environment camera), carried to world space (transform.h:264-273) and scaled by
-// 1 / sqrt(spp) (integrator.cpp:282-283, geometry.h:908-913).  (o, d) = the world-space camera ray.
-PG_DEV void camera_differentials(const PgRenderDesc &rd, const float *c2w, float pFilmX, float pFilmY, float l0, float l1, V3 o, V3 d, V3 &rxO, V3 &rxD, V3 &ryO, V3 &ryD) {
-    if (rd.camera_type == 2) {
-        const float eps = .05f;
-        V3 xo, xd, yo, yd;
-        float tm;
-        camera_ray(rd, c2w, pFilmX + eps, pFilmY, l0, l1, xo, xd, tm);
-        camera_ray(rd, c2w, pFilmX, pFilmY + eps, l0, l1, yo, yd, tm);
-        rxO = o + vdiv(xo - o, eps); rxD = d + vdiv(xd - d, eps);
-        ryO = o + vdiv(yo - o, eps); ryD = d + vdiv(yd - d, eps);
-    } else {
-        const V3 dxCamera = mk(rd.dx_camera[0], rd.dx_camera[1], rd.dx_camera[2]), dyCamera = mk(rd.dy_camera[0], rd.dy_camera[1], rd.dy_camera[2]);
-        const V3 pCamera = xform_point(rd.raster_to_camera, mk(pFilmX, pFilmY, 0));
-        V3 co = mk(0, 0, 0), cd = normalize(mk(pCamera.x, pCamera.y, pCamera.z));  // the camera-space main ray again
-        if (rd.camera_type == 1) { co = pCamera; cd = mk(0, 0, 1); }
-        float lx = 0, ly = 0;
-        if (rd.lens_radius > 0) {
-            concentric_sample_disk(l0, l1, lx, ly);
-            lx = rd.lens_radius * lx; ly = rd.lens_radius * ly;
-            const float ft = rd.focal_distance / cd.z;
-            const V3 pFocus = co + cd * ft;
-            co = mk(lx, ly, 0);
-            cd = normalize(pFocus - co);
-        }
-        if (rd.camera_type == 0) {
-            if (rd.lens_radius > 0) {
-                const V3 dx = normalize(pCamera + dxCamera);
-                float ft = rd.focal_distance / dx.z;
-                V3 pFocus = mk(0, 0, 0) + dx * ft;
-                rxO = mk(lx, ly, 0);
-                rxD = normalize(pFocus - rxO);
-                const V3 dy = normalize(pCamera + dyCamera);
-                ft = rd.focal_distance / dy.z;
-                pFocus = mk(0, 0, 0) + dy * ft;
-                ryO = mk(lx, ly, 0);
-                ryD = normalize(pFocus - ryO);
-            } else {
-                rxO = ryO = co;
-                rxD = normalize(pCamera + dxCamera);
-                ryD = normalize(pCamera + dyCamera);
-            }
-        } else {
-            if (rd.lens_radius > 0) {
-                const float ft = rd.focal_distance / cd.z;
-                V3 pFocus = (pCamera + dxCamera) + mk(0, 0, 1) * ft;
-                rxO = mk(lx, ly, 0);
-                rxD = normalize(pFocus - rxO);
-                pFocus = (pCamera + dyCamera) + mk(0, 0, 1) * ft;
-                ryO = mk(lx, ly, 0);
-                ryD = normalize(pFocus - ryO);
-            } else {
-                rxO = co + dxCamera;
-                ryO = co + dyCamera;
-                rxD = ryD = cd;
-            }
-        }
-        rxO = xform_point(c2w, rxO); ryO = xform_point(c2w, ryO);
-        rxD = m4_vec(c2w, rxD); ryD = m4_vec(c2w, ryD);
-    }
-    const float sc = 1 / sqrtf((float)rd.spp);
-    rxO = o + (rxO - o) * sc; ryO = o + (ryO - o) * sc;
-    rxD = d + (rxD - d) * sc; ryD = d + (ryD - d) * sc;
-}
-// ANIM: the camera moves (PgRenderDesc::camera_animated) -- every sample's camera-to-world matrix is interpolated at its time; the still
-// camera's kernel does not carry that code (64 instead of 39 registers, 113 spilled scalars)
-// The realistic camera's sample (camera_type 3): Camera::GenerateRayDifferential over the lens system `L` (pg_lens.h) -- the main ray and the
-// shifted rays, each carried to world space by c2w and normalized (realistic.cpp:700-701) -- giving the world-space ray, the sample's weight
-// (0: vignetted), the calls' statistics, and where `diff` is not null the differentials scaled by 1 / sqrt(spp) (integrator.cpp:282-283) as 12 floats.
-PG_DEV float lens_camera_sample(const PgLensSystem &L, const PgRenderDesc &rd, const float *c2w, float pFilmX, float pFilmY, float l0, float l1, V3 &o, V3 &d, float &tMax,
-                                int &nCalls, int &nVignetted, float4 *diff) {
-    LensRay rays[3];
-    float eps[2] = {.05f, .05f};
-    auto toWorld = [&](LensRay &r) {
-        V3 ro = mk(r.o.x, r.o.y, r.o.z), rdir = mk(r.d.x, r.d.y, r.d.z);
-        float tm = PG_INF;
-        xform_ray(c2w, ro, rdir, tm);
-        rdir = normalize(rdir);
-        r.o = lens_v(ro.x, ro.y, ro.z); r.d = lens_v(rdir.x, rdir.y, rdir.z);
-    };
-    const float wt = lens_generate_ray_differential(L, pFilmX, pFilmY, rd.full_res[0], rd.full_res[1], l0, l1, rd.shutter_close - rd.shutter_open, toWorld, rays, eps,
-                                                    &nCalls, &nVignetted);
-    if (wt == 0) return 0;
-    o = mk(rays[0].o.x, rays[0].o.y, rays[0].o.z); d = mk(rays[0].d.x, rays[0].d.y, rays[0].d.z);
-    tMax = PG_INF;
-    if (diff) {
-        const V3 xo = mk(rays[1].o.x, rays[1].o.y, rays[1].o.z), xd = mk(rays[1].d.x, rays[1].d.y, rays[1].d.z);
-        const V3 yo = mk(rays[2].o.x, rays[2].o.y, rays[2].o.z), yd = mk(rays[2].d.x, rays[2].d.y, rays[2].d.z);
-        V3 rxO = o + vdiv(xo - o, eps[0]), rxD = d + vdiv(xd - d, eps[0]);  // camera.cpp:72-73, :87-88
-        V3 ryO = o + vdiv(yo - o, eps[1]), ryD = d + vdiv(yd - d, eps[1]);
-        const float sc = 1 / sqrtf((float)rd.spp);
-        rxO = o + (rxO - o) * sc; ryO = o + (ryO - o) * sc;
-        rxD = d + (rxD - d) * sc; ryD = d + (ryD - d) * sc;
-        diff[0] = make_float4(rxO.x, rxO.y, rxO.z, rxD.x); diff[1] = make_float4(rxD.y, rxD.z, ryO.x, ryO.y); diff[2] = make_float4(ryO.z, ryD.x, ryD.y, ryD.z);
-    }
-    return wt;
-}
-// The lens statistics of the lanes of a wave in one set of atomics (as the integrator statistics are counted): calls, vignetted, samples of weight 0
-PG_DEV void lens_stats_add(LensFrame *lens, int nCalls, int nVignetted, bool zeroWeight) {
-    const unsigned long long calls = wave_sum((unsigned long long)nCalls), vig = wave_sum((unsigned long long)nVignetted), zero = wave_sum(zeroWeight ? 1ull : 0ull);
-    if (lane_id() == 0 && calls) {
-        unsigned long long *st = lens->stats;
-        atomicAdd(st, calls);
-        if (vig) atomicAdd(st + 1, vig);
-        if (zero) atomicAdd(st + 2, zero);
-    }
-}
 // REAL: the realistic camera (camera_type 3), an instantiation of its own chosen only for such frames: the lens block is staged from the frame's
 // LensFrame into LDS once per block (1.5 KB; every lane walks the interfaces with a uniform index and picks a pupil box with its own), each sample
 // runs 3 to 5 lens traces, and the sample's weight goes to the LensFrame's per-slot array.  A sample of weight 0 enters no queue: its path never
@@ -845,1574 +366,9 @@ void launch_ts_generate(const DScene &sc, const RenderParams &rp, PathState st, 
 // ===========================================================================
 // Shading
 // ===========================================================================
-struct Isect { V3 p, pError, wo, n, ns, sdpdu, sdpdv, sdndu, sdndv; };  // n: geometric normal; ns, sd*: shading.n, shading.dpdu/dpdv/dndu/dndv (the last three feed bump mapping only)
-
-PG_DEV V3 tri_normal(const Tri &t) {  // triangle.cpp:346-348
-    V3 n = normalize(cross(t.p0 - t.p2, t.p1 - t.p2));
-    if (t.flags & PG_TRI_FLIP_NORMAL) n = -n;
-    return n;
-}
-PG_DEV void load_uv(const DScene &sc, int prim, uint32_t flags, float uv[6]) {  // triangle.h:98-108
-    if (sc.attrUV && (flags & PG_TRI_HAS_UV)) tri_attr_uv(sc, prim, uv);
-    else { uv[0] = 0; uv[1] = 0; uv[2] = 1; uv[3] = 0; uv[4] = 1; uv[5] = 1; }
-}
-// The tail of Triangle::Intersect (triangle.cpp:293-348) for the surviving hit.
-// Per-vertex attribute a (N or S) of triangle prim interpolated with weights (w0, w1, w2): w0*a0 + w1*a1 + w2*a2.
-PG_DEV V3 tri_interp(const float4 *attr, int prim, float w0, float w1, float w2) {
-    const float4 a = attr[3 * (size_t)prim], b = attr[3 * (size_t)prim + 1], c = attr[3 * (size_t)prim + 2];
-    return mk(a.x, a.y, a.z) * w0 + mk(b.x, b.y, b.z) * w1 + mk(c.x, c.y, c.z) * w2;
-}
-PG_DEV V3 tri_interp_normal(const DScene &sc, int prim, float w0, float w1, float w2) {  // the same with the per-vertex normals of DScene::triAttr
-    float n[9];
-    tri_attr_normals(sc, prim, n);
-    return mk(n[0], n[1], n[2]) * w0 + mk(n[3], n[4], n[5]) * w1 + mk(n[6], n[7], n[8]) * w2;
-}
-// Triangle::Intersect's geometric normal for a hit with barycentrics (b0,b1,b2): Normalize(Cross(dp02, dp12)), flipped by
-// reverseOrientation ^ transformSwapsHandedness (triangle.cpp:346-348), then made to face the interpolated shading normal
-// when the mesh has per-vertex normals (SetShadingGeometry's Faceforward, interaction.cpp:79-81) -- full version below.
-// The tail of Triangle::Intersect (triangle.cpp:293-419) for the surviving hit.
-PG_DEV Isect make_isect(const DScene &sc, int prim, const Tri &t, float b0, float b1, float b2, V3 rayD) {
-    Isect is;
-    float uv[6];
-    load_uv(sc, prim, t.flags, uv);
-    V3 dpdu, dpdv;
-    tri_dpdu_dpdv(t.p0, t.p1, t.p2, uv, dpdu, dpdv);
-    float xAbsSum = (fabsf(b0 * t.p0.x) + fabsf(b1 * t.p1.x) + fabsf(b2 * t.p2.x));
-    float yAbsSum = (fabsf(b0 * t.p0.y) + fabsf(b1 * t.p1.y) + fabsf(b2 * t.p2.y));
-    float zAbsSum = (fabsf(b0 * t.p0.z) + fabsf(b1 * t.p1.z) + fabsf(b2 * t.p2.z));
-    is.pError = mk(xAbsSum, yAbsSum, zAbsSum) * pgamma(7);
-    is.p = t.p0 * b0 + t.p1 * b1 + t.p2 * b2;
-    is.wo = normalize(-rayD);  // Interaction ctor, interaction.h:60
-    is.n = tri_normal(t);
-    is.ns = is.n;
-    is.sdpdu = dpdu; is.sdpdv = dpdv;
-    is.sdndu = is.sdndv = mk(0, 0, 0);
-    const bool hasN = sc.attrN && (t.flags & PG_TRI_HAS_N), hasS = sc.triS && (t.flags & PG_TRI_HAS_S);
-    if (hasN || hasS) {  // shading geometry, triangle.cpp:350-419 (dndu/dndv only feed ray differentials)
-        V3 ns = is.n, ss = normalize(dpdu), ts;
-        if (hasN) {
-            V3 v = tri_interp_normal(sc, prim, b0, b1, b2);
-            if (lensq(v) > 0) ns = normalize(v);
-        }
-        if (hasS) {
-            V3 v = tri_interp(sc.triS, prim, b0, b1, b2);
-            if (lensq(v) > 0) ss = normalize(v);
-        }
-        ts = cross(ss, ns);
-        if (lensq(ts) > 0.f) { ts = normalize(ts); ss = cross(ts, ns); }
-        else coordinate_system(ns, ss, ts);
-        if (hasN) {  // dndu, dndv of the shading geometry, triangle.cpp:383-416
-            const float d02x = uv[0] - uv[4], d02y = uv[1] - uv[5], d12x = uv[2] - uv[4], d12y = uv[3] - uv[5];
-            float nv[9];
-            tri_attr_normals(sc, prim, nv);
-            const V3 n0 = mk(nv[0], nv[1], nv[2]), n1 = mk(nv[3], nv[4], nv[5]), n2 = mk(nv[6], nv[7], nv[8]);
-            const V3 dn1 = n0 - n2, dn2 = n1 - n2;
-            const float determinant = d02x * d12y - d02y * d12x;
-            if ((double)fabsf(determinant) < 1e-8) {
-                const V3 dn = cross(n2 - n0, n1 - n0);
-                if (lensq(dn) != 0) coordinate_system(dn, is.sdndu, is.sdndv);
-            } else {
-                const float invDet = 1 / determinant;
-                is.sdndu = (dn1 * d12y - dn2 * d02y) * invDet;
-                is.sdndv = (dn1 * (-d12x) + dn2 * d02x) * invDet;
-            }
-        }
-        if (t.flags & PG_TRI_REVERSE_ORIENTATION) ts = -ts;
-        // SetShadingGeometry(ss, ts, ..., orientationIsAuthoritative = true), interaction.cpp:74-90
-        is.ns = normalize(cross(ss, ts));
-        if (dot(is.n, is.ns) < 0.f) is.n = -is.n;
-        is.sdpdu = ss; is.sdpdv = ts;
-    }
-    return is;
-}
-// The geometric normal alone, as make_isect leaves it in isect.n (for Le() at a hit that is not shaded further).
-PG_DEV V3 hit_normal(const DScene &sc, int prim, const Tri &t, float b0, float b1, float b2) {
-    if ((sc.attrN && (t.flags & PG_TRI_HAS_N)) || (sc.triS && (t.flags & PG_TRI_HAS_S))) return make_isect(sc, prim, t, b0, b1, b2, mk(0, 0, 1)).n;
-    return tri_normal(t);
-}
-
-// BSDF: LambertianReflection and/or MicrofacetReflection(TrowbridgeReitz, FresnelDielectric(1.5, 1)) lobes in the order
-// the materials add them (matte.cpp:45-62, plastic.cpp:45-70); reflection.h:164-213, reflection.cpp:680-796.
-struct Bsdf {
-    V3 ns, ng, ss, ts; Spec R, Ks; float alpha; int nBxDFs; bool hasDiff, hasSpec;
-    bool orenNayar; float onA, onB;  // the diffuse lobe is OrenNayar(R, sigma) (reflection.h:425-431) instead of LambertianReflection
-    int specular;  // 0; 1 = SpecularReflection(Kr, FresnelNoOp) (mirror.cpp:44-56); 2 = FresnelSpecular(Kr, Kt, 1, eta) (glass.cpp:45-65)
-    Spec Kr, Kt; float eta;
-};
-#define PG_BSDF_REFLECTION 1
-#define PG_BSDF_TRANSMISSION 2
-#define PG_BSDF_SPECULAR 16
-PG_DEV V3 world_to_local(const Bsdf &b, V3 v) { return mk(dot(v, b.ss), dot(v, b.ts), dot(v, b.ns)); }
-PG_DEV V3 local_to_world(const Bsdf &b, V3 v) {
-    return mk(b.ss.x * v.x + b.ts.x * v.y + b.ns.x * v.z, b.ss.y * v.x + b.ts.y * v.y + b.ns.y * v.z,
-              b.ss.z * v.x + b.ts.z * v.y + b.ns.z * v.z);
-}
-// reflection.h:52-83
-PG_DEV float cos2_theta(V3 w) { return w.z * w.z; }
-PG_DEV float sin2_theta(V3 w) { return pmax(0.f, 1.f - cos2_theta(w)); }
-PG_DEV float sin_theta(V3 w) { return sqrtf(sin2_theta(w)); }
-PG_DEV float tan_theta(V3 w) { return sin_theta(w) / w.z; }
-PG_DEV float tan2_theta(V3 w) { return sin2_theta(w) / cos2_theta(w); }
-PG_DEV float cos_phi(V3 w) { float st = sin_theta(w); return (st == 0) ? 1 : clampf(w.x / st, -1, 1); }
-PG_DEV float sin_phi(V3 w) { float st = sin_theta(w); return (st == 0) ? 0 : clampf(w.y / st, -1, 1); }
-PG_DEV float cos2_phi(V3 w) { return cos_phi(w) * cos_phi(w); }
-PG_DEV float sin2_phi(V3 w) { return sin_phi(w) * sin_phi(w); }
-PG_DEV float fr_dielectric(float cosThetaI, float etaI, float etaT) {  // reflection.cpp:47-68
-    cosThetaI = clampf(cosThetaI, -1, 1);
-    if (!(cosThetaI > 0.f)) { float t = etaI; etaI = etaT; etaT = t; cosThetaI = fabsf(cosThetaI); }
-    float sinThetaI = sqrtf(pmax(0.f, 1 - cosThetaI * cosThetaI));
-    float sinThetaT = etaI / etaT * sinThetaI;
-    if (sinThetaT >= 1) return 1;
-    float cosThetaT = sqrtf(pmax(0.f, 1 - sinThetaT * sinThetaT));
-    float Rparl = ((etaT * cosThetaI) - (etaI * cosThetaT)) / ((etaT * cosThetaI) + (etaI * cosThetaT));
-    float Rperp = ((etaI * cosThetaI) - (etaT * cosThetaT)) / ((etaI * cosThetaI) + (etaT * cosThetaT));
-    return (Rparl * Rparl + Rperp * Rperp) / 2;
-}
-// TrowbridgeReitzDistribution with alphax == alphay == a, microfacet.cpp:155-184, microfacet.h:57-63
-PG_DEV float tr_D(float a, V3 wh) {
-    float tan2Theta = tan2_theta(wh);
-    if (isinf(tan2Theta)) return 0.f;
-    const float cos4Theta = cos2_theta(wh) * cos2_theta(wh);
-    float e = (cos2_phi(wh) / (a * a) + sin2_phi(wh) / (a * a)) * tan2Theta;
-    return 1 / (PG_PI * a * a * cos4Theta * (1 + e) * (1 + e));
-}
-PG_DEV float tr_lambda(float a, V3 w) {
-    float absTanTheta = fabsf(tan_theta(w));
-    if (isinf(absTanTheta)) return 0.f;
-    float alpha = sqrtf(cos2_phi(w) * a * a + sin2_phi(w) * a * a);
-    float alpha2Tan2Theta = (alpha * absTanTheta) * (alpha * absTanTheta);
-    return (-1 + sqrtf(1.f + alpha2Tan2Theta)) / 2;
-}
-PG_DEV float tr_G1(float a, V3 w) { return 1 / (1 + tr_lambda(a, w)); }
-PG_DEV float tr_G(float a, V3 wo, V3 wi) { return 1 / (1 + tr_lambda(a, wo) + tr_lambda(a, wi)); }
-PG_DEV float tr_pdf(float a, V3 wo, V3 wh) { return tr_D(a, wh) * tr_G1(a, wo) * absdot(wo, wh) / fabsf(wo.z); }  // microfacet.cpp:339-345
-// TrowbridgeReitzSample11 / TrowbridgeReitzSample / Sample_wh (visible area), microfacet.cpp:238-336.  The
-// normal-incidence branch evaluates sqrt/cos/sin in double on float arguments, as the reference's source does.
-PG_DEV void tr_sample11(float cosTheta, float U1, float U2, float &slope_x, float &slope_y) {
-    if ((double)cosTheta > .9999) {
-        float r = (float)sqrt((double)(U1 / (1 - U1)));
-        float phi = (float)(6.28318530718 * (double)U2);
-        double s, c;
-        sincos((double)phi, &s, &c);
-        slope_x = (float)((double)r * c);
-        slope_y = (float)((double)r * s);
-        return;
-    }
-    float sinTheta = sqrtf(pmax(0.f, 1.f - cosTheta * cosTheta));
-    float tanTheta = sinTheta / cosTheta;
-    float a = 1 / tanTheta;
-    float G1 = 2 / (1 + sqrtf(1.f + 1.f / (a * a)));
-    float A = 2 * U1 / G1 - 1;
-    float tmp = 1.f / (A * A - 1.f);
-    if (tmp > 1e10f) tmp = 1e10f;
-    float B = tanTheta;
-    float D = sqrtf(pmax(B * B * tmp * tmp - (A * A - B * B) * tmp, 0.f));
-    float slope_x_1 = B * tmp - D;
-    float slope_x_2 = B * tmp + D;
-    slope_x = (A < 0 || slope_x_2 > 1.f / tanTheta) ? slope_x_1 : slope_x_2;
-    float S;
-    if (U2 > 0.5f) { S = 1.f; U2 = 2.f * (U2 - .5f); }
-    else { S = -1.f; U2 = 2.f * (.5f - U2); }
-    float z = (U2 * (U2 * (U2 * 0.27385f - 0.73369f) + 0.46341f)) /
-              (U2 * (U2 * (U2 * 0.093073f + 0.309420f) - 1.000000f) + 0.597999f);
-    slope_y = S * z * sqrtf(1.f + slope_x * slope_x);
-}
-PG_DEV V3 tr_sample_wh(float a, V3 wo, float u0, float u1) {
-    const bool flip = wo.z < 0;
-    V3 wi = flip ? -wo : wo;
-    V3 wiStretched = normalize(mk(a * wi.x, a * wi.y, wi.z));
-    float slope_x, slope_y;
-    tr_sample11(wiStretched.z, u0, u1, slope_x, slope_y);
-    float tmp = cos_phi(wiStretched) * slope_x - sin_phi(wiStretched) * slope_y;
-    slope_y = sin_phi(wiStretched) * slope_x + cos_phi(wiStretched) * slope_y;
-    slope_x = tmp;
-    slope_x = a * slope_x;
-    slope_y = a * slope_y;
-    V3 wh = normalize(mk(-slope_x, -slope_y, 1.f));
-    return flip ? -wh : wh;
-}
-// MicrofacetReflection::f / Pdf / Sample_f, reflection.cpp:226-238, :410-429 (local coordinates)
-PG_DEV Spec mf_f(const Bsdf &b, V3 wo, V3 wi) {
-    float cosThetaO = fabsf(wo.z), cosThetaI = fabsf(wi.z);
-    V3 wh = wi + wo;
-    if (cosThetaI == 0 || cosThetaO == 0) return sp(0);
-    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return sp(0);
-    wh = normalize(wh);
-    V3 whf = (dot(wh, mk(0, 0, 1)) < 0.f) ? -wh : wh;  // Faceforward
-    Spec F = sp(fr_dielectric(dot(wi, whf), 1.5f, 1.f));  // FresnelDielectric(1.5f, 1.f)
-    return (((b.Ks * tr_D(b.alpha, wh)) * tr_G(b.alpha, wo, wi)) * F) / (4 * cosThetaI * cosThetaO);
-}
-PG_DEV float mf_pdf(const Bsdf &b, V3 wo, V3 wi) {
-    if (!(wo.z * wi.z > 0)) return 0;
-    V3 wh = normalize(wo + wi);
-    return tr_pdf(b.alpha, wo, wh) / (4 * dot(wo, wh));
-}
-PG_DEV void mf_sample(const Bsdf &b, V3 wo, V3 &wi, float u0, float u1, float &pdf) {  // leaves pdf = 0 when no sample
-    if (wo.z == 0) return;
-    V3 wh = tr_sample_wh(b.alpha, wo, u0, u1);
-    if (dot(wo, wh) < 0) return;
-    wi = -wo + wh * (2 * dot(wo, wh));  // Reflect, reflection.h:93-95
-    if (!(wo.z * wi.z > 0)) return;
-    pdf = tr_pdf(b.alpha, wo, wh) / (4 * dot(wo, wh));
-}
-PG_DEV float lambert_pdf(V3 wo, V3 wi) { return (wo.z * wi.z > 0) ? fabsf(wi.z) * PG_INVPI : 0; }  // reflection.cpp:392-394
-// the diffuse lobe: LambertianReflection::f (reflection.cpp:178-180) or OrenNayar::f (:197-219)
-PG_DEV Spec diffuse_f(const Bsdf &b, V3 wo, V3 wi) {
-    if (!b.orenNayar) return b.R * PG_INVPI;
-    float sinThetaI = sin_theta(wi), sinThetaO = sin_theta(wo);
-    float maxCos = 0;
-    if ((double)sinThetaI > 1e-4 && (double)sinThetaO > 1e-4) {
-        float sinPhiI = sin_phi(wi), cosPhiI = cos_phi(wi);
-        float sinPhiO = sin_phi(wo), cosPhiO = cos_phi(wo);
-        float dCos = cosPhiI * cosPhiO + sinPhiI * sinPhiO;
-        maxCos = pmax(0.f, dCos);
-    }
-    float sinAlpha, tanBeta;
-    if (fabsf(wi.z) > fabsf(wo.z)) { sinAlpha = sinThetaO; tanBeta = sinThetaI / fabsf(wi.z); }
-    else { sinAlpha = sinThetaI; tanBeta = sinThetaO / fabsf(wo.z); }
-    return (b.R * PG_INVPI) * (b.onA + b.onB * maxCos * sinAlpha * tanBeta);
-}
-PG_DEV Spec bsdf_f_local(const Bsdf &b, V3 wo, V3 wi, bool reflect) {
-    Spec f = sp(0);
-    if (b.hasDiff && reflect) f = f + diffuse_f(b, wo, wi);
-    if (b.hasSpec && reflect) f = f + mf_f(b, wo, wi);
-    return f;
-}
-PG_DEV Spec bsdf_f(const Bsdf &b, V3 woW, V3 wiW) {  // reflection.cpp:680-693
-    V3 wi = world_to_local(b, wiW), wo = world_to_local(b, woW);
-    if (wo.z == 0) return sp(0);
-    bool reflect = dot(wiW, b.ng) * dot(woW, b.ng) > 0;
-    return bsdf_f_local(b, wo, wi, reflect);
-}
-PG_DEV float bsdf_pdf(const Bsdf &b, V3 woW, V3 wiW) {  // reflection.cpp:781-796
-    if (b.nBxDFs == 0) return 0.f;
-    V3 wo = world_to_local(b, woW), wi = world_to_local(b, wiW);
-    if (wo.z == 0) return 0.f;
-    float pdf = 0.f;
-    if (b.hasDiff) pdf += lambert_pdf(wo, wi);
-    if (b.hasSpec) pdf += mf_pdf(b, wo, wi);
-    return pdf / b.nBxDFs;
-}
-// A BSDF whose only lobe is specular: SpecularReflection::Sample_f (reflection.cpp:136-143) or FresnelSpecular::Sample_f
-// (:487-521) inside BSDF::Sample_f (:714-779).
-PG_DEV Spec bsdf_sample_specular(const Bsdf &b, V3 woWorld, V3 &wiWorld, float u0, float &pdf, int &sampledType) {
-    V3 wo = world_to_local(b, woWorld), wi;
-    Spec f;
-    pdf = 0; sampledType = 0;
-    if (wo.z == 0) return sp(0);
-    if (b.specular == 1) {
-        wi = mk(-wo.x, -wo.y, wo.z);
-        pdf = 1;
-        f = (sp(1.f) * b.Kr) / fabsf(wi.z);
-        sampledType = PG_BSDF_SPECULAR | PG_BSDF_REFLECTION;
-    } else {
-        const float ur = pmin(u0 * 1 - 0, PG_ONE_MINUS_EPS);
-        const float F = fr_dielectric(wo.z, 1.f, b.eta);
-        if (ur < F) {
-            wi = mk(-wo.x, -wo.y, wo.z);
-            sampledType = PG_BSDF_SPECULAR | PG_BSDF_REFLECTION;
-            pdf = F;
-            f = (b.Kr * F) / fabsf(wi.z);
-        } else {
-            const bool entering = wo.z > 0;
-            const float etaI = entering ? 1.f : b.eta, etaT = entering ? b.eta : 1.f;
-            const V3 n = (wo.z < 0.f) ? mk(0, 0, -1) : mk(0, 0, 1);  // Faceforward(Normal3f(0, 0, 1), wo)
-            const float eta = etaI / etaT;
-            // Refract, reflection.h:97-109
-            const float cosThetaI = dot(n, wo);
-            const float sin2ThetaI = pmax(0.f, 1 - cosThetaI * cosThetaI);
-            const float sin2ThetaT = eta * eta * sin2ThetaI;
-            if (sin2ThetaT >= 1) return sp(0);
-            const float cosThetaT = sqrtf(1 - sin2ThetaT);
-            wi = (-wo) * eta + n * (eta * cosThetaI - cosThetaT);
-            Spec ft = b.Kt * (1 - F);
-            ft = ft * ((etaI * etaI) / (etaT * etaT));  // TransportMode::Radiance
-            sampledType = PG_BSDF_SPECULAR | PG_BSDF_TRANSMISSION;
-            pdf = 1 - F;
-            f = ft / fabsf(wi.z);
-        }
-    }
-    if (pdf == 0) { sampledType = 0; return sp(0); }
-    wiWorld = local_to_world(b, wi);
-    return f;
-}
-PG_DEV Spec bsdf_sample_f(const Bsdf &b, V3 woWorld, V3 &wiWorld, float u0, float u1, float &pdf) {  // reflection.cpp:714-779
-    int matchingComps = b.nBxDFs;
-    pdf = 0;
-    if (matchingComps == 0) return sp(0);
-    int comp = (int)floorf(u0 * matchingComps);
-    if (comp > matchingComps - 1) comp = matchingComps - 1;
-    const bool useSpec = b.hasSpec && (comp == 1 || !b.hasDiff);  // lobe order: Lambertian, then microfacet
-    float ur0 = pmin(u0 * matchingComps - comp, PG_ONE_MINUS_EPS);
-    V3 wo = world_to_local(b, woWorld), wi = mk(0, 0, 0);
-    if (wo.z == 0) return sp(0);
-    if (useSpec) mf_sample(b, wo, wi, ur0, u1, pdf);
-    else {  // BxDF::Sample_f, :383-390
-        wi = cosine_sample_hemisphere(ur0, u1);
-        if (wo.z < 0) wi.z *= -1;
-        pdf = lambert_pdf(wo, wi);
-    }
-    if (pdf == 0) return sp(0);
-    wiWorld = local_to_world(b, wi);
-    if (matchingComps > 1) {
-        pdf += useSpec ? lambert_pdf(wo, wi) : mf_pdf(b, wo, wi);
-        pdf /= matchingComps;
-    }
-    bool reflect = dot(wiWorld, b.ng) * dot(woWorld, b.ng) > 0;
-    return bsdf_f_local(b, wo, wi, reflect);
-}
-
-// Triangle::Sample(u, pdf) + Shape::Sample(ref, u, pdf) + DiffuseAreaLight::Sample_Li
-// (triangle.cpp:582-607, shape.cpp:56-70, diffuse.cpp:68-81).
-// ===========================================================================
-// BSDF over a material's BxDF list (PgBxDF, include/pbrt_gpu.h): every BxDF of core/reflection.cpp the closed set of
-// materials can add, and BSDF::f / Pdf / Sample_f over the list (reflection.cpp:680-796).  Used by the EXT kernels for
-// every material; the specialised Bsdf above is the same arithmetic with the list shape of matte/plastic/mirror/glass
-// baked in.
-// ===========================================================================
-#define PG_BSDF_DIFFUSE 4
-#define PG_BSDF_GLOSSY 8
-#define PG_BSDF_ALL 31
-// `types`: the PgBxDFType of lobes[i] in bits 4i .. 4i+3, `scaled`: bit i = lobes[i] has ScaledBxDF wrappers -- read once when the
-// list is bound (lbsdf_bind), so that BSDF::NumComponents / the component choice of Sample_f / the matching tests of f and Pdf are
-// register arithmetic instead of a chain of dependent loads through the lane's list pointer
-// LB: what a list is made of.  PgBxDF (120 B, the ABI's record: the scene's constant lists, the shading kernel's own copies) or PkLobe,
-// the 48-B record k_material writes and k_shade<3> reads (pg_kernels.h) -- the same member NAMES over a type-dependent layout, so that
-// lobe_f / lobe_pdf / lobe_sample_f / lobe_fresnel below are ONE text for both and read each field where it is used.  A MixMaterial's
-// ScaledBxDF factors take a record of their own behind a PkLobe; all lobes of a hit have them or none has (the hit's material is a mix or
-// it is not): recStride = 2 or 1 records per lobe.  (Round 5: the lists were up to 5 x 120 B + 32 B per textured hit, written by k_material
-// and read back line by line -- 4.9 x the slot's algorithmic bytes at the L2s' memory side.)
-template <class LB> struct LobeBsdfT { V3 ns, ng, ss, ts; const LB *lobes; int recStride; int n; float eta; unsigned types, scaled; };
-typedef LobeBsdfT<PgBxDF> LobeBsdf;
-PG_DEV int lobe_fresnel_kind(const PgBxDF &b) { return b.fresnel; }
-PG_DEV int lobe_fresnel_kind(const PkLobe &b) { return (int)((b.hdr >> 4) & 3u); }
-PG_DEV void lbsdf_bind(LobeBsdfT<PgBxDF> &b, const PgBxDF *lobes, int n, float eta) {
-    b.lobes = lobes; b.recStride = 1; b.n = n; b.eta = eta; b.types = 0; b.scaled = 0;
-    for (int i = 0; i < n; ++i) {
-        b.types |= (unsigned)lobes[i].type << (4 * i);
-        b.scaled |= (lobes[i].n_scales > 0 ? 1u : 0u) << i;
-    }
-}
-PG_DEV void lbsdf_bind(LobeBsdfT<PkLobe> &b, const PkLobe *rec, int n, float eta, int recStride) {
-    b.lobes = rec; b.recStride = recStride; b.n = n; b.eta = eta; b.types = 0; b.scaled = 0;
-    for (int i = 0; i < n; ++i) {
-        const unsigned hdr = rec[i * recStride].hdr;
-        b.types |= (hdr & 15u) << (4 * i);
-        b.scaled |= (((hdr >> 6) & 3u) > 0 ? 1u : 0u) << i;
-    }
-}
-template <class LB> PG_DEV const LB &lobe_at(const LobeBsdfT<LB> &b, int i) { return b.lobes[i * b.recStride]; }
-template <class LB> PG_DEV int lbsdf_lobe(const LobeBsdfT<LB> &b, int i) { return (int)((b.types >> (4 * i)) & 15u); }
-template <class LB> PG_DEV V3 world_to_local(const LobeBsdfT<LB> &b, V3 v) { return mk(dot(v, b.ss), dot(v, b.ts), dot(v, b.ns)); }
-template <class LB> PG_DEV V3 local_to_world(const LobeBsdfT<LB> &b, V3 v) {
-    return mk(b.ss.x * v.x + b.ts.x * v.y + b.ns.x * v.z, b.ss.y * v.x + b.ts.y * v.y + b.ns.y * v.z,
-              b.ss.z * v.x + b.ts.z * v.y + b.ns.z * v.z);
-}
-PG_DEV Spec operator-(Spec a, Spec b) { return sp3(a.r - b.r, a.g - b.g, a.b - b.b); }
-PG_DEV Spec operator/(Spec a, Spec b) { return sp3(a.r / b.r, a.g / b.g, a.b / b.b); }
-PG_DEV Spec sp_sqrt(Spec a) { return sp3(sqrtf(a.r), sqrtf(a.g), sqrtf(a.b)); }
-PG_DEV Spec fr_conductor(float cosThetaI, Spec etai, Spec etat, Spec k) {  // reflection.cpp:71-96
-    cosThetaI = clampf(cosThetaI, -1, 1);
-    const Spec eta = etat / etai;
-    const Spec etak = k / etai;
-    const float cosThetaI2 = cosThetaI * cosThetaI;
-    const float sinThetaI2 = 1.f - cosThetaI2;
-    const Spec eta2 = eta * eta;
-    const Spec etak2 = etak * etak;
-    const Spec t0 = (eta2 - etak2) - sp(sinThetaI2);
-    const Spec a2plusb2 = sp_sqrt(t0 * t0 + (eta2 * 4.f) * etak2);
-    const Spec t1 = a2plusb2 + sp(cosThetaI2);
-    const Spec a = sp_sqrt((a2plusb2 + t0) * 0.5f);
-    const Spec t2 = a * (2.f * cosThetaI);
-    const Spec Rs = (t1 - t2) / (t1 + t2);
-    const Spec t3 = a2plusb2 * cosThetaI2 + sp(sinThetaI2 * sinThetaI2);
-    const Spec t4 = t2 * sinThetaI2;
-    const Spec Rp = (Rs * (t3 - t4)) / (t3 + t4);
-    return (Rp + Rs) * 0.5f;
-}
-// TrowbridgeReitzDistribution(alphax, alphay), microfacet.cpp:155-184, :310-345
-PG_DEV float tr2_D(float ax, float ay, V3 wh) {
-    float tan2Theta = tan2_theta(wh);
-    if (isinf(tan2Theta)) return 0.f;
-    const float cos4Theta = cos2_theta(wh) * cos2_theta(wh);
-    float e = (cos2_phi(wh) / (ax * ax) + sin2_phi(wh) / (ay * ay)) * tan2Theta;
-    return 1 / (PG_PI * ax * ay * cos4Theta * (1 + e) * (1 + e));
-}
-PG_DEV float tr2_lambda(float ax, float ay, V3 w) {
-    float absTanTheta = fabsf(tan_theta(w));
-    if (isinf(absTanTheta)) return 0.f;
-    float alpha = sqrtf(cos2_phi(w) * ax * ax + sin2_phi(w) * ay * ay);
-    float alpha2Tan2Theta = (alpha * absTanTheta) * (alpha * absTanTheta);
-    return (-1 + sqrtf(1.f + alpha2Tan2Theta)) / 2;
-}
-PG_DEV float tr2_G1(float ax, float ay, V3 w) { return 1 / (1 + tr2_lambda(ax, ay, w)); }
-PG_DEV float tr2_G(float ax, float ay, V3 wo, V3 wi) { return 1 / (1 + tr2_lambda(ax, ay, wo) + tr2_lambda(ax, ay, wi)); }
-PG_DEV float tr2_pdf(float ax, float ay, V3 wo, V3 wh) { return tr2_D(ax, ay, wh) * tr2_G1(ax, ay, wo) * absdot(wo, wh) / fabsf(wo.z); }
-PG_DEV V3 tr2_sample_wh(float ax, float ay, V3 wo, float u0, float u1) {
-    const bool flip = wo.z < 0;
-    V3 wi = flip ? -wo : wo;
-    V3 wiStretched = normalize(mk(ax * wi.x, ay * wi.y, wi.z));
-    float slope_x, slope_y;
-    tr_sample11(wiStretched.z, u0, u1, slope_x, slope_y);
-    float tmp = cos_phi(wiStretched) * slope_x - sin_phi(wiStretched) * slope_y;
-    slope_y = sin_phi(wiStretched) * slope_x + cos_phi(wiStretched) * slope_y;
-    slope_x = tmp;
-    slope_x = ax * slope_x;
-    slope_y = ay * slope_y;
-    V3 wh = normalize(mk(-slope_x, -slope_y, 1.f));
-    return flip ? -wh : wh;
-}
-PG_DEV bool same_hemisphere(V3 w, V3 wp) { return w.z * wp.z > 0; }  // reflection.h:111-113
-PG_DEV V3 reflect_about(V3 wo, V3 n) { return -wo + n * (2 * dot(wo, n)); }  // reflection.h:93-95
-PG_DEV bool refract_dir(V3 wi, V3 n, float eta, V3 &wt) {  // reflection.h:97-109
-    float cosThetaI = dot(n, wi);
-    float sin2ThetaI = pmax(0.f, 1 - cosThetaI * cosThetaI);
-    float sin2ThetaT = eta * eta * sin2ThetaI;
-    if (sin2ThetaT >= 1) return false;
-    float cosThetaT = sqrtf(1 - sin2ThetaT);
-    wt = (-wi) * eta + n * (eta * cosThetaI - cosThetaT);
-    return true;
-}
-PG_DEV int lobe_type(int type) {  // the BxDFType each constructor passes to BxDF()
-    switch (type) {
-    case PG_BXDF_LAMBERT_R: case PG_BXDF_OREN_NAYAR: return PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
-    case PG_BXDF_LAMBERT_T: return PG_BSDF_TRANSMISSION | PG_BSDF_DIFFUSE;
-    case PG_BXDF_SPECULAR_R: return PG_BSDF_REFLECTION | PG_BSDF_SPECULAR;
-    case PG_BXDF_SPECULAR_T: return PG_BSDF_TRANSMISSION | PG_BSDF_SPECULAR;
-    case PG_BXDF_FRESNEL_SPECULAR: return PG_BSDF_REFLECTION | PG_BSDF_TRANSMISSION | PG_BSDF_SPECULAR;
-    case PG_BXDF_MICROFACET_R: case PG_BXDF_FRESNEL_BLEND: return PG_BSDF_REFLECTION | PG_BSDF_GLOSSY;
-    case PG_BXDF_MICROFACET_T: return PG_BSDF_TRANSMISSION | PG_BSDF_GLOSSY;
-    }
-    return 0;
-}
-PG_DEV bool lobe_matches(int lobe, int t) { const int type = lobe_type(lobe); return (type & t) == type; }  // reflection.h:225
-template <class LB> PG_DEV Spec lobe_fresnel(const LB &b, float cosI) {  // Fresnel::Evaluate, reflection.cpp:120-135
-    const int kind = lobe_fresnel_kind(b);
-    if (kind == PG_FRESNEL_DIELECTRIC) return sp(fr_dielectric(cosI, b.eta_a, b.eta_b));
-    if (kind == PG_FRESNEL_CONDUCTOR) return fr_conductor(fabsf(cosI), sp(1.f), sp_of(b.cond_eta), sp_of(b.cond_k));
-    return sp(1.f);
-}
-PG_DEV float pow5f(float v) { return (v * v) * (v * v) * v; }
-template <class LB> PG_DEV Spec lobe_f(const LB &b, int lobe, V3 wo, V3 wi) {  // BxDF::f of the wrapped BxDF (lobe = b.type), local frame
-    const float ax = b.alpha_x, ay = b.alpha_y;
-    switch (lobe) {
-    case PG_BXDF_LAMBERT_R: return sp_of(b.R) * PG_INVPI;  // reflection.cpp:178-180
-    case PG_BXDF_LAMBERT_T: return sp_of(b.T) * PG_INVPI;  // :188-190
-    case PG_BXDF_OREN_NAYAR: {  // :197-219
-        float sinThetaI = sin_theta(wi), sinThetaO = sin_theta(wo);
-        float maxCos = 0;
-        if (sinThetaI > 1e-4f && sinThetaO > 1e-4f) {
-            float sinPhiI = sin_phi(wi), cosPhiI = cos_phi(wi);
-            float sinPhiO = sin_phi(wo), cosPhiO = cos_phi(wo);
-            float dCos = cosPhiI * cosPhiO + sinPhiI * sinPhiO;
-            maxCos = pmax(0.f, dCos);
-        }
-        float sinAlpha, tanBeta;
-        if (fabsf(wi.z) > fabsf(wo.z)) { sinAlpha = sinThetaO; tanBeta = sinThetaI / fabsf(wi.z); }
-        else { sinAlpha = sinThetaI; tanBeta = sinThetaO / fabsf(wo.z); }
-        return (sp_of(b.R) * PG_INVPI) * (b.on_a + b.on_b * maxCos * sinAlpha * tanBeta);
-    }
-    case PG_BXDF_MICROFACET_R: {  // :226-238
-        float cosThetaO = fabsf(wo.z), cosThetaI = fabsf(wi.z);
-        V3 wh = wi + wo;
-        if (cosThetaI == 0 || cosThetaO == 0) return sp(0);
-        if (wh.x == 0 && wh.y == 0 && wh.z == 0) return sp(0);
-        wh = normalize(wh);
-        V3 whf = (wh.z < 0.f) ? -wh : wh;  // Faceforward(wh, (0,0,1))
-        Spec F = lobe_fresnel(b, dot(wi, whf));
-        return (((sp_of(b.R) * tr2_D(ax, ay, wh)) * tr2_G(ax, ay, wo, wi)) * F) / (4 * cosThetaI * cosThetaO);
-    }
-    case PG_BXDF_MICROFACET_T: {  // :247-274, TransportMode::Radiance
-        if (same_hemisphere(wo, wi)) return sp(0);
-        float cosThetaO = wo.z, cosThetaI = wi.z;
-        if (cosThetaI == 0 || cosThetaO == 0) return sp(0);
-        float eta = wo.z > 0 ? (b.eta_b / b.eta_a) : (b.eta_a / b.eta_b);
-        V3 wh = normalize(wo + wi * eta);
-        if (wh.z < 0) wh = -wh;
-        if (dot(wo, wh) * dot(wi, wh) > 0) return sp(0);
-        Spec F = sp(fr_dielectric(dot(wo, wh), b.eta_a, b.eta_b));
-        float sqrtDenom = dot(wo, wh) + eta * dot(wi, wh);
-        float factor = 1 / eta;
-        return ((sp(1.f) - F) * sp_of(b.T)) *
-               fabsf(tr2_D(ax, ay, wh) * tr2_G(ax, ay, wo, wi) * eta * eta * absdot(wi, wh) * absdot(wo, wh) * factor * factor /
-                     (cosThetaI * cosThetaO * sqrtDenom * sqrtDenom));
-    }
-    case PG_BXDF_FRESNEL_BLEND: {  // :295-310; Rd = R, Rs = T
-        const Spec Rd = sp_of(b.R), Rs = sp_of(b.T);
-        Spec diffuse = (((Rd * (28.f / (23.f * PG_PI))) * (sp(1.f) - Rs)) * (1 - pow5f(1 - .5f * fabsf(wi.z)))) * (1 - pow5f(1 - .5f * fabsf(wo.z)));
-        V3 wh = wi + wo;
-        if (wh.x == 0 && wh.y == 0 && wh.z == 0) return sp(0);
-        wh = normalize(wh);
-        Spec schlick = Rs + (sp(1.f) - Rs) * pow5f(1 - dot(wi, wh));  // SchlickFresnel, reflection.h:496-499
-        Spec specular = schlick * (tr2_D(ax, ay, wh) / (4 * absdot(wi, wh) * pmax(fabsf(wi.z), fabsf(wo.z))));
-        return diffuse + specular;
-    }
-    }
-    return sp(0);  // specular BxDFs: f() = 0
-}
-template <class LB> PG_DEV float lobe_pdf(const LB &b, int lobe, V3 wo, V3 wi) {
-    const float ax = b.alpha_x, ay = b.alpha_y;
-    switch (lobe) {
-    case PG_BXDF_LAMBERT_R: case PG_BXDF_OREN_NAYAR: return same_hemisphere(wo, wi) ? fabsf(wi.z) * PG_INVPI : 0;  // :392-394
-    case PG_BXDF_LAMBERT_T: return !same_hemisphere(wo, wi) ? fabsf(wi.z) * PG_INVPI : 0;  // :405-408
-    case PG_BXDF_MICROFACET_R: {  // :425-429
-        if (!same_hemisphere(wo, wi)) return 0;
-        V3 wh = normalize(wo + wi);
-        return tr2_pdf(ax, ay, wo, wh) / (4 * dot(wo, wh));
-    }
-    case PG_BXDF_MICROFACET_T: {  // :444-458
-        if (same_hemisphere(wo, wi)) return 0;
-        float eta = wo.z > 0 ? (b.eta_b / b.eta_a) : (b.eta_a / b.eta_b);
-        V3 wh = normalize(wo + wi * eta);
-        if (dot(wo, wh) * dot(wi, wh) > 0) return 0;
-        float sqrtDenom = dot(wo, wh) + eta * dot(wi, wh);
-        float dwh_dwi = fabsf((eta * eta * dot(wi, wh)) / (sqrtDenom * sqrtDenom));
-        return tr2_pdf(ax, ay, wo, wh) * dwh_dwi;
-    }
-    case PG_BXDF_FRESNEL_BLEND: {  // :480-485
-        if (!same_hemisphere(wo, wi)) return 0;
-        V3 wh = normalize(wo + wi);
-        float pdf_wh = tr2_pdf(ax, ay, wo, wh);
-        return .5f * (fabsf(wi.z) * PG_INVPI + pdf_wh / (4 * dot(wo, wh)));
-    }
-    }
-    return 0;
-}
-// BxDF::Sample_f of the wrapped BxDF; pdf keeps the caller's 0 on the reference's early `return 0` paths.  wantF = false: the
-// value of a NON-specular BxDF is not computed (0 is returned) -- BSDF::Sample_f throws it away and sums f() over all matching
-// BxDFs instead (reflection.cpp:768-775); direction, pdf and the specular BxDFs' values are what they always are
-template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &wi, float u0, float u1, float &pdf, int &sampledType, bool wantF = true) {
-    const float ax = b.alpha_x, ay = b.alpha_y;
-    switch (lobe) {
-    case PG_BXDF_LAMBERT_R: case PG_BXDF_OREN_NAYAR:  // BxDF::Sample_f, :383-390
-        wi = cosine_sample_hemisphere(u0, u1);
-        if (wo.z < 0) wi.z *= -1;
-        pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
-    case PG_BXDF_LAMBERT_T:  // :396-403
-        wi = cosine_sample_hemisphere(u0, u1);
-        if (wo.z > 0) wi.z *= -1;
-        pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
-    case PG_BXDF_SPECULAR_R:  // :136-143
-        wi = mk(-wo.x, -wo.y, wo.z);
-        pdf = 1;
-        return (lobe_fresnel(b, wi.z) * sp_of(b.R)) / fabsf(wi.z);
-    case PG_BXDF_SPECULAR_T: {  // :151-167
-        const bool entering = wo.z > 0;
-        const float etaI = entering ? b.eta_a : b.eta_b, etaT = entering ? b.eta_b : b.eta_a;
-        const V3 n = (wo.z < 0.f) ? mk(0, 0, -1) : mk(0, 0, 1);
-        if (!refract_dir(wo, n, etaI / etaT, wi)) return sp(0);
-        pdf = 1;
-        Spec ft = sp_of(b.T) * (sp(1.f) - sp(fr_dielectric(wi.z, b.eta_a, b.eta_b)));
-        ft = ft * ((etaI * etaI) / (etaT * etaT));
-        return ft / fabsf(wi.z);
-    }
-    case PG_BXDF_FRESNEL_SPECULAR: {  // :487-521
-        const float F = fr_dielectric(wo.z, b.eta_a, b.eta_b);
-        if (u0 < F) {
-            wi = mk(-wo.x, -wo.y, wo.z);
-            sampledType = PG_BSDF_SPECULAR | PG_BSDF_REFLECTION;
-            pdf = F;
-            return (sp_of(b.R) * F) / fabsf(wi.z);
-        }
-        const bool entering = wo.z > 0;
-        const float etaI = entering ? b.eta_a : b.eta_b, etaT = entering ? b.eta_b : b.eta_a;
-        const V3 n = (wo.z < 0.f) ? mk(0, 0, -1) : mk(0, 0, 1);
-        if (!refract_dir(wo, n, etaI / etaT, wi)) return sp(0);
-        Spec ft = sp_of(b.T) * (1 - F);
-        ft = ft * ((etaI * etaI) / (etaT * etaT));
-        sampledType = PG_BSDF_SPECULAR | PG_BSDF_TRANSMISSION;
-        pdf = 1 - F;
-        return ft / fabsf(wi.z);
-    }
-    case PG_BXDF_MICROFACET_R: {  // :410-423
-        if (wo.z == 0) return sp(0);
-        V3 wh = tr2_sample_wh(ax, ay, wo, u0, u1);
-        if (dot(wo, wh) < 0) return sp(0);
-        wi = reflect_about(wo, wh);
-        if (!same_hemisphere(wo, wi)) return sp(0);
-        pdf = tr2_pdf(ax, ay, wo, wh) / (4 * dot(wo, wh));
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
-    }
-    case PG_BXDF_MICROFACET_T: {  // :431-442
-        if (wo.z == 0) return sp(0);
-        V3 wh = tr2_sample_wh(ax, ay, wo, u0, u1);
-        if (dot(wo, wh) < 0) return sp(0);
-        float eta = wo.z > 0 ? (b.eta_a / b.eta_b) : (b.eta_b / b.eta_a);
-        if (!refract_dir(wo, wh, eta, wi)) return sp(0);
-        pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
-    }
-    case PG_BXDF_FRESNEL_BLEND: {  // :460-478
-        if ((double)u0 < .5) {
-            u0 = pmin(2 * u0, PG_ONE_MINUS_EPS);
-            wi = cosine_sample_hemisphere(u0, u1);
-            if (wo.z < 0) wi.z *= -1;
-        } else {
-            u0 = pmin(2 * (u0 - .5f), PG_ONE_MINUS_EPS);
-            V3 wh = tr2_sample_wh(ax, ay, wo, u0, u1);
-            wi = reflect_about(wo, wh);
-            if (!same_hemisphere(wo, wi)) return sp(0);
-        }
-        pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
-    }
-    }
-    return sp(0);
-}
-PG_DEV Spec lobe_scale(const PgBxDF &b, Spec f, int) {  // ScaledBxDF, reflection.cpp:98-107: innermost wrapper first
-    for (int i = 0; i < b.n_scales; ++i) f = sp_of(b.scale[i]) * f;
-    return f;
-}
-PG_DEV Spec lobe_scale(const PkLobe &b, Spec f, int recStride) {  // the factors: nine floats in the record behind the lobe's (half a lobe's stride on: a scaled list has two records per lobe)
-    const float *sc = reinterpret_cast<const float *>(&b + (recStride >> 1));
-    const int n = (int)((b.hdr >> 6) & 3u);
-    for (int i = 0; i < n; ++i) f = sp_of(sc + 3 * i) * f;
-    return f;
-}
-template <class LB> PG_DEV int lbsdf_num_components(const LobeBsdfT<LB> &b, int flags) {  // reflection.cpp:672-678
-    int num = 0;
-    for (int i = 0; i < b.n; ++i) if (lobe_matches(lbsdf_lobe(b, i), flags)) ++num;
-    return num;
-}
-template <class LB> PG_DEV Spec lbsdf_scaled(const LobeBsdfT<LB> &b, int i, Spec f) {
-    if (!((b.scaled >> i) & 1u)) return f;
-    const auto &L = lobe_at(b, i);
-    return lobe_scale(L, f, b.recStride);
-}
-// BxDF::f and BxDF::Pdf of one BxDF for the same pair of directions.  Each value is what lobe_f / lobe_pdf compute -- the same
-// operations in the same order --, but the microfacet BxDFs' half vector, D(wh) and Lambda(wo) are computed once for both (a path
-// vertex asks for f AND pdf of the other matching BxDFs inside both of its BSDF::Sample_f calls.  For the light's direction BSDF::f and
-// BSDF::Pdf stay two walks: fused there as well the kernel gained nothing on microfacet scenes and lost 20 % on an all-Lambert one --
-// a matter of what the register allocator makes of it, profiles/r04l_*).
-template <class LB> PG_DEV void lobe_f_pdf(const LB &b, int lobe, V3 wo, V3 wi, bool wantF, bool wantPdf, Spec &f, float &pdf) {
-    const float ax = b.alpha_x, ay = b.alpha_y;
-    f = sp(0); pdf = 0;
-    switch (lobe) {
-    case PG_BXDF_MICROFACET_R: {  // reflection.cpp:226-238, :425-429
-        V3 wh = wi + wo;  // (= wo + wi of Pdf: the same three sums)
-        const bool whZero = wh.x == 0 && wh.y == 0 && wh.z == 0;
-        wh = normalize(wh);
-        const float D = tr2_D(ax, ay, wh), lambdaO = tr2_lambda(ax, ay, wo);
-        if (wantPdf && same_hemisphere(wo, wi)) pdf = (D * (1 / (1 + lambdaO)) * absdot(wo, wh) / fabsf(wo.z)) / (4 * dot(wo, wh));
-        if (wantF) {
-            const float cosThetaO = fabsf(wo.z), cosThetaI = fabsf(wi.z);
-            if (!(cosThetaI == 0 || cosThetaO == 0 || whZero)) {
-                const V3 whf = (wh.z < 0.f) ? -wh : wh;  // Faceforward(wh, (0,0,1))
-                const Spec F = lobe_fresnel(b, dot(wi, whf));
-                f = (((sp_of(b.R) * D) * (1 / (1 + lambdaO + tr2_lambda(ax, ay, wi)))) * F) / (4 * cosThetaI * cosThetaO);
-            }
-        }
-        return;
-    }
-    case PG_BXDF_FRESNEL_BLEND: {  // :295-310, :480-485
-        V3 wh = wi + wo;
-        const bool whZero = wh.x == 0 && wh.y == 0 && wh.z == 0;
-        wh = normalize(wh);
-        const float D = tr2_D(ax, ay, wh);
-        if (wantPdf && same_hemisphere(wo, wi)) {
-            const float pdf_wh = D * tr2_G1(ax, ay, wo) * absdot(wo, wh) / fabsf(wo.z);
-            pdf = .5f * (fabsf(wi.z) * PG_INVPI + pdf_wh / (4 * dot(wo, wh)));
-        }
-        if (wantF && !whZero) {
-            const Spec Rd = sp_of(b.R), Rs = sp_of(b.T);
-            const Spec diffuse = (((Rd * (28.f / (23.f * PG_PI))) * (sp(1.f) - Rs)) * (1 - pow5f(1 - .5f * fabsf(wi.z)))) * (1 - pow5f(1 - .5f * fabsf(wo.z)));
-            const Spec schlick = Rs + (sp(1.f) - Rs) * pow5f(1 - dot(wi, wh));
-            f = diffuse + schlick * (D / (4 * absdot(wi, wh) * pmax(fabsf(wi.z), fabsf(wo.z))));
-        }
-        return;
-    }
-    }
-    if (wantF) f = lobe_f(b, lobe, wo, wi);
-    if (wantPdf) pdf = lobe_pdf(b, lobe, wo, wi);
-}
-template <class LB> PG_DEV Spec lbsdf_f_local(const LobeBsdfT<LB> &b, V3 wo, V3 wi, bool reflect, int flags) {
-    Spec f = sp(0);
-    for (int i = 0; i < b.n; ++i) {
-        const int lobe = lbsdf_lobe(b, i), type = lobe_type(lobe);
-        if ((type & flags) == type && ((reflect && (type & PG_BSDF_REFLECTION)) || (!reflect && (type & PG_BSDF_TRANSMISSION))))
-            { const auto &L = lobe_at(b, i); f = f + lbsdf_scaled(b, i, lobe_f(L, lobe, wo, wi)); }
-    }
-    return f;
-}
-template <class LB> PG_DEV Spec lbsdf_f(const LobeBsdfT<LB> &b, V3 woW, V3 wiW, int flags) {  // reflection.cpp:680-693
-    V3 wi = world_to_local(b, wiW), wo = world_to_local(b, woW);
-    if (wo.z == 0) return sp(0);
-    return lbsdf_f_local(b, wo, wi, dot(wiW, b.ng) * dot(woW, b.ng) > 0, flags);
-}
-template <class LB> PG_DEV float lbsdf_pdf(const LobeBsdfT<LB> &b, V3 woW, V3 wiW, int flags) {  // reflection.cpp:781-796
-    if (b.n == 0) return 0.f;
-    V3 wo = world_to_local(b, woW), wi = world_to_local(b, wiW);
-    if (wo.z == 0) return 0.f;
-    float pdf = 0.f;
-    int matchingComps = 0;
-    for (int i = 0; i < b.n; ++i) {
-        const int lobe = lbsdf_lobe(b, i);
-        if (lobe_matches(lobe, flags)) { ++matchingComps; const auto &L = lobe_at(b, i); pdf += lobe_pdf(L, lobe, wo, wi); }
-    }
-    return matchingComps > 0 ? pdf / matchingComps : 0.f;
-}
-// BSDF::Sample_f, reflection.cpp:714-779: returns f, pdf = 0 when there is no sample
-template <class LB> PG_DEV Spec lbsdf_sample_f(const LobeBsdfT<LB> &b, V3 woWorld, V3 &wiWorld, float u0, float u1, float &pdf, int flags, int &sampledType) {
-    const int matchingComps = lbsdf_num_components(b, flags);
-    sampledType = 0;
-    pdf = 0;
-    if (matchingComps == 0) return sp(0);
-    int comp = (int)floorf(u0 * matchingComps);
-    if (comp > matchingComps - 1) comp = matchingComps - 1;
-    int chosen = 0, count = comp;
-    for (int i = 0; i < b.n; ++i)
-        if (lobe_matches(lbsdf_lobe(b, i), flags) && count-- == 0) { chosen = i; break; }
-    const auto &bxdf = lobe_at(b, chosen);
-    const int chosenLobe = lbsdf_lobe(b, chosen);
-    const float uR0 = pmin(u0 * matchingComps - comp, PG_ONE_MINUS_EPS);
-    V3 wi = mk(0, 0, 0), wo = world_to_local(b, woWorld);
-    if (wo.z == 0) return sp(0);
-    sampledType = lobe_type(chosenLobe);
-    const bool bxdfSpecular = (sampledType & PG_BSDF_SPECULAR) != 0;
-    Spec f = lbsdf_scaled(b, chosen, lobe_sample_f(bxdf, chosenLobe, wo, wi, uR0, u1, pdf, sampledType, bxdfSpecular));
-    if (pdf == 0) { sampledType = 0; return sp(0); }
-    wiWorld = local_to_world(b, wi);
-    if (!bxdfSpecular) {  // :760-775: the other matching BxDFs' pdfs, and f over all matching BxDFs of the hemisphere the pair is in
-        const bool reflect = dot(wiWorld, b.ng) * dot(woWorld, b.ng) > 0;
-        f = sp(0);
-        for (int i = 0; i < b.n; ++i) {
-            const int lobe = lbsdf_lobe(b, i), type = lobe_type(lobe);
-            if ((type & flags) != type) continue;
-            const bool wantPdf = matchingComps > 1 && i != chosen;
-            const bool wantF = (reflect && (type & PG_BSDF_REFLECTION)) || (!reflect && (type & PG_BSDF_TRANSMISSION));
-            if (!(wantPdf || wantF)) continue;
-            Spec fi;
-            float pi;
-            { const auto &L = lobe_at(b, i); lobe_f_pdf(L, lobe, wo, wi, wantF, wantPdf, fi, pi); }
-            if (wantPdf) pdf += pi;
-            if (wantF) f = f + lbsdf_scaled(b, i, fi);
-        }
-    }
-    if (matchingComps > 1) pdf /= matchingComps;
-    return f;
-}
-
-PG_DEV Spec sp_clamp0(Spec v) { return sp3(v.r < 0 ? 0 : v.r, v.g < 0 ? 0 : v.g, v.b < 0 ? 0 : v.b); }  // Spectrum::Clamp()
-PG_DEV void lobe_init(PgBxDF &b, int type) {
-    b.type = type; b.fresnel = PG_FRESNEL_NOOP; b.eta_a = b.eta_b = 1; b.alpha_x = b.alpha_y = 1; b.on_a = 1; b.on_b = 0; b.n_scales = 0;
-    for (int i = 0; i < 3; ++i) { b.R[i] = b.T[i] = b.cond_eta[i] = b.cond_k[i] = 0; }
-}
-PG_DEV void lobe_set(float *dst, Spec v) { dst[0] = v.r; dst[1] = v.g; dst[2] = v.b; }
-PG_DEV float roughness_to_alpha(float roughness) {  // microfacet.h:127-132; std::log evaluated in double, rounded once
-    roughness = pmax(roughness, 1e-3f);
-    const float x = pg_logf(roughness);
-    return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
-}
-PG_DEV void lobe_tr(PgBxDF &b, float ax, float ay) { b.alpha_x = pmax(0.001f, ax); b.alpha_y = pmax(0.001f, ay); }  // microfacet.h:109-113
-// Material::ComputeScatteringFunctions of material `mat` at this hit (materials/): appends its BxDFs to out[n...]; eta receives
-// BSDF::eta.  D bounds the nesting of mix materials; cap = the room in out[] (PG_MAX_BXDFS, or the scene's largest list when the
-// list goes to k_material's buffer).
-// Where MatEval puts a BxDF list: an array of PgBxDFs (the shading kernel's own, MODE 2) or k_material's packed records (LobeBsdfT)
-struct LobeOutRaw {
-    PgBxDF *p;
-    PG_DEV void put(int i, const PgBxDF &b) const { p[i] = b; }
-    PG_DEV void add_scale(int i, Spec s) const { if (p[i].n_scales < PG_MAX_BXDF_SCALES) { lobe_set(p[i].scale[p[i].n_scales], s); p[i].n_scales++; } }
-};
-struct LobeOutPacked {
-    float4 *rec;    // record 0 of this thread's list; record r lies r planes on (MatPre)
-    int recStride;  // 2: the hit's material is a mix, every lobe is followed by the record of its scale factors
-    int plane;      // records per plane = the queue's entries
-    PG_DEV void put(int i, const PgBxDF &b) const {
-        float4 *q = rec + 3 * ((size_t)(i * recStride) * plane);
-        pg_pack_lobe(b, reinterpret_cast<float *>(q));
-        if (recStride == 2) pg_pack_lobe_scales(b, reinterpret_cast<float *>(q + 3 * (size_t)plane));
-    }
-    PG_DEV void add_scale(int i, Spec s) const {  // ScaledBxDF around lobe i (mixmat.cpp:60-65): the next free factor of its scale record
-        float4 *q = rec + 3 * ((size_t)(i * recStride) * plane);
-        const unsigned hdr = __float_as_uint(q[0].x), ns = (hdr >> 6) & 3u;
-        if (ns < PG_MAX_BXDF_SCALES) {
-            float *f = reinterpret_cast<float *>(q + 3 * (size_t)plane) + 3 * ns;
-            f[0] = s.r; f[1] = s.g; f[2] = s.b;
-            q[0].x = __uint_as_float(hdr + (1u << 6));
-        }
-    }
-};
-template <int D, int W = 0, class OUT = LobeOutRaw> struct MatEval {
-    static PG_DEV_CALL void run(const DScene &sc, int mat, const TexHit &h, OUT out, int &n, float &eta, int capArg) {
-        const int cap = W == 0 ? PG_MAX_BXDFS : capArg;  // (the shading kernel's own copies: a constant, no register held for it)
-        const PgMaterial &m = sc.materials[mat];
-        if (m.type != PG_MAT_TEXTURED) {  // constant parameters: the list the host built
-            for (int i = 0; i < m.n_bxdfs && n < cap; ++i) out.put(n++, sc.bxdfs[m.first_bxdf + i]);
-            eta = m.bsdf_eta;
-            return;
-        }
-        const PgTexturedMaterial &tm = sc.textured[m.textured_index];
-        auto TS = [&](int i) { return TexEval<PG_TEX_DEPTH, W>::s(sc, tm.s[i], h); };
-        auto TF = [&](int i) { return TexEval<PG_TEX_DEPTH, W>::f(sc, tm.f[i], h); };
-        auto push = [&](const PgBxDF &b) { if (n < cap) out.put(n++, b); };
-        PgBxDF b;
-        eta = 1;
-        switch (tm.kind) {
-        case PG_KIND_MATTE: {  // matte.cpp:45-62
-            const Spec r = sp_clamp0(TS(0));
-            const float sig = clampf(TF(0), 0, 90);
-            if (!is_black(r)) {
-                lobe_init(b, sig == 0 ? PG_BXDF_LAMBERT_R : PG_BXDF_OREN_NAYAR);
-                lobe_set(b.R, r);
-                if (sig != 0) {
-                    const float sigma = (PG_PI / 180) * sig, sigma2 = sigma * sigma;
-                    b.on_a = 1.f - (sigma2 / (2.f * (sigma2 + 0.33f)));
-                    b.on_b = 0.45f * sigma2 / (sigma2 + 0.09f);
-                }
-                push(b);
-            }
-            break;
-        }
-        case PG_KIND_PLASTIC: {  // plastic.cpp:45-70
-            const Spec kd = sp_clamp0(TS(0));
-            if (!is_black(kd)) { lobe_init(b, PG_BXDF_LAMBERT_R); lobe_set(b.R, kd); push(b); }
-            const Spec ks = sp_clamp0(TS(1));
-            if (!is_black(ks)) {
-                lobe_init(b, PG_BXDF_MICROFACET_R); lobe_set(b.R, ks);
-                b.fresnel = PG_FRESNEL_DIELECTRIC; b.eta_a = 1.5f; b.eta_b = 1.f;
-                float rough = TF(0);
-                if (tm.remap_roughness) rough = roughness_to_alpha(rough);
-                lobe_tr(b, rough, rough);
-                push(b);
-            }
-            break;
-        }
-        case PG_KIND_MIRROR: {  // mirror.cpp:44-56
-            const Spec R = sp_clamp0(TS(0));
-            if (!is_black(R)) { lobe_init(b, PG_BXDF_SPECULAR_R); lobe_set(b.R, R); push(b); }
-            break;
-        }
-        case PG_KIND_GLASS: {  // glass.cpp:45-96
-            const float e = TF(2);
-            float urough = TF(0), vrough = TF(1);
-            const Spec R = sp_clamp0(TS(0)), T = sp_clamp0(TS(1));
-            eta = e;
-            if (is_black(R) && is_black(T)) break;
-            if (urough == 0 && vrough == 0) { lobe_init(b, PG_BXDF_FRESNEL_SPECULAR); lobe_set(b.R, R); lobe_set(b.T, T); b.eta_a = 1.f; b.eta_b = e; push(b); }
-            else {
-                if (tm.remap_roughness) { urough = roughness_to_alpha(urough); vrough = roughness_to_alpha(vrough); }
-                if (!is_black(R)) { lobe_init(b, PG_BXDF_MICROFACET_R); lobe_set(b.R, R); b.fresnel = PG_FRESNEL_DIELECTRIC; b.eta_a = 1.f; b.eta_b = e; lobe_tr(b, urough, vrough); push(b); }
-                if (!is_black(T)) { lobe_init(b, PG_BXDF_MICROFACET_T); lobe_set(b.T, T); b.eta_a = 1.f; b.eta_b = e; lobe_tr(b, urough, vrough); push(b); }
-            }
-            break;
-        }
-        case PG_KIND_UBER: {  // uber.cpp:45-101
-            const float e = TF(3);
-            const Spec op = sp_clamp0(TS(4));
-            const Spec t = sp_clamp0(op * -1.f + sp(1.f));
-            if (!is_black(t)) { lobe_init(b, PG_BXDF_SPECULAR_T); lobe_set(b.T, t); push(b); eta = 1.f; }
-            else eta = e;
-            const Spec kd = op * sp_clamp0(TS(0));
-            if (!is_black(kd)) { lobe_init(b, PG_BXDF_LAMBERT_R); lobe_set(b.R, kd); push(b); }
-            const Spec ks = op * sp_clamp0(TS(1));
-            if (!is_black(ks)) {
-                float roughu = tm.has_u ? TF(1) : TF(0);
-                float roughv = tm.has_v ? TF(2) : roughu;
-                if (tm.remap_roughness) { roughu = roughness_to_alpha(roughu); roughv = roughness_to_alpha(roughv); }
-                lobe_init(b, PG_BXDF_MICROFACET_R); lobe_set(b.R, ks); b.fresnel = PG_FRESNEL_DIELECTRIC; b.eta_a = 1.f; b.eta_b = e; lobe_tr(b, roughu, roughv);
-                push(b);
-            }
-            const Spec kr = op * sp_clamp0(TS(2));
-            if (!is_black(kr)) { lobe_init(b, PG_BXDF_SPECULAR_R); lobe_set(b.R, kr); b.fresnel = PG_FRESNEL_DIELECTRIC; b.eta_a = 1.f; b.eta_b = e; push(b); }
-            const Spec kt = op * sp_clamp0(TS(3));
-            if (!is_black(kt)) { lobe_init(b, PG_BXDF_SPECULAR_T); lobe_set(b.T, kt); b.eta_a = 1.f; b.eta_b = e; push(b); }
-            break;
-        }
-        case PG_KIND_METAL: {  // metal.cpp:61-82
-            float uRough = tm.has_u ? TF(1) : TF(0);
-            float vRough = tm.has_v ? TF(2) : TF(0);
-            if (tm.remap_roughness) { uRough = roughness_to_alpha(uRough); vRough = roughness_to_alpha(vRough); }
-            lobe_init(b, PG_BXDF_MICROFACET_R);
-            lobe_set(b.R, sp(1.f));
-            b.fresnel = PG_FRESNEL_CONDUCTOR;
-            lobe_set(b.cond_eta, TS(0)); lobe_set(b.cond_k, TS(1));
-            lobe_tr(b, uRough, vRough);
-            push(b);
-            break;
-        }
-        case PG_KIND_SUBSTRATE: {  // substrate.cpp:45-65
-            const Spec d = sp_clamp0(TS(0)), s2 = sp_clamp0(TS(1));
-            float roughu = TF(0), roughv = TF(1);
-            if (!is_black(d) || !is_black(s2)) {
-                if (tm.remap_roughness) { roughu = roughness_to_alpha(roughu); roughv = roughness_to_alpha(roughv); }
-                lobe_init(b, PG_BXDF_FRESNEL_BLEND); lobe_set(b.R, d); lobe_set(b.T, s2); lobe_tr(b, roughu, roughv); push(b);
-            }
-            break;
-        }
-        case PG_KIND_TRANSLUCENT: {  // translucent.cpp:45-80
-            const float e = 1.5f;
-            eta = e;
-            const Spec r = sp_clamp0(TS(2)), t = sp_clamp0(TS(3));
-            if (is_black(r) && is_black(t)) break;
-            const Spec kd = sp_clamp0(TS(0));
-            if (!is_black(kd)) {
-                if (!is_black(r)) { lobe_init(b, PG_BXDF_LAMBERT_R); lobe_set(b.R, r * kd); push(b); }
-                if (!is_black(t)) { lobe_init(b, PG_BXDF_LAMBERT_T); lobe_set(b.T, t * kd); push(b); }
-            }
-            const Spec ks = sp_clamp0(TS(1));
-            if (!is_black(ks) && (!is_black(r) || !is_black(t))) {
-                float rough = TF(0);
-                if (tm.remap_roughness) rough = roughness_to_alpha(rough);
-                if (!is_black(r)) { lobe_init(b, PG_BXDF_MICROFACET_R); lobe_set(b.R, r * ks); b.fresnel = PG_FRESNEL_DIELECTRIC; b.eta_a = 1.f; b.eta_b = e; lobe_tr(b, rough, rough); push(b); }
-                if (!is_black(t)) { lobe_init(b, PG_BXDF_MICROFACET_T); lobe_set(b.T, t * ks); b.eta_a = 1.f; b.eta_b = e; lobe_tr(b, rough, rough); push(b); }
-            }
-            break;
-        }
-        case PG_KIND_MIX: {  // mixmat.cpp:45-65
-            const Spec s1 = sp_clamp0(TS(0));
-            const Spec s2 = sp_clamp0(sp(1.f) - s1);
-            for (int j = 0; j < 2; ++j) {
-                const int first = n;
-                float subEta = 1;
-                MatEval<D - 1, W, OUT>::run(sc, tm.sub[j], h, out, n, subEta, cap);
-                if (j == 0) eta = subEta;  // si->bsdf stays m1's
-                const Spec scl = j == 0 ? s1 : s2;
-                for (int i = first; i < n; ++i) out.add_scale(i, scl);
-            }
-            break;
-        }
-        }
-    }
-};
-template <int W, class OUT> struct MatEval<0, W, OUT> {  // below the deepest mix the host allows: only constant-parameter materials
-    static PG_DEV void run(const DScene &sc, int mat, const TexHit &, OUT out, int &n, float &eta, int capArg) {
-        const int cap = W == 0 ? PG_MAX_BXDFS : capArg;
-        const PgMaterial &m = sc.materials[mat];
-        for (int i = 0; i < m.n_bxdfs && n < cap; ++i) out.put(n++, sc.bxdfs[m.first_bxdf + i]);
-        eta = m.bsdf_eta;
-    }
-};
-
-struct LightSample { V3 p, n, pError; };
-// SpotLight::Falloff, spot.cpp:62-72
-PG_DEV float spot_falloff(const PgLight &l, V3 w) {
-    V3 wl = normalize(mk(l.w2l[0] * w.x + l.w2l[1] * w.y + l.w2l[2] * w.z, l.w2l[3] * w.x + l.w2l[4] * w.y + l.w2l[5] * w.z,
-                         l.w2l[6] * w.x + l.w2l[7] * w.y + l.w2l[8] * w.z));  // Transform::operator()(Vector3), transform.h:233-239
-    float cosTheta = wl.z;
-    if (cosTheta < l.cos_total_width) return 0;
-    if (cosTheta >= l.cos_falloff_start) return 1;
-    float delta = (cosTheta - l.cos_total_width) / (l.cos_falloff_start - l.cos_total_width);
-    return (delta * delta) * (delta * delta);
-}
-// ---- Sphere as the shape of a DiffuseAreaLight: Sphere::Sample / ::Pdf, shapes/sphere.cpp:205-305
-PG_DEV bool sphere_ref_inside(const PgSphere &s, V3 refp, V3 refErr, V3 refn) {  // sphere.cpp:223-226, :294-297
-    const V3 pCenter = m4_point(s.o2w, mk(0, 0, 0));
-    const V3 pOrigin = offset_ray_origin(refp, refErr, refn, pCenter - refp);
-    return lensq(pOrigin - pCenter) <= s.radius * s.radius;
-}
-PG_DEV float sphere_cone_pdf(const PgSphere &s, V3 refp) {  // sphere.cpp:301-304, UniformConePdf sampling.cpp:132-134
-    const V3 pCenter = m4_point(s.o2w, mk(0, 0, 0));
-    const float sinThetaMax2 = s.radius * s.radius / lensq(refp - pCenter);
-    const float cosThetaMax = sqrtf(pmax(0.f, 1 - sinThetaMax2));
-    return 1 / (2 * PG_PI * (1 - cosThetaMax));
-}
-PG_DEV LightSample sphere_sample(const PgSphere &s, V3 refp, V3 refErr, V3 refn, float u0, float u1, float &pdf) {
-    LightSample it;
-    const float radius = s.radius;
-    const V3 pCenter = m4_point(s.o2w, mk(0, 0, 0));
-    if (sphere_ref_inside(s, refp, refErr, refn)) {  // uniform over the area (sphere.cpp:205-217), then to solid angle (:227-239)
-        const float z = 1 - 2 * u0;  // UniformSampleSphere, sampling.cpp:98-103
-        const float r = sqrtf(pmax(0.f, 1.f - z * z));
-        const float phi = 2 * PG_PI * u1;
-        float sP, cP;
-        pg_sincosf(phi, &sP, &cP);
-        V3 pObj = mk(r * (float)cP, r * (float)sP, z) * radius;
-        it.n = normalize(m4_normal(s.w2o, pObj));
-        if (s.reverse_orientation) it.n = it.n * -1.f;
-        pObj = pObj * (radius / sqrtf(lensq(pObj)));
-        it.p = m4_point_err2(s.o2w, pObj, vabs(pObj) * pgamma(5), it.pError);
-        pdf = 1 / (s.phi_max * radius * (s.z_max - s.z_min));
-        V3 wi = it.p - refp;
-        if (lensq(wi) == 0) pdf = 0;
-        else {
-            wi = normalize(wi);
-            pdf *= lensq(refp - it.p) / absdot(it.n, -wi);
-        }
-        if (isinf(pdf)) pdf = 0.f;
-        return it;
-    }
-    // uniformly inside the subtended cone, sphere.cpp:241-289
-    const float dc = sqrtf(lensq(refp - pCenter));
-    const float invDc = 1 / dc;
-    const V3 wc = (pCenter - refp) * invDc;
-    V3 wcX, wcY;
-    coordinate_system(wc, wcX, wcY);
-    const float sinThetaMax = radius * invDc;
-    const float sinThetaMax2 = sinThetaMax * sinThetaMax;
-    const float invSinThetaMax = 1 / sinThetaMax;
-    const float cosThetaMax = sqrtf(pmax(0.f, 1 - sinThetaMax2));
-    float cosTheta = (cosThetaMax - 1) * u0 + 1;
-    float sinTheta2 = 1 - cosTheta * cosTheta;
-    if (sinThetaMax2 < 0.00068523f) {  // sin^2(1.5 deg): the reference's small-angle series
-        sinTheta2 = sinThetaMax2 * u0;
-        cosTheta = sqrtf(1 - sinTheta2);
-    }
-    const float cosAlpha = sinTheta2 * invSinThetaMax + cosTheta * sqrtf(pmax(0.f, 1.f - sinTheta2 * invSinThetaMax * invSinThetaMax));
-    const float sinAlpha = sqrtf(pmax(0.f, 1.f - cosAlpha * cosAlpha));
-    const float phi = u1 * 2 * PG_PI;
-    float sP, cP;
-    pg_sincosf(phi, &sP, &cP);
-    // SphericalDirection(sinAlpha, cosAlpha, phi, -wcX, -wcY, -wc), geometry.h:1461-1466
-    const V3 nWorld = (-wcX) * (sinAlpha * (float)cP) + (-wcY) * (sinAlpha * (float)sP) + (-wc) * cosAlpha;
-    const V3 pWorld = pCenter + nWorld * radius;
-    it.p = pWorld;
-    it.pError = vabs(pWorld) * pgamma(5);
-    it.n = nWorld;
-    if (s.reverse_orientation) it.n = it.n * -1.f;
-    pdf = 1 / (2 * PG_PI * (1 - cosThetaMax));
-    return it;
-}
-
-// Cylinder::Sample(u, pdf), cylinder.cpp:208-223; Disk::Sample(u, pdf), disk.cpp:128-137
-PG_DEV LightSample quadric_sample_area(const PgSphere &s, float u0, float u1, float &pdf) {
-    LightSample it;
-    if (s.shape == PG_SHAPE_CYLINDER) {
-        const float z = plerp(u0, s.z_min, s.z_max);
-        const float phi = u1 * s.phi_max;
-        float sP, cP;
-        pg_sincosf(phi, &sP, &cP);
-        V3 pObj = mk(s.radius * (float)cP, s.radius * (float)sP, z);
-        it.n = normalize(m4_normal(s.w2o, mk(pObj.x, pObj.y, 0)));
-        if (s.reverse_orientation) it.n = it.n * -1.f;
-        const float hitRad = sqrtf(pObj.x * pObj.x + pObj.y * pObj.y);
-        pObj.x *= s.radius / hitRad;
-        pObj.y *= s.radius / hitRad;
-        it.p = m4_point_err2(s.o2w, pObj, vabs(mk(pObj.x, pObj.y, 0)) * pgamma(3), it.pError);
-    } else {
-        float px, py;
-        concentric_sample_disk(u0, u1, px, py);
-        const V3 pObj = mk(px * s.radius, py * s.radius, s.height);
-        it.n = normalize(m4_normal(s.w2o, mk(0, 0, 1)));
-        if (s.reverse_orientation) it.n = it.n * -1.f;
-        it.p = m4_point_err2(s.o2w, pObj, mk(0, 0, 0), it.pError);
-    }
-    pdf = 1 / s.area;
-    return it;
-}
-
-// Triangle::Sample(u, pdf), triangle.cpp:582-607 with UniformSampleTriangle, sampling.cpp:154-157
-PG_DEV LightSample tri_sample_area(const DScene &sc, const Tri &t, int prim, float area, float u0, float u1, float &pdf) {
-    LightSample ls;
-    float su0 = sqrtf(u0);
-    float b0 = 1 - su0, b1 = u1 * su0;
-    float b2 = (1 - b0 - b1);
-    ls.p = t.p0 * b0 + t.p1 * b1 + t.p2 * b2;
-    ls.n = normalize(cross(t.p1 - t.p0, t.p2 - t.p0));
-    if (sc.attrN && (t.flags & PG_TRI_HAS_N)) {  // triangle.cpp:593-597: orientation follows the shading normal
-        V3 ns = tri_interp_normal(sc, prim, b0, b1, b2);
-        if (dot(ls.n, ns) < 0.f) ls.n = -ls.n;
-    } else if (t.flags & PG_TRI_FLIP_NORMAL) ls.n = ls.n * -1.f;
-    V3 pAbsSum = vabs(t.p0 * b0) + vabs(t.p1 * b1) + vabs(t.p2 * b2);
-    ls.pError = pAbsSum * pgamma(6);
-    pdf = 1 / area;
-    return ls;
-}
-// Shape::Sample(ref, u, pdf), shape.cpp:56-70: the area sample's pdf with respect to solid angle at refp
-PG_DEV void area_to_solid_angle(V3 refp, const LightSample &ls, float &pdf) {
-    V3 w = ls.p - refp;
-    if (lensq(w) == 0) pdf = 0;
-    else {
-        w = normalize(w);
-        pdf *= lensq(refp - ls.p) / absdot(ls.n, -w);
-        if (isinf(pdf)) pdf = 0.f;
-    }
-}
-// ---- InfiniteAreaLight with constant radiance: Lmap is a 1x1 MIPMap (lights/infinite.cpp, core/mipmap.h:245-274).
-// sinf/cosf/acosf/atan2f of the reference (glibc) are matched by evaluating in double and rounding once.
-PG_DEV V3 mat3_mul(const float *m, V3 w) {  // Transform::operator()(Vector3), transform.h:233-239
-    return mk(m[0] * w.x + m[1] * w.y + m[2] * w.z, m[3] * w.x + m[4] * w.y + m[5] * w.z, m[6] * w.x + m[7] * w.y + m[8] * w.z);
-}
-PG_DEV Spec env_lookup(const DScene &sc, const PgLight &l, float s0_, float t0_) {  // Lmap->Lookup(st): width 0 -> triangle(0, st), mipmap.h:214-243
-    return mip_triangle(sc, sc.images[l.env_image], 0, s0_, t0_);
-}
-PG_DEV Spec env_le(const DScene &sc, const PgLight &l, V3 rayD) {  // InfiniteAreaLight::Le, infinite.cpp:93-97
-    V3 w = normalize(mat3_mul(l.w2l, rayD));
-    return env_lookup(sc, l, spherical_phi(w) * PG_INV2PI, spherical_theta(w) * PG_INVPI);
-}
-// ProjectionLight::Projection (projection.cpp:79-91) and GonioPhotometricLight::Scale (goniometric.h:67-76); Lookup(st) of
-// their maps is triangle(0, st) (mipmap.h:214-243 with width 0)
-PG_DEV Spec light_projection(const DScene &sc, const PgLight &l, V3 w) {
-    const V3 wl = mat3_mul(l.w2l, w);
-    if (wl.z < l.hither) return sp(0);
-    const V3 p = m4_point(l.proj, wl);
-    if (!(p.x >= l.screen[0] && p.x <= l.screen[2] && p.y >= l.screen[1] && p.y <= l.screen[3])) return sp(0);
-    if (l.env_image < 0) return sp(1);
-    float ox = p.x - l.screen[0], oy = p.y - l.screen[1];  // Bounds2::Offset
-    if (l.screen[2] > l.screen[0]) ox /= l.screen[2] - l.screen[0];
-    if (l.screen[3] > l.screen[1]) oy /= l.screen[3] - l.screen[1];
-    return env_lookup(sc, l, ox, oy);
-}
-PG_DEV Spec light_gonio_scale(const DScene &sc, const PgLight &l, V3 w) {
-    V3 wp = normalize(mat3_mul(l.w2l, w));
-    const float t = wp.y; wp.y = wp.z; wp.z = t;
-    const float theta = spherical_theta(wp), phi = spherical_phi(wp);
-    if (l.env_image < 0) return sp(1);
-    return env_lookup(sc, l, phi * PG_INV2PI, theta * PG_INVPI);
-}
-PG_DEV float env_sample_1d(const float *func, const float *cdf, float funcInt, int n, float u, float &pdf, int *off) {  // sampling.h:72-89
-    int size = n + 1, first = 0, len = size;
-    while (len > 0) {
-        int half = len >> 1, middle = first + half;
-        if (cdf[middle] <= u) { first = middle + 1; len -= half + 1; } else len = half;
-    }
-    int offset = first - 1; offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
-    if (off) *off = offset;
-    float du = u - cdf[offset];
-    if ((cdf[offset + 1] - cdf[offset]) > 0) du /= (cdf[offset + 1] - cdf[offset]);
-    pdf = (funcInt > 0) ? func[offset] / funcInt : 0;
-    return (offset + du) / n;
-}
-PG_DEV float env_pdf_li(const DScene &sc, const PgLight &l, V3 w) {  // InfiniteAreaLight::Pdf_Li, infinite.cpp:127-135; Distribution2D::Pdf, sampling.h:135-141
-    V3 wi = mat3_mul(l.w2l, w);
-    float theta = spherical_theta(wi), phi = spherical_phi(wi);
-    float sinTheta = pg_sinf(theta);
-    if (sinTheta == 0) return 0;
-    float p0 = phi * PG_INV2PI, p1 = theta * PG_INVPI;
-    const int nu = l.env_nu, nv = l.env_nv;
-    const float *tab = sc.envTables + l.env_table;
-    int iu = (int)(p0 * nu); iu = iu < 0 ? 0 : (iu > nu - 1 ? nu - 1 : iu);
-    int iv = (int)(p1 * nv); iv = iv < 0 ? 0 : (iv > nv - 1 ? nv - 1 : iv);
-    const float *row = tab + (size_t)(2 * nu + 2) * iv, *marg = tab + (size_t)(2 * nu + 2) * nv;
-    return (row[iu] / marg[2 * nv + 1]) / (2 * PG_PI * PG_PI * sinTheta);
-}
-// EXT: the scene has primitives or lights beyond triangles + area / delta lights (spheres, infinite lights); the plain
-// instantiation keeps the common kernels at their register count
-template <bool EXT>
-PG_DEV Spec light_sample_li(const DScene &sc, const PgLight &light, V3 refp, V3 refErr, V3 refn, float u0, float u1, V3 &wi, float &pdf,
-                            LightSample &ls) {
-    if (EXT && light.type == PG_LIGHT_INFINITE) {  // InfiniteAreaLight::Sample_Li, infinite.cpp:99-125
-        float pdf0, pdf1;
-        int v;
-        const int nu = light.env_nu, nv = light.env_nv;
-        const float *tab = sc.envTables + light.env_table, *marg = tab + (size_t)(2 * nu + 2) * nv;
-        float d1 = env_sample_1d(marg, marg + nv, marg[2 * nv + 1], nv, u1, pdf1, &v);  // Distribution2D::SampleContinuous, sampling.h:127-134
-        const float *row = tab + (size_t)(2 * nu + 2) * v;
-        float d0 = env_sample_1d(row, row + nu, row[2 * nu + 1], nu, u0, pdf0, nullptr);
-        float mapPdf = pdf0 * pdf1;
-        ls.n = mk(0, 0, 0); ls.pError = mk(0, 0, 0); ls.p = refp;
-        pdf = 0;
-        if (mapPdf == 0) return sp(0);
-        float theta = d1 * PG_PI, phi = d0 * 2 * PG_PI;
-        float sT, cT, sP, cP;
-        pg_sincosf(theta, &sT, &cT);
-        pg_sincosf(phi, &sP, &cP);
-        float cosTheta = (float)cT, sinTheta = (float)sT, sinPhi = (float)sP, cosPhi = (float)cP;
-        wi = mat3_mul(light.l2w, mk(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta));
-        pdf = mapPdf / (2 * PG_PI * PG_PI * sinTheta);
-        if (sinTheta == 0) pdf = 0;
-        ls.p = refp + wi * (2 * light.world_radius);
-        return env_lookup(sc, light, d0, d1);
-    }
-    if (light.type != PG_LIGHT_AREA) {  // delta lights: point.cpp:43-52, spot.cpp:51-60, distant.cpp:50-60
-        const Spec I = sp3(light.L[0], light.L[1], light.L[2]);
-        const V3 pos = mk(light.pos[0], light.pos[1], light.pos[2]);
-        ls.n = mk(0, 0, 0); ls.pError = mk(0, 0, 0);  // VisibilityTester end point: Interaction(p, time, mediumInterface)
-        pdf = 1.f;
-        if (light.type == PG_LIGHT_DISTANT) {
-            wi = pos;  // wLight
-            ls.p = refp + pos * (2 * light.world_radius);  // pOutside
-            return I;
-        }
-        wi = normalize(pos - refp);
-        ls.p = pos;
-        const float d2 = lensq(pos - refp);
-        if (light.type == PG_LIGHT_SPOT) return (I * spot_falloff(light, -wi)) / d2;
-        if (EXT && light.type == PG_LIGHT_PROJECTION) return (I * light_projection(sc, light, -wi)) / d2;  // projection.cpp:71-77
-        if (EXT && light.type == PG_LIGHT_GONIO) return (I * light_gonio_scale(sc, light, -wi)) / d2;     // goniometric.cpp:43-52
-        return I / d2;
-    }
-    Tri t = load_tri(sc, light.prim);
-    const bool quadric = EXT && (t.flags & PG_PRIM_SPHERE);
-    if (quadric && sc.spheres[__float_as_int(t.p0.x)].shape == PG_SHAPE_SPHERE)
-        ls = sphere_sample(sc.spheres[__float_as_int(t.p0.x)], refp, refErr, refn, u0, u1, pdf);
-    else {
-        if (quadric) ls = quadric_sample_area(sc.spheres[__float_as_int(t.p0.x)], u0, u1, pdf);
-        else ls = tri_sample_area(sc, t, light.prim, light.area, u0, u1, pdf);
-        area_to_solid_angle(refp, ls, pdf);
-    }
-    if (pdf == 0 || lensq(ls.p - refp) == 0) { pdf = 0; return sp(0); }
-    wi = normalize(ls.p - refp);
-    return (light.two_sided || dot(ls.n, -wi) > 0) ? sp3(light.L[0], light.L[1], light.L[2]) : sp(0);
-}
-// The light as the shading kernel first meets it: DScene::lightHot's record, fetched in one round trip.
-struct LightHot { int type, prim, two_sided; float area; Spec L; Tri tri; };
-PG_DEV LightHot load_light_hot(const DScene &sc, int lightNum) {
-    const float4 *h = sc.lightHot + 5 * (size_t)lightNum;
-    const float4 h0 = h[0], h1 = h[1], a = h[2], b = h[3], c = h[4];
-    LightHot lh;
-    lh.type = __float_as_int(h0.x); lh.prim = __float_as_int(h0.y); lh.two_sided = __float_as_int(h0.z); lh.area = h0.w;
-    lh.L = sp3(h1.x, h1.y, h1.z);
-    lh.tri.p0 = mk(a.x, a.y, a.z); lh.tri.p1 = mk(b.x, b.y, b.z); lh.tri.p2 = mk(c.x, c.y, c.z);
-    lh.tri.flags = __float_as_uint(a.w); lh.tri.material = __float_as_int(b.w); lh.tri.light = __float_as_int(c.w);
-    return lh;
-}
-// light_sample_li for a light whose hot record is at hand: a diffuse area light on a triangle -- the common case -- is sampled
-// from the record alone; everything else goes through the general routine (same arithmetic either way)
-template <bool EXT>
-PG_DEV Spec light_sample_li_hot(const DScene &sc, const LightHot &lh, const PgLight &light, V3 refp, V3 refErr, V3 refn, float u0, float u1, V3 &wi,
-                                float &pdf, LightSample &ls) {
-    if (lh.type != PG_LIGHT_AREA || (lh.tri.flags & PG_PRIM_SPHERE)) return light_sample_li<EXT>(sc, light, refp, refErr, refn, u0, u1, wi, pdf, ls);
-    ls = tri_sample_area(sc, lh.tri, lh.prim, lh.area, u0, u1, pdf);
-    area_to_solid_angle(refp, ls, pdf);
-    if (pdf == 0 || lensq(ls.p - refp) == 0) { pdf = 0; return sp(0); }
-    wi = normalize(ls.p - refp);
-    return (lh.two_sided || dot(ls.n, -wi) > 0) ? lh.L : sp(0);
-}
-
-// LightDistribution::Lookup (lightdistrib.cpp:68-82,135-149) -> table of one Distribution1D
-PG_DEV const float *light_distribution(const DScene &sc, V3 p) {
-    if (sc.lightStrategy != PG_LIGHTS_SPATIAL) return sc.distTable;
-    V3 o = p - mk(sc.bmin[0], sc.bmin[1], sc.bmin[2]);  // Bounds3::Offset, geometry.h:801-807
-    if (sc.bmax[0] > sc.bmin[0]) o.x /= sc.bmax[0] - sc.bmin[0];
-    if (sc.bmax[1] > sc.bmin[1]) o.y /= sc.bmax[1] - sc.bmin[1];
-    if (sc.bmax[2] > sc.bmin[2]) o.z /= sc.bmax[2] - sc.bmin[2];
-    int pi0 = (int)(o.x * sc.nVoxels[0]), pi1 = (int)(o.y * sc.nVoxels[1]), pi2 = (int)(o.z * sc.nVoxels[2]);
-    pi0 = pi0 < 0 ? 0 : (pi0 > sc.nVoxels[0] - 1 ? sc.nVoxels[0] - 1 : pi0);
-    pi1 = pi1 < 0 ? 0 : (pi1 > sc.nVoxels[1] - 1 ? sc.nVoxels[1] - 1 : pi1);
-    pi2 = pi2 < 0 ? 0 : (pi2 > sc.nVoxels[2] - 1 ? sc.nVoxels[2] - 1 : pi2);
-    size_t idx = ((size_t)pi2 * sc.nVoxels[1] + pi1) * sc.nVoxels[0] + pi0;
-    if (sc.sparseLights) {  // computed on first touch, like the reference's hash table: ask for it and let the caller retry
-        const int slot = sc.voxelSlot[idx];
-        if (slot >= 0) return sc.distTable + (size_t)slot * (size_t)(2 * sc.nLights + 2);
-        if (slot == -1 && atomicCAS(&sc.voxelSlot[idx], -1, -2) == -1) sc.voxelRequests[atomicAdd(&sc.voxelCounters[0], 1)] = (int)idx;
-        return nullptr;
-    }
-    return sc.distTable + idx * (size_t)(2 * sc.nLights + 2);
-}
-// Distribution1D::SampleDiscrete, sampling.h:90-100 + FindInterval pbrt.h:403-415
-PG_DEV int sample_discrete(const float *tab, int n, float u, float &pdf) {
-    if (n <= 3) {
-        // a table of at most 8 floats (func[n], cdf[n+1], funcInt) is fetched in ONE round trip and searched in registers; the
-        // general path below meets it with three or four dependent loads (funcInt, the cdf entries of the search, func)
-        float row[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) row[k] = k < 2 * n + 2 ? tab[k] : 0.f;
-        asm volatile("" : "+v"(row[0]), "+v"(row[1]), "+v"(row[2]), "+v"(row[3]), "+v"(row[4]), "+v"(row[5]), "+v"(row[6]), "+v"(row[7]));
-        auto at = [&](int k) { return k == 0 ? row[0] : (k == 1 ? row[1] : (k == 2 ? row[2] : (k == 3 ? row[3] : (k == 4 ? row[4] : (k == 5 ? row[5] : (k == 6 ? row[6] : row[7])))))); };
-        const float funcInt = at(2 * n + 1);
-        int size = n + 1, first = 0, len = size;
-        while (len > 0) {
-            int half = len >> 1, middle = first + half;
-            if (at(n + middle) <= u) { first = middle + 1; len -= half + 1; }
-            else len = half;
-        }
-        int offset = first - 1;
-        offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
-        pdf = (funcInt > 0) ? at(offset) / (funcInt * n) : 0;
-        return offset;
-    }
-    const float *func = tab, *cdf = tab + n;
-    float funcInt = tab[2 * n + 1];
-    int size = n + 1, first = 0, len = size;
-    while (len > 0) {
-        int half = len >> 1, middle = first + half;
-        if (cdf[middle] <= u) { first = middle + 1; len -= half + 1; }
-        else len = half;
-    }
-    int offset = first - 1;
-    offset = offset < 0 ? 0 : (offset > size - 2 ? size - 2 : offset);
-    pdf = (funcInt > 0) ? func[offset] / (funcInt * n) : 0;
-    return offset;
-}
-
-PG_DEV void spawn_ray(const Isect &is, V3 d, V3 &o) { o = offset_ray_origin(is.p, is.pError, is.n, d); }  // interaction.h:64-67
 
 // MODE 0: triangles + matte/plastic/mirror/glass + area and delta lights (specialised BSDF).  MODE 1 (EXT): any material as
 // its BxDF list, quadrics, object instances, infinite lights.  MODE 2: MODE 1 + textured materials, evaluated per hit.
-
-// ===========================================================================
-// Participating media (VolPathIntegrator): HomogeneousMedium and the Henyey-Greenstein phase function.  expf / logf /
-// sinf / cosf are evaluated in double and rounded once, like every libm call of this file (DESIGN.md "libm").
-// ===========================================================================
-#define PG_MAX_FLOAT 3.40282346638528859811704183484516925e+38f
-PG_DEV Spec sp_exp(Spec a) { return sp3(pg_expf(a.r), pg_expf(a.g), pg_expf(a.b)); }  // Exp(), spectrum.h:414-419
-// HomogeneousMedium::Tr, homogeneous.cpp:44-47, for a ray with the given tMax and |d|
-PG_DEV Spec medium_tr(const PgMedium &m, float tMax, float dLen) {
-    const Spec negSt = sp3(-m.sigma_t[0], -m.sigma_t[1], -m.sigma_t[2]);
-    return sp_exp(negSt * pmin(tMax * dLen, PG_MAX_FLOAT));
-}
-PG_DEV float phase_hg(float cosTheta, float g) {  // medium.h:69-72
-    const float denom = 1 + g * g + 2 * g * cosTheta;
-    return 0.07957747154594766788f * (1 - g * g) / (denom * sqrtf(denom));
-}
-PG_DEV float hg_sample_p(float g, V3 wo, V3 &wi, float u0, float u1) {  // HenyeyGreenstein::Sample_p, medium.cpp:194-213
-    float cosTheta;
-    if ((double)fabsf(g) < 1e-3) cosTheta = 1 - 2 * u0;
-    else {
-        const float sqrTerm = (1 - g * g) / (1 + g - 2 * g * u0);
-        cosTheta = -(1 + g * g - sqrTerm * sqrTerm) / (2 * g);
-    }
-    const float sinTheta = sqrtf(pmax(0.f, 1 - cosTheta * cosTheta));
-    const float phi = 2 * PG_PI * u1;
-    V3 v1, v2;
-    coordinate_system(wo, v1, v2);
-    float sP, cP;
-    pg_sincosf(phi, &sP, &cP);
-    wi = (v1 * (sinTheta * (float)cP) + v2 * (sinTheta * (float)sP)) + wo * cosTheta;  // SphericalDirection, geometry.h:1461-1466
-    return phase_hg(cosTheta, g);
-}
-// GeometricPrimitive::Intersect's mediumInterface (primitive.cpp:121-125): the primitive's own when it marks a transition,
-// else the ray's medium on both sides.  Media are index + 1, 0 = none.
-PG_DEV void prim_interface(const DScene &sc, int prim, int rayMedium, int &mIn, int &mOut) {
-    const int in1 = sc.triMediumIn ? sc.triMediumIn[prim] + 1 : 0, out1 = sc.triMediumOut ? sc.triMediumOut[prim] + 1 : 0;
-    if (in1 != out1) { mIn = in1; mOut = out1; }
-    else mIn = mOut = rayMedium;
-}
-
-// ---- what every kernel that meets a closest hit shares: the hit's transforms, its SurfaceInteraction, an emitter's L there, and the two rays of
-// EstimateDirect's light sample and BSDF sample.  One implementation each: the films are the reference's bit for bit, and two copies of a formula
-// are two chances to round differently.
-
-// One transform above a closest hit: InstanceToWorld, its inverse and IsIdentity of instance `inst` (< 0: none) -- the instance's own or, a moving one's,
-// PrimitiveToWorld.Interpolate(r.time) as pg_motion.h left it in record off + i of `kept`.  Made once per hit: `outer` is the object instance's, `inner` the
-// TransformedPrimitive's INSIDE the object of a hit two levels deep (DScene::hasNest).  It holds the two indices, not the addresses: those are formed where a
-// matrix is read -- both sources are global memory --, so that no pointer is live across the interaction's arithmetic.  `kept` must exist whenever an instance
-// is animated (moving() does not test it; k_sss_exit once fell back to the instance's own matrices under `animated && hitXf`): DScene::animXf and
-// SssState::hitXf are both allocated exactly for a scene with motion (pg_abi.hip, `hasMotion`)
-struct InstXf {
-    const PgInstance *instances; const float *kept; int off;  // (uniform over a launch)
-    int inst, i;
-    PG_DEV bool some() const { return inst >= 0; }
-    PG_DEV const float *moving() const { return instances[inst].animated ? kept + (size_t)PG_XF_STRIDE * ((size_t)off + i) : nullptr; }
-    PG_DEV const float *i2w() const { const float *xf = moving(); return xf ? xf : instances[inst].i2w; }
-    PG_DEV const float *w2i() const { const float *xf = moving(); return xf ? xf + 16 : instances[inst].w2i; }
-    PG_DEV bool identity() const { const float *xf = moving(); return xf ? xf[32] != 0.f : instances[inst].identity != 0; }
-};
-// of the instance closest-hit result `i` was reached through: k_trace<.., XP_ANIM> computed a moving one's matrices for the accepted hit's ray and left them
-// at animXf[i] -- the inner transform's in the buffer's second half
-PG_DEV InstXf inst_xf(const DScene &sc, int inst, int i, bool inner = false) { return InstXf{sc.instances, sc.animXf, inner ? sc.nestXfOff : 0, inst, i}; }
-// DScene::hasNest: a closest hit's instance word is outer + nInstances * (inner + 1); inner = -1 for a hit one level deep
-PG_DEV void nest_decode(const DScene &sc, int &inst, int &inst2) { inst2 = -1; if (sc.hasNest && inst >= 0) { inst2 = inst / sc.nInstances - 1; inst = inst % sc.nInstances; } }
-// The ray a hit under these transforms was computed on (primitive.cpp:80-82: the outer transform first): its direction, which every interaction's wo
-// comes from ...
-PG_DEV V3 shape_ray_dir(const InstXf &outer, const InstXf &inner, V3 rayD) {
-    V3 d = rayD;
-    if (outer.some()) d = m4_vec(outer.w2i(), rayD);
-    if (inner.some()) d = m4_vec(inner.w2i(), d);
-    return d;
-}
-// ... and the whole ray, which a quadric's interaction is computed from (instance_ray: the very operations of k_trace's, pg_sphere.h)
-PG_DEV void shape_ray(const InstXf &outer, const InstXf &inner, float4 o4, V3 rayD, V3 &shapeRayO, V3 &shapeRayD) {
-    shapeRayO = mk(o4.x, o4.y, o4.z);
-    shapeRayD = rayD;
-    if (outer.some()) { float dt; instance_ray(outer.w2i(), shapeRayO, rayD, shapeRayO, shapeRayD, dt); }
-    if (inner.some()) { float dt; instance_ray(inner.w2i(), shapeRayO, shapeRayD, shapeRayO, shapeRayD, dt); }
-}
-// Sphere::Intersect's SurfaceInteraction (sphere.cpp:149-152): the shading geometry is the quadric's own
-PG_DEV Isect sphere_isect(const SphereHit &sh) {
-    Isect is;
-    is.p = sh.p; is.pError = sh.pError; is.wo = sh.wo; is.n = sh.n; is.ns = sh.n; is.sdpdu = sh.dpdu;
-    is.sdpdv = sh.dpdv; is.sdndu = sh.dndu; is.sdndv = sh.dndv;
-    return is;
-}
-// InterpolatedPrimToWorld(*isect) of a hit reached through an object instance, transform.cpp:262-297
-PG_DEV void isect_to_world(const float *i2w, const float *w2i, Isect &is) {
-    Isect w;
-    w.p = m4_point_err2(i2w, is.p, is.pError, w.pError);
-    w.n = normalize(m4_normal(w2i, is.n));
-    w.wo = normalize(m4_vec(i2w, is.wo));
-    w.sdpdu = m4_vec(i2w, is.sdpdu);
-    w.sdpdv = m4_vec(i2w, is.sdpdv);
-    w.sdndu = m4_normal(w2i, is.sdndu); w.sdndv = m4_normal(w2i, is.sdndv);
-    w.ns = normalize(m4_normal(w2i, is.ns));
-    if (dot(w.ns, w.n) < 0.f) w.ns = -w.ns;  // Faceforward(shading.n, n)
-    is = w;
-}
-// on the way out the inner transform first (TransformedPrimitive::Intersect returns through itself twice); an identity is skipped as the
-// reference skips it (primitive.cpp:85: if (!InterpolatedPrimToWorld.IsIdentity()))
-PG_DEV void isect_to_world(const InstXf &outer, const InstXf &inner, Isect &is) {
-    if (inner.some() && !inner.identity()) isect_to_world(inner.i2w(), inner.w2i(), is);
-    if (outer.some() && !outer.identity()) isect_to_world(outer.i2w(), outer.w2i(), is);
-}
-// A quadric hit's (u, v) and geometric dpdu / dpdv, in the shape's space: what textures read besides the interaction (tex_hit_setup)
-struct QuadricUv { bool on; float u, v; V3 dpdu, dpdv; };  // (on: the hit is on a quadric at all)
-// The SurfaceInteraction of closest hit h4 on primitive `prim`, found by ray (o4, rayD) under these transforms: the three stages above in one
-PG_DEV Isect hit_isect(const DScene &sc, const InstXf &outer, const InstXf &inner, float4 o4, V3 rayD, float4 h4, int prim, const Tri &tri, QuadricUv &quv) {
-    Isect is;
-    quv.on = (tri.flags & PG_PRIM_SPHERE) != 0;
-    quv.u = quv.v = 0; quv.dpdu = quv.dpdv = mk(0, 0, 0);
-    if (quv.on) {  // the hit record of a sphere carries tHit: Sphere::Intersect's interaction from the ray and the root
-        V3 shapeRayO, shapeRayD;
-        shape_ray(outer, inner, o4, rayD, shapeRayO, shapeRayD);
-        const SphereHit sh = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], shapeRayO, shapeRayD, h4.y);
-        is = sphere_isect(sh);
-        quv.u = sh.u; quv.v = sh.v; quv.dpdu = sh.dpdu; quv.dpdv = sh.dpdv;
-    } else is = make_isect(sc, prim, tri, h4.y, h4.z, h4.w, shape_ray_dir(outer, inner, rayD));
-    isect_to_world(outer, inner, is);
-    return is;
-}
-// DiffuseAreaLight::L(intr, w) (diffuse.h:56-58) with the emitter's geometric normal n
-PG_DEV Spec area_light_l(const PgLight &l, V3 n, V3 w) { return (l.two_sided || dot(n, w) > 0) ? sp3(l.L[0], l.L[1], l.L[2]) : sp(0); }
-// ... at closest hit h4 of ray (o4, rayD) on the emitter's primitive, back along the ray (integrator.cpp:204 lightIsect.Le(-wi)): the kernels that meet
-// the hit without building its interaction.  An emitter lies under no instance (api.cpp:1408-1409: an object definition's shapes take no area light), so the ray is the
-// shape's.  SPHERES: the scene may have quadrics at all (DScene::ext)
-template <bool SPHERES>
-PG_DEV Spec area_light_le(const DScene &sc, const PgLight &l, int prim, const Tri &tri, float4 h4, float4 o4, V3 rayD) {
-    V3 nrm;
-    if (SPHERES && (tri.flags & PG_PRIM_SPHERE)) nrm = sphere_interaction(sc.spheres[__float_as_int(tri.p0.x)], mk(o4.x, o4.y, o4.z), rayD, h4.y).n;
-    else nrm = hit_normal(sc, prim, tri, h4.y, h4.z, h4.w);
-    return area_light_l(l, nrm, -rayD);
-}
-// VisibilityTester's ray from (p, pError, n) to the light sample: p0.SpawnRayTo(p1), interaction.h:73-78 -- as a shadow-queue record (tag: what the
-// queue's consumer finds the vertex by); returns the ray's direction
-PG_DEV V3 shadow_ray_to(V3 p, V3 pError, V3 n, const LightSample &ls, int tag, float4 &o4, float4 &d4) {
-    const V3 origin = offset_ray_origin(p, pError, n, ls.p - p);
-    const V3 target = offset_ray_origin(ls.p, ls.pError, ls.n, origin - ls.p);
-    const V3 d = target - origin;
-    o4 = make_float4(origin.x, origin.y, origin.z, 1 - PG_SHADOW_EPS);
-    d4 = make_float4(d.x, d.y, d.z, __int_as_float(tag));
-    return d;
-}
-// light.Pdf_Li(ref, wi) of EstimateDirect's BSDF-sampled direction (integrator.cpp:175-178), for the ray (ro, wi) spawned at refP: an infinite light's
-// from its distribution (lightPrim = -1 - its number: no geometry to test); an area light's Shape::Pdf, which intersects the light's own shape
-// (shape.cpp:72-87, diffuse.cpp:83-87) -- one triangle test counted in nLightTests, whose hit on a degenerate triangle (PG_TRI_BOGUS) the reference's
-// Triangle::Intersect refuses --, or Sphere::Pdf (sphere.cpp:292-305): the cone's for a reference point outside (`inside`: sphere_ref_inside, or a partial sphere)
-template <bool EXT>
-PG_DEV float mis_light_pdf(const DScene &sc, int lightPrim, float lightArea, bool inside, V3 refP, V3 ro, V3 wi, unsigned int &nLightTests) {
-    float lightPdf = 0;
-    if (EXT && lightPrim < 0) lightPdf = env_pdf_li(sc, sc.lights[-1 - lightPrim], wi);
-    const Tri lt = load_tri(sc, lightPrim < 0 ? 0 : lightPrim);
-    float t, lb0, lb1, lb2;
-    if (EXT && lightPrim >= 0 && (lt.flags & PG_PRIM_SPHERE)) {
-        const PgSphere &ls = sc.spheres[__float_as_int(lt.p0.x)];
-        if (!inside) lightPdf = sphere_cone_pdf(ls, refP);
-        else if (sphere_test(ls, ro, wi, PG_INF, t)) {  // Shape::Pdf, shape.cpp:72-87
-            const SphereHit sh = sphere_interaction(ls, ro, wi, t);
-            float pdf = lensq(refP - sh.p) / (absdot(sh.n, -wi) * lightArea);
-            if (isinf(pdf)) pdf = 0.f;
-            lightPdf = pdf;
-        }
-    } else {
-        if (lightPrim >= 0) ++nLightTests;
-        if (lightPrim >= 0 && tri_test(lt.p0, lt.p1, lt.p2, ro, wi, PG_INF, t, lb0, lb1, lb2) && !(lt.flags & PG_TRI_BOGUS)) {
-            const V3 lp = lt.p0 * lb0 + lt.p1 * lb1 + lt.p2 * lb2;
-            const V3 ln = normalize(cross(lt.p0 - lt.p2, lt.p1 - lt.p2));
-            float pdf = lensq(refP - lp) / (absdot(ln, -wi) * lightArea);
-            if (isinf(pdf)) pdf = 0.f;
-            lightPdf = pdf;
-        }
-    }
-    return lightPdf;
-}
-// what mis_light_pdf needs of the sampled light: (lightPrim, inside) for the reference point (p, pError, n)
-PG_DEV void mis_light_of(const DScene &sc, const LightHot &lh, int lightNum, V3 p, V3 pError, V3 n, int &lightPrim, bool &inside) {
-    lightPrim = lh.type == PG_LIGHT_INFINITE ? -1 - lightNum : lh.prim;
-    inside = false;
-    if (lh.type == PG_LIGHT_AREA && (lh.tri.flags & PG_PRIM_SPHERE)) {
-        const PgSphere &lsph = sc.spheres[__float_as_int(lh.tri.p0.x)];
-        inside = lsph.shape != PG_SHAPE_SPHERE || sphere_ref_inside(lsph, p, pError, n);
-    }
-}
-// What textures read of the SurfaceInteraction at main-queue entry i: (u, v), p and ComputeDifferentials' outputs
-// (interaction.cpp:101-147).  quv: a quadric hit's (u, v) and geometric dpdu / dpdv; filmX / filmY: the camera sample's pFilm
-PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQueue &qin, int i, int slot, int prim, const Tri &tri, float4 h4, V3 rayD, const InstXf &outer,
-                          const InstXf &inner, const QuadricUv &quv, const Isect &is, int4 meta, float filmX, float filmY,
-                          bool tileSerial, bool pixelArrays, uint64_t index, TexHit &th, const float4 *stL) {
-    th.p = is.p;
-    V3 gdpdu, gdpdv;  // the geometric dpdu / dpdv (not the shading ones)
-    if (quv.on) { th.u = quv.u; th.v = quv.v; gdpdu = quv.dpdu; gdpdv = quv.dpdv; }
-    else {
-        float uv[6];
-        load_uv(sc, prim, tri.flags, uv);
-        tri_dpdu_dpdv(tri.p0, tri.p1, tri.p2, uv, gdpdu, gdpdv);
-        th.u = h4.y * uv[0] + h4.z * uv[2] + h4.w * uv[4];  // uvHit, triangle.cpp:332
-        th.v = h4.y * uv[1] + h4.z * uv[3] + h4.w * uv[5];
-    }
-    if (inner.some() && !inner.identity()) { gdpdu = m4_vec(inner.i2w(), gdpdu); gdpdv = m4_vec(inner.i2w(), gdpdv); }  // (the inner transform first)
-    if (outer.some() && !outer.identity()) { gdpdu = m4_vec(outer.i2w(), gdpdu); gdpdv = m4_vec(outer.i2w(), gdpdv); }
-    th.dpdx = th.dpdy = mk(0, 0, 0);
-    th.dudx = th.dvdx = th.dudy = th.dvdy = 0;
-    if (meta.w & PG_META_HASDIFF) {  // SurfaceInteraction::ComputeDifferentials, interaction.cpp:101-147
-        const float4 o4 = qin.o[i];
-        const V3 rayO = mk(o4.x, o4.y, o4.z);
-        V3 rxO, rxD, ryO, ryD;
-        if (rd.camera_type == 3) {  // the realistic camera: k_generate traced the shifted rays through the lens and kept the scaled differentials by slot
-            const float4 *df = lens_frame(stL)->differentials + 3 * (size_t)slot;
-            const float4 a = df[0], b = df[1], c = df[2];
-            rxO = mk(a.x, a.y, a.z); rxD = mk(a.w, b.x, b.y); ryO = mk(b.z, b.w, c.x); ryD = mk(c.y, c.z, c.w);
-        } else {
-        float l0 = 0, l1 = 0;
-        if (tileSerial) { l0 = sc.ts[slot].lens0; l1 = sc.ts[slot].lens1; }  // the camera sample's pLens, kept by k_ts_generate
-        else if (pixelArrays) { int d2 = 1 << 6; tsb_get2d(sc, meta.x, meta.y, d2, l0, l1); }  // (its second 2D dimension)
-        else if (rd.lens_radius > 0) { l0 = halton_sample(sc, rd, index, 3); l1 = halton_sample(sc, rd, index, 4); }
-        // the camera sample's time again (its third number), for the camera-to-world transform of that moment
-        float uTime = 0;
-        if (rd.camera_animated) {
-            if (tileSerial) uTime = sc.ts[slot].time;
-            else if (pixelArrays) { int d1 = 0; uTime = tsb_get1d(sc, meta.x, meta.y, d1); }
-            else uTime = halton_sample(sc, rd, index, 2);
-        }
-        if (rd.camera_animated) {  // (two calls: one pointer that is either the description's matrix or a private array would be a generic one)
-            float c2w[16];
-            camera_matrix_at(rd, camera_time(rd, uTime), c2w);
-            camera_differentials(rd, c2w, filmX, filmY, l0, l1, rayO, rayD, rxO, rxD, ryO, ryD);
-        } else camera_differentials(rd, rd.camera_to_world, filmX, filmY, l0, l1, rayO, rayD, rxO, rxD, ryO, ryD);
-        }
-        const V3 n = is.n, p = is.p;
-        const float dd = dot(n, p);
-        const float tx = -(dot(n, rxO) - dd) / dot(n, rxD);
-        const float ty = -(dot(n, ryO) - dd) / dot(n, ryD);
-        if (!(isinf(tx) || isnan(tx)) && !(isinf(ty) || isnan(ty))) {
-            const V3 px = rxO + rxD * tx, py = ryO + ryD * ty;
-            th.dpdx = px - p;
-            th.dpdy = py - p;
-            int d0, d1;
-            if (fabsf(n.x) > fabsf(n.y) && fabsf(n.x) > fabsf(n.z)) { d0 = 1; d1 = 2; }
-            else if (fabsf(n.y) > fabsf(n.z)) { d0 = 0; d1 = 2; }
-            else { d0 = 0; d1 = 1; }
-            auto comp = [](V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); };
-            const float A00 = comp(gdpdu, d0), A01 = comp(gdpdv, d0), A10 = comp(gdpdu, d1), A11 = comp(gdpdv, d1);
-            const float Bx0 = comp(px, d0) - comp(p, d0), Bx1 = comp(px, d1) - comp(p, d1);
-            const float By0 = comp(py, d0) - comp(p, d0), By1 = comp(py, d1) - comp(p, d1);
-            const float det = A00 * A11 - A01 * A10;  // SolveLinearSystem2x2, transform.cpp:41-49
-            if (!(fabsf(det) < 1e-10f)) {
-                th.dudx = (A11 * Bx0 - A01 * Bx1) / det; th.dvdx = (A00 * Bx1 - A10 * Bx0) / det;
-                if (isnan(th.dudx) || isnan(th.dvdx)) th.dudx = th.dvdx = 0;
-                th.dudy = (A11 * By0 - A01 * By1) / det; th.dvdy = (A00 * By1 - A10 * By0) / det;
-                if (isnan(th.dudy) || isnan(th.dvdy)) th.dudy = th.dvdy = 0;
-            }
-        }
-    }
-}
-// (the same from the hit's instance words and a quadric's values apart, for k_shade, which holds no InstXf across its vertex)
-PG_DEV void tex_hit_setup(const DScene &sc, const PgRenderDesc &rd, const RayQueue &qin, int i, int slot, int prim, const Tri &tri, float4 h4, V3 rayD, int inst, int inst2,
-                          bool onSphere, float sphU, float sphV, V3 sphDpdu, V3 sphDpdv, const Isect &is, int4 meta, float filmX, float filmY,
-                          bool tileSerial, bool pixelArrays, uint64_t index, TexHit &th, const float4 *stL) {
-    const QuadricUv quv = {onSphere, sphU, sphV, sphDpdu, sphDpdv};
-    tex_hit_setup(sc, rd, qin, i, slot, prim, tri, h4, rayD, inst_xf(sc, inst, i), inst_xf(sc, inst2, i, true), quv, is, meta, filmX, filmY, tileSerial, pixelArrays, index, th, stL);
-}
-// Material::Bump (material.cpp:46-85) of the material whose BSDF this is: its own bump map, or -- through mix materials, whose
-// BSDF is their first material's -- the first material's
-template <int W = 0>
-PG_DEV void material_bump(const DScene &sc, int material, const TexHit &th, Isect &is) {
-    int bm = material;
-    for (int lvl = 0; lvl < 4; ++lvl) {
-        const PgMaterial &mm = sc.materials[bm];
-        if (mm.type != PG_MAT_TEXTURED) break;
-        const PgTexturedMaterial &tmm = sc.textured[mm.textured_index];
-        if (tmm.kind == PG_KIND_MIX) { if (tmm.sub[0] < 0) break; bm = tmm.sub[0]; continue; }
-        if (tmm.has_bump) {
-            TexHit ev = th;
-            float du = .5f * (fabsf(th.dudx) + fabsf(th.dudy));
-            if (du == 0) du = .0005f;
-            ev.p = th.p + is.sdpdu * du; ev.u = th.u + du; ev.v = th.v + 0.f;
-            const float uDisplace = TexEval<PG_TEX_DEPTH, W>::f(*sc.self, tmm.bump, ev);
-            float dv = .5f * (fabsf(th.dvdx) + fabsf(th.dvdy));
-            if (dv == 0) dv = .0005f;
-            ev.p = th.p + is.sdpdv * dv; ev.u = th.u + 0.f; ev.v = th.v + dv;
-            const float vDisplace = TexEval<PG_TEX_DEPTH, W>::f(*sc.self, tmm.bump, ev);
-            const float displace = TexEval<PG_TEX_DEPTH, W>::f(*sc.self, tmm.bump, th);
-            const V3 bdpdu = (is.sdpdu + is.ns * ((uDisplace - displace) / du)) + is.sdndu * displace;
-            const V3 bdpdv = (is.sdpdv + is.ns * ((vDisplace - displace) / dv)) + is.sdndv * displace;
-            is.ns = normalize(cross(bdpdu, bdpdv));  // SetShadingGeometry(..., false), interaction.cpp:72-89
-            if (dot(is.ns, is.n) < 0.f) is.ns = -is.ns;
-            is.sdpdu = bdpdu; is.sdpdv = bdpdv;
-        }
-        break;
-    }
-}
 
 // PG_SHADE_MIN_WAVES: waves per SIMD the BxDF-list variants (MODE 1) are compiled for.  Left alone the volumetric one takes 177
 // VGPRs = 2 waves; capped at 168 (3 waves, 20 B of scratch) it is 31 % faster (150 -> 104 ms per frame on the 1 M-triangle volpath
@@ -2444,12 +400,6 @@ PG_DEV void material_bump(const DScene &sc, int material, const TexHit &th, Isec
 // phase 1 = everything up to the MIS candidate (emission, medium sampling incl. delta tracking, the light sample), then the
 // transmittance rays (k_through draws and counts), k_resolve_vol, and phase 2 = the vertex rebuilt, its next direction and the
 // roulette.  Scenes without a grid medium run the single-pass kernels they ran before (phase 0).
-// HomogeneousMedium::Sample's channel and distance from its two numbers, homogeneous.cpp:51-54
-PG_DEV void homogeneous_sample_distance(const PgMedium &mm, float uChannel, float uDist, int &channel, float &dist) {
-    channel = (int)(uChannel * 3);
-    if (channel > 2) channel = 2;
-    dist = -pg_logf((1 - uDist)) / mm.sigma_t[channel];
-}
 struct GridShade { float4 *vertex; int phase; };  // vertex[slot] = (medium interaction point, kind: 0 none, 1 medium vertex, 2 surface vertex)
 template <int MODE, bool VOL, bool SSS = false, bool GRID = false>
 __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MODE == 1 || MODE == 3) && PG_SHADE_MIN_WAVES > 0) ? PG_SHADE_MIN_WAVES : (MODE == 2 ? (VOL ? PG_SHADE2V_WAVES : PG_SHADE2_WAVES) : 1))) void k_shade(DScene sc, RenderParams rp, PathState st, RayQueue qin, const float4 *__restrict__ hits,
@@ -4249,6 +2199,5 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
     int nblk = (nDistributions + PG_BLOCK - 1) / PG_BLOCK;
     hipLaunchKernelGGL(k_light_tables, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, table, nDistributions);
 }
-
 
 #include "pg_direct.h"  // the kernels of the DirectLightingIntegrator, built from the pieces above

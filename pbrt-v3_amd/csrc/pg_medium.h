@@ -1,0 +1,56 @@
+// pg_medium.h -- participating media as device functions: HomogeneousMedium's transmittance and distance sample, the
+// Henyey-Greenstein phase function, and a primitive's medium interface.  (GridDensityMedium: pg_grid.h.)
+//
+// Used by the VOL instantiations of k_shade, k_through, k_resolve_vol and k_sss_exit (pg_kernels.hip).  phase_hg / hg_sample_p are
+// pinned on the host (tests/test_device_headers_on_host.py) and on the device (tests/test_gpu_device_arithmetic.py).
+#ifndef PG_MEDIUM_H
+#define PG_MEDIUM_H
+#include "pg_device.h"
+#include "pg_kernels.h"
+
+// ===========================================================================
+// Participating media (VolPathIntegrator): HomogeneousMedium and the Henyey-Greenstein phase function.  expf / logf /
+// sinf / cosf are evaluated in double and rounded once, like every libm call of this file (DESIGN.md "libm").
+// ===========================================================================
+#define PG_MAX_FLOAT 3.40282346638528859811704183484516925e+38f
+PG_DEV Spec sp_exp(Spec a) { return sp3(pg_expf(a.r), pg_expf(a.g), pg_expf(a.b)); }  // Exp(), spectrum.h:414-419
+// HomogeneousMedium::Tr, homogeneous.cpp:44-47, for a ray with the given tMax and |d|
+PG_DEV Spec medium_tr(const PgMedium &m, float tMax, float dLen) {
+    const Spec negSt = sp3(-m.sigma_t[0], -m.sigma_t[1], -m.sigma_t[2]);
+    return sp_exp(negSt * pmin(tMax * dLen, PG_MAX_FLOAT));
+}
+PG_DEV float phase_hg(float cosTheta, float g) {  // medium.h:69-72
+    const float denom = 1 + g * g + 2 * g * cosTheta;
+    return 0.07957747154594766788f * (1 - g * g) / (denom * sqrtf(denom));
+}
+PG_DEV float hg_sample_p(float g, V3 wo, V3 &wi, float u0, float u1) {  // HenyeyGreenstein::Sample_p, medium.cpp:194-213
+    float cosTheta;
+    if ((double)fabsf(g) < 1e-3) cosTheta = 1 - 2 * u0;
+    else {
+        const float sqrTerm = (1 - g * g) / (1 + g - 2 * g * u0);
+        cosTheta = -(1 + g * g - sqrTerm * sqrTerm) / (2 * g);
+    }
+    const float sinTheta = sqrtf(pmax(0.f, 1 - cosTheta * cosTheta));
+    const float phi = 2 * PG_PI * u1;
+    V3 v1, v2;
+    coordinate_system(wo, v1, v2);
+    float sP, cP;
+    pg_sincosf(phi, &sP, &cP);
+    wi = (v1 * (sinTheta * (float)cP) + v2 * (sinTheta * (float)sP)) + wo * cosTheta;  // SphericalDirection, geometry.h:1461-1466
+    return phase_hg(cosTheta, g);
+}
+// GeometricPrimitive::Intersect's mediumInterface (primitive.cpp:121-125): the primitive's own when it marks a transition,
+// else the ray's medium on both sides.  Media are index + 1, 0 = none.
+PG_DEV void prim_interface(const DScene &sc, int prim, int rayMedium, int &mIn, int &mOut) {
+    const int in1 = sc.triMediumIn ? sc.triMediumIn[prim] + 1 : 0, out1 = sc.triMediumOut ? sc.triMediumOut[prim] + 1 : 0;
+    if (in1 != out1) { mIn = in1; mOut = out1; }
+    else mIn = mOut = rayMedium;
+}
+// HomogeneousMedium::Sample's channel and distance from its two numbers, homogeneous.cpp:51-54
+PG_DEV void homogeneous_sample_distance(const PgMedium &mm, float uChannel, float uDist, int &channel, float &dist) {
+    channel = (int)(uChannel * 3);
+    if (channel > 2) channel = 2;
+    dist = -pg_logf((1 - uDist)) / mm.sigma_t[channel];
+}
+
+#endif  // PG_MEDIUM_H

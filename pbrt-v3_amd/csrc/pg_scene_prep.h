@@ -339,7 +339,7 @@ inline int pgPrepPrimitives(const PgSceneDesc *desc, PreparedScene &ps, std::str
     }
     return PG_OK;
 }
-// --- texture graph: operands are earlier nodes (no cycles), nesting <= 3 levels (the unrolled evaluator of pg_kernels.hip)
+// --- texture graph: operands are earlier nodes (no cycles), nesting <= 3 levels (the unrolled evaluator of pg_texture.h)
 inline int pgPrepTextures(const PgSceneDesc *desc, PreparedScene &ps, std::string &err) {
     std::vector<int> depth((size_t)(desc->n_textures > 0 ? desc->n_textures : 0), 1);
     auto refDepth = [&](const PgTexRef &r, int self) -> int { return r.tex < 0 ? 0 : ((r.tex >= self) ? 1000 : depth[r.tex]); };
@@ -605,7 +605,7 @@ inline int pgPrepNoiseAndSobol(const PgSceneDesc *desc, PreparedScene &ps, std::
     }
     return PG_OK;
 }
-// the longest BxDF list material mi can build, counted as the materials' ComputeScatteringFunctions add them (materials/*.cpp; MatEval, pg_kernels.hip)
+// the longest BxDF list material mi can build, counted as the materials' ComputeScatteringFunctions add them (materials/*.cpp; MatEval, pg_material.h)
 inline int pgPrepLobeCount(const PgSceneDesc *desc, int mi, int depth) {
     if (mi < 0 || mi >= desc->n_materials) return 0;
     const PgMaterial &m = desc->materials[mi];
@@ -628,7 +628,7 @@ inline void pgPrepShadingPlan(const PgSceneDesc *desc, PreparedScene &ps) {
     // build.  Not for scenes with BSSRDF materials or grid media (their kernels evaluate inside), PG_MAT_PRE=0: nowhere.
     const char *mp = getenv("PG_MAT_PRE");
     if (d.hasTextured && desc->n_bssrdfs == 0 && d.nGrids == 0 && !d.hasNest && !(mp && atoi(mp) == 0)) {  // (hasNest: MODE 2 carries the second transform)
-        // in RECORDS of 48 B (LobeBsdfT, pg_kernels.hip): one per BxDF, two where the hit's material is a mix (the ScaledBxDF factors)
+        // in RECORDS of 48 B (LobeBsdfT, pg_bxdf.h): one per BxDF, two where the hit's material is a mix (the ScaledBxDF factors)
         int stride = 1;
         for (int i = 0; i < desc->n_materials; ++i)
             if (desc->materials[i].type == PG_MAT_TEXTURED)

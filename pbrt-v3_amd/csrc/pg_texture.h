@@ -1,5 +1,5 @@
 // pg_texture.h -- texture evaluation on the device, shared by the shading kernels (materials' texture parameters,
-// pg_kernels.hip) and the traversal kernel (alpha masks of triangle meshes, pg_traverse.hip).
+// MatEval of pg_material.h) and the traversal kernel (alpha masks of triangle meshes, pg_traverse.hip).
 #ifndef PG_TEXTURE_H
 #define PG_TEXTURE_H
 #include "pg_device.h"

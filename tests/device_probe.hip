@@ -2,13 +2,18 @@
 // pbrt-v3_amd/Makefile with exactly the product's GPUFLAGS, loaded only by tests/test_gpu_device_arithmetic.py, which compares what it returns bit
 // for bit with the host build of the same source (tests/libm_pin.cpp, tests/device_headers_host.hip: the builds the non-GPU tests pin to glibc
 // and to the oracle).  Every entry point takes host pointers, does its own allocation / copies / launch / synchronize / free and returns 0 or
-// the hipError_t that stopped it (devprobe_error_string).  Nothing here is linked into libpbrt_gpu.so.  Functions defined inside
-// csrc/pg_kernels.hip are out of reach: including that translation unit would compile all its kernels a second time.
+// the hipError_t that stopped it (devprobe_error_string).  Nothing here is linked into libpbrt_gpu.so.  The device library of the shading
+// kernels (pg_bxdf.h, pg_medium.h, pg_sampler.h, pg_camera.h) is within reach like every other header: csrc/pg_kernels.hip holds kernels, their
+// launchers and a few helpers only kernels call, so no kernel of the product is compiled a second time here.
 #include "../pbrt-v3_amd/csrc/pg_device.h"
 #include "../pbrt-v3_amd/csrc/pg_sphere.h"
 #include "../pbrt-v3_amd/csrc/pg_grid.h"
 #include "../pbrt-v3_amd/csrc/pg_bssrdf.h"
 #include "../pbrt-v3_amd/csrc/pg_motion.h"
+#include "../pbrt-v3_amd/csrc/pg_sampler.h"
+#include "../pbrt-v3_amd/csrc/pg_camera.h"
+#include "../pbrt-v3_amd/csrc/pg_bxdf.h"
+#include "../pbrt-v3_amd/csrc/pg_medium.h"
 #include "libm_chunk.h"
 #include <vector>
 
@@ -192,6 +197,59 @@ template <bool INV> __global__ void k_interpolate_trs(int n, const float *T, con
     interpolate_trs<INV>((const float(*)[3])(T + 6 * i), (const float(*)[4])(R + 8 * i), (const float(*)[9])(S + 18 * i), dt[i], a, b);
     for (int k = 0; k < 16; ++k) { m[16 * i + k] = a[k]; mInv[16 * i + k] = b[k]; }
 }
+// ---- pg_bxdf.h: the wrappers of tests/device_headers_host.hip, a lane each (a disagreement among the forms of one evaluation comes back as NaNs) ----
+__device__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__global__ void k_lobe_f_pdf(int n, const PgBxDF *lobes, const float *wo, const float *wi, float *out) {
+    DP_LANE();
+    const PgBxDF &b = lobes[i];
+    const V3 o = v3at(wo, i), w = v3at(wi, i);
+    Spec f, fOnly, fNone;
+    float pdf, pdfOnly, pdfNone;
+    lobe_f_pdf(b, b.type, o, w, true, true, f, pdf);
+    lobe_f_pdf(b, b.type, o, w, true, false, fOnly, pdfNone);
+    lobe_f_pdf(b, b.type, o, w, false, true, fNone, pdfOnly);
+    const Spec fs = lobe_f(b, b.type, o, w);
+    const float ps = lobe_pdf(b, b.type, o, w);
+    float *q = out + 4 * i;
+    q[0] = f.r; q[1] = f.g; q[2] = f.b; q[3] = pdf;
+    const bool ok = same_bits(f.r, fOnly.r) && same_bits(f.g, fOnly.g) && same_bits(f.b, fOnly.b) && same_bits(pdf, pdfOnly) &&
+                    same_bits(f.r, fs.r) && same_bits(f.g, fs.g) && same_bits(f.b, fs.b) && same_bits(pdf, ps) &&
+                    pdfNone == 0 && fNone.r == 0 && fNone.g == 0 && fNone.b == 0;
+    if (!ok) q[0] = q[1] = q[2] = q[3] = __builtin_nanf("");
+}
+__global__ void k_lobe_sample_f(int n, const PgBxDF *lobes, const float *wo, const float *u0, const float *u1, float *out, int *type) {
+    DP_LANE();
+    const PgBxDF &b = lobes[i];
+    V3 wi = mk(0, 0, 0), wi2 = mk(0, 0, 0);
+    float pdf = 0, pdf2 = 0;
+    int sampledType = lobe_type(b.type), sampledType2 = sampledType;
+    const Spec f = lobe_sample_f(b, b.type, v3at(wo, i), wi, u0[i], u1[i], pdf, sampledType);
+    lobe_sample_f(b, b.type, v3at(wo, i), wi2, u0[i], u1[i], pdf2, sampledType2, false);
+    float *q = out + 7 * i;
+    q[0] = f.r; q[1] = f.g; q[2] = f.b; q[3] = pdf; q[4] = wi.x; q[5] = wi.y; q[6] = wi.z;
+    if (!(same_bits(pdf, pdf2) && same_bits(wi.x, wi2.x) && same_bits(wi.y, wi2.y) && same_bits(wi.z, wi2.z) && sampledType == sampledType2)) q[3] = __builtin_nanf("");
+    type[i] = sampledType;
+}
+// ---- pg_medium.h, pg_sampler.h, pg_camera.h ----------------------------------------------------------------------------------------------
+__global__ void k_henyey_greenstein(int n, const float *g, const float *wo, const float *u, const float *cosTheta, float *p, float *wi, float *phase) {
+    DP_LANE();
+    V3 w = mk(0, 0, 0);
+    p[i] = hg_sample_p(g[i], v3at(wo, i), w, u[2 * i], u[2 * i + 1]);
+    wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+    phase[i] = phase_hg(cosTheta[i], g[i]);
+}
+__global__ void k_halton_index(int n, const PgRenderDesc *rd, const int *px, const int *py, const long long *sampleNum, long long *out) {
+    DP_LANE();
+    out[i] = (long long)halton_index(*rd, px[i], py[i], (uint64_t)sampleNum[i]);
+}
+__global__ void k_camera_ray(int n, const PgRenderDesc *rd, const float *fx, const float *fy, const float *lx, const float *ly, float *out) {
+    DP_LANE();
+    V3 o, d;
+    float tMax;
+    camera_ray(*rd, rd->camera_to_world, fx[i], fy[i], lx[i], ly[i], o, d, tMax);
+    float *q = out + 7 * i;
+    q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = d.x; q[4] = d.y; q[5] = d.z; q[6] = tMax;
+}
 }  // namespace
 
 #define F(k) as<float>(d[k])
@@ -308,5 +366,35 @@ int devprobe_interpolate_trs(int n, int inv, const float *T, const float *R, con
         if (inv) hipLaunchKernelGGL(k_interpolate_trs<true>, blocks(n), dim3(LANES), 0, 0, n, F(0), F(1), F(2), F(3), (float *)d[4], (float *)d[5]);
         else hipLaunchKernelGGL(k_interpolate_trs<false>, blocks(n), dim3(LANES), 0, 0, n, F(0), F(1), F(2), F(3), (float *)d[4], (float *)d[5]);
     });
+}
+// lobes: n PgBxDFs, each evaluated as its own type; out: n x (f rgb, pdf)
+int devprobe_lobe_f_pdf(int n, const PgBxDF *lobes, const float *wo, const float *wi, float *out) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{lobes, (size_t)n * sizeof(PgBxDF)}, {wo, FB(3 * n)}, {wi, FB(3 * n)}}, {{out, FB(4 * n)}},
+               [&](void **d) { hipLaunchKernelGGL(k_lobe_f_pdf, blocks(n), dim3(LANES), 0, 0, n, as<PgBxDF>(d[0]), F(1), F(2), (float *)d[3]); });
+}
+// out: n x (f rgb, pdf, wi); type: the sampled type
+int devprobe_lobe_sample_f(int n, const PgBxDF *lobes, const float *wo, const float *u0, const float *u1, float *out, int *type) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{lobes, (size_t)n * sizeof(PgBxDF)}, {wo, FB(3 * n)}, {u0, FB(n)}, {u1, FB(n)}}, {{out, FB(7 * n)}, {type, n * sizeof(int)}},
+               [&](void **d) { hipLaunchKernelGGL(k_lobe_sample_f, blocks(n), dim3(LANES), 0, 0, n, as<PgBxDF>(d[0]), F(1), F(2), F(3), (float *)d[4], (int *)d[5]); });
+}
+// u: n x 2; p = hg_sample_p's value with its direction wi (n x 3), phase = phase_hg(cosTheta, g)
+int devprobe_henyey_greenstein(int n, const float *g, const float *wo, const float *u, const float *cosTheta, float *p, float *wi, float *phase) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{g, FB(n)}, {wo, FB(3 * n)}, {u, FB(2 * n)}, {cosTheta, FB(n)}}, {{p, FB(n)}, {wi, FB(3 * n)}, {phase, FB(n)}},
+               [&](void **d) { hipLaunchKernelGGL(k_henyey_greenstein, blocks(n), dim3(LANES), 0, 0, n, F(0), F(1), F(2), F(3), (float *)d[4], (float *)d[5], (float *)d[6]); });
+}
+int devprobe_halton_index(int n, const PgRenderDesc *rd, const int *px, const int *py, const long long *sampleNum, long long *out) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{rd, sizeof(PgRenderDesc)}, {px, n * sizeof(int)}, {py, n * sizeof(int)}, {sampleNum, n * sizeof(long long)}}, {{out, n * sizeof(long long)}}, [&](void **d) {
+        hipLaunchKernelGGL(k_halton_index, blocks(n), dim3(LANES), 0, 0, n, as<PgRenderDesc>(d[0]), as<int>(d[1]), as<int>(d[2]), as<long long>(d[3]), (long long *)d[4]);
+    });
+}
+// the camera of rd at its start transform (rd->camera_to_world), as tests/device_headers_host.hip's wrapper; out: n x (o, d, tMax)
+int devprobe_camera_ray(int n, const PgRenderDesc *rd, const float *fx, const float *fy, const float *lx, const float *ly, float *out) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{rd, sizeof(PgRenderDesc)}, {fx, FB(n)}, {fy, FB(n)}, {lx, FB(n)}, {ly, FB(n)}}, {{out, FB(7 * n)}},
+               [&](void **d) { hipLaunchKernelGGL(k_camera_ray, blocks(n), dim3(LANES), 0, 0, n, as<PgRenderDesc>(d[0]), F(1), F(2), F(3), F(4), (float *)d[5]); });
 }
 }

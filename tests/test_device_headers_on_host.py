@@ -1,5 +1,5 @@
 """The device arithmetic the HIP kernels execute, run WITHOUT a GPU: tests/device_headers_host.hip compiles the product's device headers
-(pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
+(pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h ... and the shading kernels' device library, pg_queue.h ... pg_hit.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
 file compares their functions with the oracle bit for bit -- on inputs far outside what the golden scenes contain (coordinates from
 1e-8 to 1e8, quadric radii from 1e-4 to 1e4), including exactly the ray sets of the GPU tests test_triangle_reintersect_on_device /
 test_quadric_reintersect_on_device.  That the gfx950 build of the same source returns the same bits is tests/test_gpu_device_arithmetic.py: it
@@ -53,6 +53,19 @@ def build_host_headers(directory):
     lib.hostdev_concentric_sample_disk.argtypes = [C.c_float, C.c_float, C.c_void_p]
     lib.hostdev_interpolate_trs.restype = None
     lib.hostdev_interpolate_trs.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2
+    lib.hostdev_lobe_f_pdf.argtypes = [C.c_void_p] * 4
+    lib.hostdev_lobe_sample_f.restype = C.c_int
+    lib.hostdev_lobe_sample_f.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    lib.hostdev_bssrdf_adapter_f.restype = C.c_float
+    lib.hostdev_bssrdf_adapter_f.argtypes = [C.c_float, C.c_float]
+    lib.hostdev_phase_hg.restype = C.c_float
+    lib.hostdev_phase_hg.argtypes = [C.c_float, C.c_float]
+    lib.hostdev_hg_sample_p.restype = C.c_float
+    lib.hostdev_hg_sample_p.argtypes = [C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+    lib.hostdev_halton_index.restype = C.c_longlong
+    lib.hostdev_halton_index.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong]
+    lib.hostdev_camera_ray.restype = None
+    lib.hostdev_camera_ray.argtypes = [C.c_void_p] + [C.c_float] * 4 + [C.c_void_p]
     return lib
 
 
@@ -234,31 +247,6 @@ def test_radical_inverses_equal_oracle(dev, pkg, oracle):
             assert bits([want])[0] == bits([dev.hostdev_scrambled_radical_inverse(base, perm.ctypes.data, a)])[0], (base, a)
 
 
-@pytest.fixture(scope="module")
-def devk(tmp_path_factory):
-    """pbrt-v3_amd/csrc/pg_kernels.hip -- the shading kernels' translation unit -- compiled for the host (tests/device_kernels_host.hip)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    so = str(tmp_path_factory.mktemp("hostdevk") / "libdevice_kernels_host.so")
-    subprocess.check_call([HIPCC, "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                           os.path.join(ROOT, "tests", "device_kernels_host.hip"), "-o", so])
-    lib = C.CDLL(so)
-    lib.hostdev_lobe_f_pdf.argtypes = [C.c_void_p] * 4
-    lib.hostdev_lobe_sample_f.restype = C.c_int
-    lib.hostdev_lobe_sample_f.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
-    lib.hostdev_bssrdf_adapter_f.restype = C.c_float
-    lib.hostdev_bssrdf_adapter_f.argtypes = [C.c_float, C.c_float]
-    lib.hostdev_phase_hg.restype = C.c_float
-    lib.hostdev_phase_hg.argtypes = [C.c_float, C.c_float]
-    lib.hostdev_hg_sample_p.restype = C.c_float
-    lib.hostdev_hg_sample_p.argtypes = [C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
-    lib.hostdev_halton_index.restype = C.c_longlong
-    lib.hostdev_halton_index.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong]
-    lib.hostdev_camera_ray.restype = None
-    lib.hostdev_camera_ray.argtypes = [C.c_void_p] + [C.c_float] * 4 + [C.c_void_p]
-    return lib
-
-
 def random_lobe(pkg, rng, kind):
     """A PgBxDF of the given PgBxDFType with random parameters (include/pbrt_gpu.h)."""
     b = pkg.abi.PgBxDF()
@@ -282,27 +270,36 @@ def unit(rng, flip=None):
     return v
 
 
-@pytest.mark.parametrize("kind,name", [(1, "LambertianReflection"), (2, "LambertianTransmission"), (3, "OrenNayar"), (4, "SpecularReflection"), (5, "SpecularTransmission"),
-                                       (6, "FresnelSpecular"), (7, "MicrofacetReflection"), (8, "MicrofacetTransmission"), (9, "FresnelBlend")])
-def test_bxdf_library_equals_the_correctly_rounded_oracle(devk, pkg, oracle, kind, name):
-    """lobe_f / lobe_pdf / lobe_sample_f of the shading kernels (every BxDF of core/reflection.cpp the ABI carries) run on the host and
-    compared bit for bit with the oracle's correctly-rounded-libm build -- the arithmetic the device is required to reproduce
-    (tests/test_gpu_parity.py) -- on random parameters and directions of both hemispheres, grazing ones included."""
-    L = oracle.lib()
+def bxdf_inputs(pkg, kind):
+    """(lobes, wo, wi, u0, u1), 400 each: random BxDFs of the given PgBxDFType, unit directions of both hemispheres -- the wo of every seventh trial
+    grazing (|z| = 1e-4 before normalization) -- and the sample pair."""
     rng = np.random.default_rng(100 + kind)
-    nz = 0
+    rows = []
     for trial in range(400):
         b = random_lobe(pkg, rng, kind)
         wo, wi = unit(rng), unit(rng)
         if trial % 7 == 0: wo[2] = np.float32(1e-4) * (1 if wo[2] > 0 else -1); wo = (wo / np.linalg.norm(wo)).astype(np.float32)
+        u0, u1 = np.float32(rng.random()), np.float32(rng.random())
+        rows.append((b, wo, wi, u0, u1))
+    return ([r[0] for r in rows],) + tuple(np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(1, 5))
+
+
+@pytest.mark.parametrize("kind,name", [(1, "LambertianReflection"), (2, "LambertianTransmission"), (3, "OrenNayar"), (4, "SpecularReflection"), (5, "SpecularTransmission"),
+                                       (6, "FresnelSpecular"), (7, "MicrofacetReflection"), (8, "MicrofacetTransmission"), (9, "FresnelBlend")])
+def test_bxdf_library_equals_the_correctly_rounded_oracle(dev, pkg, oracle, kind, name):
+    """lobe_f / lobe_pdf / lobe_sample_f of the shading kernels (every BxDF of core/reflection.cpp the ABI carries) run on the host and
+    compared bit for bit with the oracle's correctly-rounded-libm build -- the arithmetic the device is required to reproduce
+    (tests/test_gpu_parity.py) -- on random parameters and directions of both hemispheres, grazing ones included."""
+    L = oracle.lib()
+    nz = 0
+    for trial, (b, wo, wi, u0, u1) in enumerate(zip(*bxdf_inputs(pkg, kind))):
         a, d = np.zeros(4, np.float32), np.zeros(4, np.float32)
         L.oracle_lobe_f_pdf(C.addressof(b), wo.ctypes.data, wi.ctypes.data, a.ctypes.data)
-        devk.hostdev_lobe_f_pdf(C.addressof(b), wo.ctypes.data, wi.ctypes.data, d.ctypes.data)
+        dev.hostdev_lobe_f_pdf(C.addressof(b), wo.ctypes.data, wi.ctypes.data, d.ctypes.data)
         assert np.array_equal(bits(a), bits(d)), (name, trial, a, d)
-        u0, u1 = np.float32(rng.random()), np.float32(rng.random())
         sa, sd = np.zeros(7, np.float32), np.zeros(7, np.float32)
         ta = L.oracle_lobe_sample_f(C.addressof(b), wo.ctypes.data, u0, u1, sa.ctypes.data)
-        td = devk.hostdev_lobe_sample_f(C.addressof(b), wo.ctypes.data, u0, u1, sd.ctypes.data)
+        td = dev.hostdev_lobe_sample_f(C.addressof(b), wo.ctypes.data, u0, u1, sd.ctypes.data)
         if sa[3] == 0 and sd[3] == 0:  # no sample: f and wi are not looked at by BSDF::Sample_f
             continue
         assert ta == td and np.array_equal(bits(sa), bits(sd)), (name, trial, sa, sd)
@@ -459,7 +456,7 @@ def test_bssrdf_spatial_device_functions_equal_the_correctly_rounded_oracle(dev,
         assert bits([want])[0] == bits([dev.hostdev_invert_catmull_rom(100, rho.ctypes.data, rho_eff.ctypes.data, x)])[0]
 
 
-def test_bssrdf_adapter_f_equals_oracle(devk, pkg, oracle):
+def test_bssrdf_adapter_f_equals_oracle(dev, pkg, oracle):
     """SeparableBSSRDFAdapter::f = Sw(wi) * eta^2 with the shading kernels' own FrDielectric against the oracle's adapter lobe."""
     L = oracle.lib()
     rng = np.random.default_rng(31)
@@ -472,54 +469,81 @@ def test_bssrdf_adapter_f_equals_oracle(devk, pkg, oracle):
         out = np.zeros(4, np.float32)
         wo = np.array([0, 0, 1], np.float32)
         L.oracle_lobe_f_pdf(C.addressof(lobe), wo.ctypes.data, wi.ctypes.data, out.ctypes.data)
-        assert bits(out[:1])[0] == bits([devk.hostdev_bssrdf_adapter_f(eta, wi[2])])[0], (trial, eta, wi)
+        assert bits(out[:1])[0] == bits([dev.hostdev_bssrdf_adapter_f(eta, wi[2])])[0], (trial, eta, wi)
 
 
-def test_henyey_greenstein_equals_the_correctly_rounded_oracle(devk, oracle):
-    """phase_hg / hg_sample_p of the volpath kernels (HenyeyGreenstein::p / Sample_p) against the oracle, isotropic and both signs of g."""
-    L = oracle.lib()
+def henyey_greenstein_inputs():
+    """(g, wo, u, cosTheta), 3 000 each: every fifth g one of 0, 5e-4 (the isotropic branch), -0.9, 0.9, the others in (-0.95, 0.95)."""
     rng = np.random.default_rng(41)
+    rows = []
     for trial in range(3000):
         g = np.float32([0.0, 5e-4, -0.9, 0.9][trial % 4] if trial % 5 == 0 else rng.uniform(-0.95, 0.95))
         wo = unit(rng)
         u = rng.random(2).astype(np.float32)
+        ct = np.float32(rng.uniform(-1, 1))
+        rows.append((g, wo, u, ct))
+    return tuple(np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(4))
+
+
+def test_henyey_greenstein_equals_the_correctly_rounded_oracle(dev, oracle):
+    """phase_hg / hg_sample_p of the volpath kernels (HenyeyGreenstein::p / Sample_p) against the oracle, isotropic and both signs of g."""
+    L = oracle.lib()
+    for trial, (g, wo, u, ct) in enumerate(zip(*henyey_greenstein_inputs())):
         a, c = np.zeros(3, np.float32), np.zeros(3, np.float32)
         pa = L.oracle_hg_sample_p(g, wo.ctypes.data, u.ctypes.data, a.ctypes.data)
-        pc = devk.hostdev_hg_sample_p(g, wo.ctypes.data, u[0], u[1], c.ctypes.data)
+        pc = dev.hostdev_hg_sample_p(g, wo.ctypes.data, u[0], u[1], c.ctypes.data)
         assert bits([pa])[0] == bits([pc])[0] and np.array_equal(bits(a), bits(c)), (trial, g)
-        ct = np.float32(rng.uniform(-1, 1))
-        assert bits([L.oracle_phase_hg(ct, g)])[0] == bits([devk.hostdev_phase_hg(ct, g)])[0]
+        assert bits([L.oracle_phase_hg(ct, g)])[0] == bits([dev.hostdev_phase_hg(ct, g)])[0]
 
 
-def test_halton_pixel_index_equals_oracle(devk, pkg, oracle):
-    """HaltonSampler::GetIndexForSample (samplers/halton.cpp:92-116, the multiplicative inverses and the pixel's offset) of the kernels."""
-    L = oracle.lib()
+def halton_index_inputs(pkg):
+    """[(golden, its scene, its PgRenderDesc, [(px, py, sample number)] of 400 pixels of the film)] for three goldens, one of them cropped."""
     rng = np.random.default_rng(51)
+    cases = []
     for golden in ("cornell_32", "cornell_crop", "synthetic_n40"):
         scene = pkg.HostScene(os.path.join(ROOT, "tests", "golden", golden + ".pbrt"))
         rd = scene.render_desc()
         w, h = scene.film_size
-        for _ in range(400):
-            px, py, k = int(rng.integers(0, max(1, w))), int(rng.integers(0, max(1, h))), int(rng.integers(0, 1 << 20))
-            assert L.oracle_halton_index(C.byref(rd), px, py, k) == devk.hostdev_halton_index(C.byref(rd), px, py, k), (golden, px, py, k)
+        cases.append((golden, scene, rd, [(int(rng.integers(0, max(1, w))), int(rng.integers(0, max(1, h))), int(rng.integers(0, 1 << 20))) for _ in range(400)]))
+    return cases
 
 
-@pytest.mark.parametrize("golden", ["cornell_32", "cornell_lens", "cornell_ortho", "cornell_ortho_lens", "cornell_envcam", "cornell_crop"])
-def test_camera_rays_equal_the_correctly_rounded_oracle(devk, pkg, oracle, golden):
+def test_halton_pixel_index_equals_oracle(dev, pkg, oracle):
+    """HaltonSampler::GetIndexForSample (samplers/halton.cpp:92-116, the multiplicative inverses and the pixel's offset) of the kernels."""
+    L = oracle.lib()
+    for golden, scene, rd, pixels in halton_index_inputs(pkg):
+        for px, py, k in pixels:
+            assert L.oracle_halton_index(C.byref(rd), px, py, k) == dev.hostdev_halton_index(C.byref(rd), px, py, k), (golden, px, py, k)
+
+
+CAMERA_GOLDENS = ["cornell_32", "cornell_lens", "cornell_ortho", "cornell_ortho_lens", "cornell_envcam", "cornell_crop"]
+
+
+def camera_ray_inputs(pkg, golden):
+    """(the golden's scene, its PgRenderDesc, (fx, fy, lx, ly) of 2 000 film / lens samples over the full resolution)"""
+    scene = pkg.HostScene(os.path.join(ROOT, "tests", "golden", golden + ".pbrt"))
+    rd = scene.render_desc()
+    rng = np.random.default_rng(61)
+    fw, fh = rd.full_res[0], rd.full_res[1]
+    rows = []
+    for _ in range(2000):
+        fx, fy = np.float32(rng.random() * fw), np.float32(rng.random() * fh)
+        lx, ly = np.float32(rng.random()), np.float32(rng.random())
+        rows.append((fx, fy, lx, ly))
+    return scene, rd, tuple(np.ascontiguousarray([r[k] for r in rows], np.float32) for k in range(4))
+
+
+@pytest.mark.parametrize("golden", CAMERA_GOLDENS)
+def test_camera_rays_equal_the_correctly_rounded_oracle(dev, pkg, oracle, golden):
     """camera_ray of k_generate (PerspectiveCamera / OrthographicCamera / EnvironmentCamera ::GenerateRay, thin lens included) against
     the oracle: origin, direction and tMax of 2 000 film / lens samples per camera, bit for bit."""
     path = os.path.join(ROOT, "tests", "golden", golden + ".pbrt")
     if not os.path.exists(path):
         pytest.skip(golden + " is not among the goldens")
-    scene = pkg.HostScene(path)
-    rd = scene.render_desc()
+    scene, rd, samples = camera_ray_inputs(pkg, golden)
     L = oracle.lib()
-    rng = np.random.default_rng(61)
-    fw, fh = rd.full_res[0], rd.full_res[1]
-    for _ in range(2000):
-        fx, fy = np.float32(rng.random() * fw), np.float32(rng.random() * fh)
-        lx, ly = np.float32(rng.random()), np.float32(rng.random())
+    for fx, fy, lx, ly in zip(*samples):
         a, c = np.zeros(7, np.float32), np.zeros(7, np.float32)
         L.oracle_generate_ray(C.byref(rd), fx, fy, lx, ly, a.ctypes.data)
-        devk.hostdev_camera_ray(C.byref(rd), fx, fy, lx, ly, c.ctypes.data)
+        dev.hostdev_camera_ray(C.byref(rd), fx, fy, lx, ly, c.ctypes.data)
         assert np.array_equal(bits(a), bits(c)), (golden, fx, fy, lx, ly, a, c)

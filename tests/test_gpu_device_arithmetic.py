@@ -9,7 +9,9 @@ tests/device_probe.hip (pbrt-v3_amd/libpg_devprobe.so, compiled with the product
   * pg_libm.h over every float argument (atan2f: the 2^32 pairs of tests/test_libm_restated.py), compared through 1024 chunk sums per
     function with tests/golden/libm_chunk_sums.npz, which tests/test_libm_chunk_sums.py ties to the host build and to glibc;
   * the header functions on the inputs of tests/test_device_headers_on_host.py, and pg_motion.h's interpolate_trs, compared word for word
-    with tests/device_headers_host.hip's build, at batch sizes around the wave width and at the full count.
+    with tests/device_headers_host.hip's build, at batch sizes around the wave width and at the full count -- the device library of the
+    shading kernels among them: every BxDF (pg_bxdf.h), Henyey-Greenstein (pg_medium.h), the Halton sample index (pg_sampler.h) and the
+    camera ray (pg_camera.h).
 
 PG_DEVPROBE_LIB names another build of the probe (to see these tests fail on one compiled with other flags)."""
 import ctypes as C
@@ -41,7 +43,9 @@ def probe(gpu):
            "scrambled_radical_inverse": [C.c_int, P, P, C.c_int, P, P, P], "concentric_sample_disk": [C.c_int] + [P] * 3, "grid_density": [C.c_int] + [P] * 4,
            "grid_tr": [C.c_int] + [P] * 6 + [C.c_int, P, P], "grid_sample": [C.c_int] + [P] * 6 + [C.c_int, P, P, P], "bssrdf_radial": [C.c_int, P, P, C.c_longlong, P, P, P],
            "fresnel_moment1": [C.c_int, P, P], "invert_catmull_rom": [C.c_int, C.c_int] + [P] * 4, "bssrdf_pdf_sp": [C.c_int, P, P, C.c_longlong] + [P] * 5,
-           "bssrdf_probe_segment": [C.c_int, P, P, C.c_longlong] + [P] * 7, "interpolate_trs": [C.c_int, C.c_int] + [P] * 6}
+           "bssrdf_probe_segment": [C.c_int, P, P, C.c_longlong] + [P] * 7, "interpolate_trs": [C.c_int, C.c_int] + [P] * 6,
+           "lobe_f_pdf": [C.c_int] + [P] * 4, "lobe_sample_f": [C.c_int] + [P] * 6, "henyey_greenstein": [C.c_int] + [P] * 7, "halton_index": [C.c_int] + [P] * 5,
+           "camera_ray": [C.c_int] + [P] * 6}
     for name, argtypes in sig.items():
         fn = getattr(lib, "devprobe_" + name)
         fn.restype, fn.argtypes = C.c_int, argtypes
@@ -390,11 +394,120 @@ def case_interpolate_trs(inv):
     return case
 
 
+BXDF_KINDS = range(1, 10)  # every PgBxDFType
+
+
+def lobe_array(pkg, lobes):
+    arr = (pkg.abi.PgBxDF * len(lobes))()
+    for i, b in enumerate(lobes):
+        arr[i] = b
+    return arr
+
+
+def case_lobe_f_pdf(probe, host, pkg):
+    per_kind = []
+    for kind in BXDF_KINDS:
+        lobes, wo, wi, _, _ = H.bxdf_inputs(pkg, kind)
+        N = len(lobes)
+        assert N == 400
+        arr = lobe_array(pkg, lobes)
+        out = np.zeros((N, 4), F32)
+        for i in range(N):
+            host.hostdev_lobe_f_pdf(C.addressof(arr[i]), ptr(wo[i]), ptr(wi[i]), ptr(out[i]))
+
+        def device(n, arr=arr, wo=wo, wi=wi):
+            dout = np.zeros((n, 4), F32)
+            run(probe, "lobe_f_pdf", n, C.addressof(arr), rows(wo, n), rows(wi, n), dout)
+            return (dout,)
+        per_kind.append((N, (out,), device))
+    return per_kind
+
+
+def case_lobe_sample_f(probe, host, pkg):
+    """f, pdf, wi and the sampled type, with and without wantF (the wrapper's NaN pdf says the two disagree).  A trial whose pdf is 0 in BOTH builds compares
+    pdf and type only, as the host test does against the oracle (BSDF::Sample_f does not look at f and wi then): the host rows are reduced where the host's
+    pdf is 0, the device rows where both are 0 -- so a pdf that is 0 in one build only still differs in its own word."""
+    per_kind = []
+    for kind in BXDF_KINDS:
+        lobes, wo, _, u0, u1 = H.bxdf_inputs(pkg, kind)
+        N = len(lobes)
+        assert N == 400
+        arr = lobe_array(pkg, lobes)
+        out, typ = np.zeros((N, 7), F32), np.zeros(N, np.int32)
+        for i in range(N):
+            typ[i] = host.hostdev_lobe_sample_f(C.addressof(arr[i]), ptr(wo[i]), u0[i], u1[i], ptr(out[i]))
+        host_zero = out[:, 3] == 0
+        assert (~host_zero).sum() > 100, (kind, int((~host_zero).sum()))  # compared in full
+        pdf_only = lambda o, zero: np.where(zero[:, None] & (np.arange(7) != 3)[None, :], F32(0), o)
+
+        def device(n, arr=arr, wo=wo, u0=u0, u1=u1, host_zero=host_zero):
+            dout, dtyp = np.zeros((n, 7), F32), np.zeros(n, np.int32)
+            run(probe, "lobe_sample_f", n, C.addressof(arr), rows(wo, n), rows(u0, n), rows(u1, n), dout, dtyp)
+            return dtyp, pdf_only(dout, host_zero[:n] & (dout[:, 3] == 0))
+        per_kind.append((N, (typ, pdf_only(out, host_zero)), device))
+    return per_kind
+
+
+def case_henyey_greenstein(probe, host, pkg):
+    g, wo, u, ct = H.henyey_greenstein_inputs()
+    N = len(g)
+    assert N == 3000
+    p, wi, phase = np.zeros(N, F32), np.zeros((N, 3), F32), np.zeros(N, F32)
+    for i in range(N):
+        p[i] = host.hostdev_hg_sample_p(g[i], ptr(wo[i]), u[i, 0], u[i, 1], ptr(wi[i]))
+        phase[i] = host.hostdev_phase_hg(ct[i], g[i])
+
+    def device(n):
+        dp, dwi, dphase = np.zeros(n, F32), np.zeros((n, 3), F32), np.zeros(n, F32)
+        run(probe, "henyey_greenstein", n, rows(g, n), rows(wo, n), rows(u, n), rows(ct, n), dp, dwi, dphase)
+        return dp, dwi, dphase
+    return N, (p, wi, phase), device
+
+
+def case_halton_index(probe, host, pkg):
+    per_golden = []
+    for golden, scene, rd, pixels in H.halton_index_inputs(pkg):
+        N = len(pixels)
+        assert N == 400
+        px, py = np.array([p[0] for p in pixels], np.int32), np.array([p[1] for p in pixels], np.int32)
+        k = np.array([p[2] for p in pixels], np.int64)
+        out = np.array([host.hostdev_halton_index(C.addressof(rd), int(px[i]), int(py[i]), int(k[i])) for i in range(N)], np.int64)
+
+        def device(n, rd=rd, px=px, py=py, k=k, keep=scene):
+            dout = np.zeros(n, np.int64)
+            run(probe, "halton_index", n, C.addressof(rd), rows(px, n), rows(py, n), rows(k, n), dout)
+            return (dout,)
+        per_golden.append((N, (out,), device))
+    assert len(per_golden) == 3
+    return per_golden
+
+
+def case_camera_ray(probe, host, pkg):
+    per_camera = []
+    for golden in H.CAMERA_GOLDENS:
+        scene, rd, (fx, fy, lx, ly) = H.camera_ray_inputs(pkg, golden)
+        N = len(fx)
+        assert N == 2000
+        out = np.zeros((N, 7), F32)
+        for i in range(N):
+            host.hostdev_camera_ray(C.addressof(rd), fx[i], fy[i], lx[i], ly[i], ptr(out[i]))
+
+        def device(n, rd=rd, fx=fx, fy=fy, lx=lx, ly=ly, keep=scene):
+            dout = np.zeros((n, 7), F32)
+            run(probe, "camera_ray", n, C.addressof(rd), rows(fx, n), rows(fy, n), rows(lx, n), rows(ly, n), dout)
+            return (dout,)
+        per_camera.append((N, (out,), device))
+    assert len(per_camera) == 6
+    return per_camera
+
+
 CASES = {"tri_test": case_tri_test, "offset_ray_origin": case_offset_ray_origin, "radical_inverse": case_radical_inverse,
          "scrambled_radical_inverse": case_scrambled_radical_inverse, "concentric_sample_disk": case_concentric_sample_disk,
          "grid_density": case_grid("grid_density"), "grid_tr": case_grid("grid_tr"), "grid_sample": case_grid("grid_sample"), "bssrdf_radial": case_bssrdf_radial,
          "fresnel_moment1": case_fresnel_moment1, "invert_catmull_rom": case_invert_catmull_rom, "bssrdf_pdf_sp": case_bssrdf_spatial("bssrdf_pdf_sp"),
          "bssrdf_probe_segment": case_bssrdf_spatial("bssrdf_probe_segment"), "interpolate_trs": case_interpolate_trs(0), "interpolate_trs_inverse": case_interpolate_trs(1)}
+CASES.update({"lobe_f_pdf": case_lobe_f_pdf, "lobe_sample_f": case_lobe_sample_f, "henyey_greenstein": case_henyey_greenstein, "halton_index": case_halton_index,
+              "camera_ray": case_camera_ray})
 CASES.update({"quadric_test_" + kind: case_quadric_test(kind) for kind in ("sphere", "cylinder", "disk", "cone", "paraboloid", "hyperboloid")})
 
 
