@@ -735,6 +735,32 @@ int pg_intersect(PgScene *scene, int32_t n, const float *o, const float *d,
 int pg_intersect_p(PgScene *scene, int32_t n, const float *o, const float *d,
                    const float *tmax, uint8_t *occluded, int mem, void *stream);
 
+/* What Scene::Intersect leaves in the SurfaceInteraction of one ray, in world space: 128 bytes, written by the device as eight float4.
+ * No material is evaluated (no bump mapping: that is ComputeScatteringFunctions').  On a miss every field but prim, t and time is 0. */
+typedef struct PgInteraction {
+    int32_t prim;            /* -1 = miss; otherwise as pg_intersect reports it */
+    int32_t instance;        /* instances[] index of the TransformedPrimitive the hit lies under, -1 = none */
+    int32_t instance_inner;  /* ABI 29 nesting: the moving shape's own instance inside an object definition, -1 = none */
+    int32_t material;        /* materials[] index of the primitive hit (a PG_MAT_NONE material is reported as such) */
+    int32_t light;           /* lights[] index of the hit primitive's DiffuseAreaLight, -1 = not emissive */
+    float t;                 /* ray.tMax after Scene::Intersect; the ray's own tmax on a miss */
+    float time;              /* the ray's time, as given */
+    float uv[2];             /* triangles: b0 uv0 + b1 uv1 + b2 uv2 (default uv, triangle.h:104-106); quadrics: the shape's (u, v) */
+    float p[3], p_error[3], n[3], wo[3];
+    float shading_n[3], shading_dpdu[3], shading_dpdv[3];
+    float reserved[2];       /* written as 0 */
+} PgInteraction;
+
+/* Batched Scene::Intersect with Ray::time, for an integrator whose Li stays on the host: o, d and tmax as pg_intersect takes them,
+ * time[i] = the ray's time (NULL: 0 for every ray; a scene without motion ignores the values), out[i] = the interaction of ray i.  Moving
+ * shapes and instances are intersected at the ray's time (AnimatedTransform::Interpolate).  With PG_MEM_DEVICE the inputs are read and the
+ * records are written on the device; the call synchronises once, for k_trace's cull guard.  PgCounters as pg_intersect. */
+int pg_intersect_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                    PgInteraction *out, int mem, void *stream);
+/* Batched Scene::IntersectP with Ray::time: occluded[i] = 1 if any hit.  PgCounters as pg_intersect_p. */
+int pg_intersect_p_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                      uint8_t *occluded, int mem, void *stream);
+
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);
 int pg_scene_set_option(PgScene *scene, int32_t option, int32_t value);

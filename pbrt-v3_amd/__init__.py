@@ -30,6 +30,12 @@ FILM_PIXEL_DTYPE = np.dtype([("rgb", np.float32, 3), ("weight", np.float32)])
 STRAY_DTYPE = np.dtype([("px", np.int32), ("py", np.int32), ("src_px", np.int32), ("src_py", np.int32),
                         ("rgb", np.float32, 3), ("weight", np.float32)])
 
+# one record of pg_intersect_at: abi.PgInteraction field for field (128 bytes)
+INTERACTION_DTYPE = np.dtype([("prim", np.int32), ("instance", np.int32), ("instance_inner", np.int32), ("material", np.int32), ("light", np.int32),
+                              ("t", np.float32), ("time", np.float32), ("uv", np.float32, 2),
+                              ("p", np.float32, 3), ("p_error", np.float32, 3), ("n", np.float32, 3), ("wo", np.float32, 3),
+                              ("shading_n", np.float32, 3), ("shading_dpdu", np.float32, 3), ("shading_dpdv", np.float32, 3), ("reserved", np.float32, 2)])
+
 _host = None
 _gpu = None
 
@@ -282,6 +288,46 @@ class GpuScene:
         _check(gpu_lib().pg_intersect_p(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, occ.ctypes.data,
                                         PG_MEM_HOST, None), "pg_intersect_p")
         return occ
+
+    @staticmethod
+    def _rays(o, d, tmax, time):
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        tmax = np.ascontiguousarray(tmax, np.float32)
+        n = len(tmax)
+        if time is not None:
+            time = np.ascontiguousarray(time, np.float32)
+            if o.size != 3 * n or d.size != 3 * n or time.size != n:
+                raise ValueError("o and d hold three floats, tmax and time one float per ray")
+        elif o.size != 3 * n or d.size != 3 * n:
+            raise ValueError("o and d hold three floats, tmax one float per ray")
+        return o, d, tmax, time, n
+
+    def intersect_at(self, o, d, tmax, time=None):
+        """Batched Scene::Intersect with Ray::time on host arrays (time=None: every ray at time 0): the rays' SurfaceInteractions as a
+        structured array of INTERACTION_DTYPE -- moving shapes and instances at the ray's time; prim = -1 on a miss."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        out = np.empty(n, INTERACTION_DTYPE)
+        _check(gpu_lib().pg_intersect_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                         out.ctypes.data, PG_MEM_HOST, None), "pg_intersect_at")
+        return out
+
+    def intersect_p_at(self, o, d, tmax, time=None):
+        """Batched Scene::IntersectP with Ray::time on host arrays: uint8, 1 = occluded."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        occ = np.empty(n, np.uint8)
+        _check(gpu_lib().pg_intersect_p_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                           occ.ctypes.data, PG_MEM_HOST, None), "pg_intersect_p_at")
+        return occ
+
+    def intersect_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, out_ptr, stream=None):
+        """pg_intersect_at on caller-owned device buffers (raw pointers; e.g. torch tensors' data_ptr()): n rays, 3 n floats at o_ptr and d_ptr, n at
+        tmax_ptr and time_ptr (None: time 0), n records of INTERACTION_DTYPE written at out_ptr.  Nothing visits the host."""
+        _check(gpu_lib().pg_intersect_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, out_ptr, PG_MEM_DEVICE, stream), "pg_intersect_at")
+
+    def intersect_p_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, occluded_ptr, stream=None):
+        """pg_intersect_p_at on caller-owned device buffers: n bytes written at occluded_ptr."""
+        _check(gpu_lib().pg_intersect_p_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, occluded_ptr, PG_MEM_DEVICE, stream), "pg_intersect_p_at")
 
     def counters(self):
         c = PgCounters()

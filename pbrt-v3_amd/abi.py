@@ -168,6 +168,13 @@ class PgStraySample(C.Structure):
                 ("rgb", C.c_float * 3), ("weight", C.c_float)]
 
 
+class PgInteraction(C.Structure):
+    _fields_ = [("prim", C.c_int32), ("instance", C.c_int32), ("instance_inner", C.c_int32), ("material", C.c_int32), ("light", C.c_int32),
+                ("t", C.c_float), ("time", C.c_float), ("uv", C.c_float * 2),
+                ("p", C.c_float * 3), ("p_error", C.c_float * 3), ("n", C.c_float * 3), ("wo", C.c_float * 3),
+                ("shading_n", C.c_float * 3), ("shading_dpdu", C.c_float * 3), ("shading_dpdv", C.c_float * 3), ("reserved", C.c_float * 2)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -206,6 +213,10 @@ GPU_SYMBOLS = {
                                C.c_void_p, C.c_int, C.c_void_p]),
     "pg_intersect_p": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p]),
+    "pg_intersect_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p]),
+    "pg_intersect_p_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

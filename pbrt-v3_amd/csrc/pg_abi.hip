@@ -80,6 +80,7 @@ struct PgScene {
     DeviceBuffer qsPend[2], pendList;  // QueueState::pend of the two main queues; PendJoin::list
     // test-path buffers
     DeviceBuffer tO, tD, tT, tPrim, tHit, tOcc, tCount;
+    DeviceBuffer tIn, tInst, tXf, tOut;  // pg_intersect_at / pg_intersect_p_at: host rays staged, the hits' instances and interpolated matrices, host results staged
     PgCounters counters;
     std::vector<hipEvent_t> events;
     bool hasNullMaterial = false;
@@ -257,15 +258,19 @@ static void traceAnyhit(PgScene *s, RayQueue q, int *occluded, TraceCounters *cn
 
 // k_trace's early-cull margin is exact while no ray accepts more than TR_MAX_ACCEPTED hits (pg_traverse.hip); otherwise
 // the kernel raises this flag and the call fails instead of returning a possibly different image.
-static int checkCullGuard(PgScene *s) {
-    int g = 0;
-    HIP_TRY(hipMemcpy(&g, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost));
+// (g: the guard word as read back)
+static int cullGuardStatus(PgScene *s, int g) {
     if (g) {
         HIP_TRY(hipMemset(s->cullGuard.p, 0, sizeof(int)));
         s->cullTripped = true;  // the entry points then repeat the call without the margin (exact by construction, slower)
         return setError(PG_ERR_OVERFLOW, "a ray accepted more than 4096 successive hits: the far-child cull margin is no longer provably exact");
     }
     return PG_OK;
+}
+static int checkCullGuard(PgScene *s) {
+    int g = 0;
+    HIP_TRY(hipMemcpy(&g, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost));
+    return cullGuardStatus(s, g);
 }
 // Runs `call`; if a ray outran the early-cull margin's proof (sorted stacks of alpha cards can do that), runs it again with the
 // margin disabled -- every far child then waits on the stack for the reference's own test at pop time -- with the counters put
@@ -1399,6 +1404,120 @@ int pg_intersect_p(PgScene *s, int32_t n, const float *o, const float *d, const 
     HIP_TRY(hipMemcpy(occluded, o8.data(), (size_t)n, mem == PG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost));
     TraceCounters tc[2];
     HIP_TRY(hipMemcpy(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost));
+    PgCounters &c = s->counters;
+    c.shadow_rays += (uint64_t)n;
+    c.shadow_node_visits = tc[1].node_visits; c.shadow_tri_tests = tc[1].tri_tests;
+    c.node_visits = tc[0].node_visits + tc[1].node_visits;
+    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
+    c.shadow_launches += 1;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) c.shadow_ms += ms;
+    return PG_OK;
+}
+
+// ---- the same with Ray::time, returning the SurfaceInteraction (pg_interaction.h) ------
+// The test-path buffers only grow here: DeviceBuffer::alloc frees first, and hipFree waits for the device
+static hipError_t reserve(DeviceBuffer &b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes); }
+// The rays into the test queue ON the device (k_pack_rays), their times behind `d` in PG_QUEUE_TIMES's layout -- for every scene: a still scene's
+// k_trace does not read them, the records report them.  Host rays are staged in tIn; the caller's arrays must outlive the stream's work, which the
+// entry points wait for before they return
+static int packRays(PgScene *s, int n, const float *o, const float *d, const float *tmax, const float *time, int mem, hipStream_t stream, RayQueue &q, float *&times) {
+    const size_t N = (size_t)regionCapFor(n) * PG_REGIONS;
+    HIP_TRY(reserve(s->tO, N * sizeof(float4)));
+    HIP_TRY(reserve(s->tD, N * (sizeof(float4) + sizeof(float))));
+    HIP_TRY(reserve(s->tCount, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));
+    if (mem != PG_MEM_DEVICE) {
+        const size_t n3 = 3 * (size_t)n;
+        HIP_TRY(reserve(s->tIn, (2 * n3 + 2 * (size_t)n) * sizeof(float)));
+        float *in = (float *)s->tIn.p;
+        HIP_TRY(hipMemcpyAsync(in, o, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(in + n3, d, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(in + 2 * n3, tmax, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (time) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + n, time, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
+        o = in; d = in + n3; tmax = in + 2 * n3; time = time ? in + 2 * n3 + n : nullptr;
+    }
+    q = testQueue(s, n);
+    times = reinterpret_cast<float *>(q.d + N);
+    launch_pack_rays(o, d, tmax, time, n, q, times, stream);
+    return PG_OK;
+}
+
+static int intersectAtBatch(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *out, int mem,
+                            void *streamPtr) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    RayQueue q;
+    float *times = nullptr;
+    if (int st = packRays(s, n, o, d, tmax, time, mem, stream, q, times)) return st;
+    HIP_TRY(reserve(s->tHit, sizeof(float4) * (size_t)n));
+    HIP_TRY(reserve(s->tT, sizeof(float) * (size_t)n));
+    // the launches see the scene as a frame's do -- the hits' instances, a moving one's matrices at the ray's time, rayTimes as the scene has it --
+    // over this call's own buffers (traceClosest clears all three for the unit entry points)
+    DScene dsc = s->d;
+    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
+    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * (size_t)n)); dsc.hitInst = (int *)s->tInst.p; }
+    if (dsc.hasMotion) {
+        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * (size_t)n * PG_XF_STRIDE * sizeof(float)));  // (hasNest: a second half for the inner transform)
+        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = n;
+    }
+    PgInteraction *dOut = out;  // PG_MEM_DEVICE: k_interaction writes the caller's records
+    if (mem != PG_MEM_DEVICE) { HIP_TRY(reserve(s->tOut, sizeof(PgInteraction) * (size_t)n)); dOut = (PgInteraction *)s->tOut.p; }
+    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
+    HIP_TRY(hipEventRecord(a, stream));
+    launch_closest(dsc, s->trace, q, (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+    HIP_TRY(hipEventRecord(b, stream));
+    launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dOut, stream);
+    HIP_TRY(hipGetLastError());
+    if (mem != PG_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(out, dOut, sizeof(PgInteraction) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    TraceCounters tc[2];
+    int guard = 0;
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait: the cull guard decides whether the records stand
+    PgCounters &c = s->counters;
+    c.closest_rays += (uint64_t)n;
+    c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
+    c.node_visits = tc[0].node_visits + tc[1].node_visits;
+    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
+    c.closest_launches += 1;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) c.closest_ms += ms;
+    return cullGuardStatus(s, guard);
+}
+int pg_intersect_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *out, int mem,
+                    void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !out))) return setError(PG_ERR_INVALID, "pg_intersect_at: null argument");
+    if (n == 0) return PG_OK;
+    return withExactFallback(s, [&]() { return intersectAtBatch(s, n, o, d, tmax, time, out, mem, streamPtr); });
+}
+
+int pg_intersect_p_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, uint8_t *occluded, int mem,
+                      void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p_at: null argument");
+    if (n == 0) return PG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    RayQueue q;
+    float *times = nullptr;
+    if (int st = packRays(s, n, o, d, tmax, time, mem, stream, q, times)) return st;
+    HIP_TRY(reserve(s->tOcc, sizeof(int) * (size_t)n));
+    uint8_t *dOcc = occluded;
+    if (mem != PG_MEM_DEVICE) { HIP_TRY(reserve(s->tOut, (size_t)n)); dOcc = (uint8_t *)s->tOut.p; }
+    // in the reference's visiting order, as traceAnyhit -- but with the rays' times (rayTimes as the scene has it)
+    TraceConfig cfg = s->trace;
+    cfg.anyhitFree = 0;
+    DScene dsc = s->d;
+    dsc.hitInst = nullptr; dsc.animXf = nullptr;  // (a closest hit's: an any-hit launch touches neither)
+    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
+    HIP_TRY(hipEventRecord(a, stream));
+    launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
+    HIP_TRY(hipEventRecord(b, stream));
+    launch_occluded_bytes((const int *)s->tOcc.p, dOcc, n, stream);
+    HIP_TRY(hipGetLastError());
+    if (mem != PG_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(occluded, dOcc, (size_t)n, hipMemcpyDeviceToHost, stream));
+    TraceCounters tc[2];
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     PgCounters &c = s->counters;
     c.shadow_rays += (uint64_t)n;
     c.shadow_node_visits = tc[1].node_visits; c.shadow_tri_tests = tc[1].tri_tests;

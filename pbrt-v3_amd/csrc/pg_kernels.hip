@@ -9,6 +9,7 @@
 //   k_film       SamplerIntegrator::Render's scrub + FilmTile::AddSample    (integrator.cpp:294-320, film.h:121-161)
 //   k_light_tables  SpatialLightDistribution::ComputeDistribution per voxel (lightdistrib.cpp:232-300)
 //   k_direct     DirectLightingIntegrator::Li, one (light, sample) step per launch (directlighting.cpp:62-95; pg_direct.h, included at the end)
+//   k_interaction  Scene::Intersect's SurfaceInteraction per ray, for pg_intersect_at (pg_interaction.h, included at the end)
 //
 // No MFMA: there is no dense contraction on this path; traversal is a
 // latency/bandwidth-bound gather over the node and triangle arrays.
@@ -2201,3 +2202,4 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
 }
 
 #include "pg_direct.h"  // the kernels of the DirectLightingIntegrator, built from the pieces above
+#include "pg_interaction.h"  // the kernels of the ray queries with per-ray time (pg_intersect_at / pg_intersect_p_at)
