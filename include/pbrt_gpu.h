@@ -725,9 +725,9 @@ const char *pg_shard_transport(void);
 /* pgh_box_filter_needs_gather() above as a symbol, for bindings that cannot use the C header's inline function */
 int pg_box_filter_needs_gather(const PgRenderDesc *rd);
 
-/* Batched Scene::Intersect: rays as SoA (ox..dz, tmax), n rays.  Outputs
- * prim (-1 = miss), t, b0, b1, b2 (barycentrics exactly as computed by
- * Triangle::Intersect, triangle.cpp:280-285).                                */
+/* Batched Scene::Intersect at time 0: n rays, three floats per origin in o and per direction in d, one tmax each.  Outputs prim (-1 = miss),
+ * t (the ray's tmax on a miss) and three barycentrics per ray in bary (exactly as computed by Triangle::Intersect, triangle.cpp:280-285; 0 on
+ * a miss).  mem as for pg_intersect_at: with PG_MEM_DEVICE every array is device memory, and no ray and no result visits the host. */
 int pg_intersect(PgScene *scene, int32_t n, const float *o, const float *d,
                  const float *tmax, int32_t *prim, float *t, float *bary,
                  int mem, void *stream);

@@ -268,10 +268,7 @@ class GpuScene:
 
     def intersect(self, o, d, tmax):
         """Batched Scene::Intersect on host arrays: returns prim (int32), t, bary (n,3)."""
-        o = np.ascontiguousarray(o, np.float32)
-        d = np.ascontiguousarray(d, np.float32)
-        tmax = np.ascontiguousarray(tmax, np.float32)
-        n = len(tmax)
+        o, d, tmax, _, n = self._rays(o, d, tmax, None)
         prim = np.empty(n, np.int32)
         t = np.empty(n, np.float32)
         bary = np.empty((n, 3), np.float32)
@@ -280,10 +277,7 @@ class GpuScene:
         return prim, t, bary
 
     def intersect_p(self, o, d, tmax):
-        o = np.ascontiguousarray(o, np.float32)
-        d = np.ascontiguousarray(d, np.float32)
-        tmax = np.ascontiguousarray(tmax, np.float32)
-        n = len(tmax)
+        o, d, tmax, _, n = self._rays(o, d, tmax, None)
         occ = np.empty(n, np.uint8)
         _check(gpu_lib().pg_intersect_p(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, occ.ctypes.data,
                                         PG_MEM_HOST, None), "pg_intersect_p")

@@ -79,8 +79,8 @@ struct PgScene {
     bool resolveFused = true;
     DeviceBuffer qsPend[2], pendList;  // QueueState::pend of the two main queues; PendJoin::list
     // test-path buffers
-    DeviceBuffer tO, tD, tT, tPrim, tHit, tOcc, tCount;
-    DeviceBuffer tIn, tInst, tXf, tOut;  // pg_intersect_at / pg_intersect_p_at: host rays staged, the hits' instances and interpolated matrices, host results staged
+    DeviceBuffer tO, tD, tCount, tHit, tT, tOcc;  // the test queue; a closest-hit launch's records and t, an any-hit launch's answers
+    DeviceBuffer tIn, tInst, tXf, tOut;  // host rays staged, pg_intersect_at's instances and interpolated matrices of the hits, host results staged
     PgCounters counters;
     std::vector<hipEvent_t> events;
     bool hasNullMaterial = false;
@@ -240,20 +240,6 @@ int pg_scene_create(const PgSceneDesc *desc, PgScene **out) {
     return PG_OK;
 #undef FAIL
 #undef HIP_TRY_S
-}
-
-static void traceClosest(PgScene *s, RayQueue q, float4 *hits, float *tOut, TraceCounters *cn, hipStream_t st) {
-    DScene d = s->d;
-    d.hitInst = nullptr; d.animXf = nullptr; d.rayTimes = 0;  // the unit entry points report primitive, t and barycentrics only; their rays have time 0
-    launch_closest(d, s->trace, q, hits, tOut, cn, (int *)s->cursors.p, (int *)s->cullGuard.p, st);
-}
-static void traceAnyhit(PgScene *s, RayQueue q, int *occluded, TraceCounters *cn, hipStream_t st) {
-    // the unit entry point answers in the reference's visiting order: its counters are the reference's (tests compare them)
-    TraceConfig c = s->trace;
-    c.anyhitFree = 0;
-    DScene d = s->d;
-    d.rayTimes = 0;  // the unit entry points' rays have time 0 (their queues carry no times)
-    launch_anyhit(d, c, q, occluded, cn, (int *)s->cursors.p, st);
 }
 
 // k_trace's early-cull margin is exact while no ray accepts more than TR_MAX_ACCEPTED hits (pg_traverse.hip); otherwise
@@ -1294,129 +1280,9 @@ int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *des
 }
 
 // ---- batched Scene::Intersect / IntersectP -------------------------------------------
-static int uploadRays(PgScene *s, int n, const float *o, const float *d, const float *tmax, int mem, hipStream_t stream) {
-    // AoS (3 floats) host/device input -> the kernels' float4 SoA queue layout
-    std::vector<float4> qo((size_t)n), qd((size_t)n);
-    std::vector<float> ho, hd, ht;
-    const float *po = o, *pd = d, *pt = tmax;
-    if (mem == PG_MEM_DEVICE) {
-        ho.resize(3 * (size_t)n); hd.resize(3 * (size_t)n); ht.resize((size_t)n);
-        HIP_TRY(hipMemcpy(ho.data(), o, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hd.data(), d, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ht.data(), tmax, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-        po = ho.data(); pd = hd.data(); pt = ht.data();
-    }
-    for (int i = 0; i < n; ++i) {
-        float idf;
-        memcpy(&idf, &i, 4);
-        qo[i] = make_float4(po[3 * i], po[3 * i + 1], po[3 * i + 2], pt[i]);
-        qd[i] = make_float4(pd[3 * i], pd[3 * i + 1], pd[3 * i + 2], idf);
-    }
-    HIP_TRY(s->tO.alloc(sizeof(float4) * (size_t)n));
-    HIP_TRY(s->tD.alloc(sizeof(float4) * (size_t)n));
-    // the rays fill the regions front to back: region r holds rays [r*cap, r*cap + count(r))
-    const int cap = regionCapFor(n);
-    int hc[PG_REGIONS * PG_COUNT_STRIDE] = {0};
-    for (int r = 0; r < PG_REGIONS; ++r) hc[r * PG_COUNT_STRIDE] = std::max(0, std::min(cap, n - r * cap));
-    HIP_TRY(s->tCount.alloc(sizeof(hc)));
-    HIP_TRY(hipMemcpyAsync(s->tO.p, qo.data(), s->tO.bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(s->tD.p, qd.data(), s->tD.bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(s->tCount.p, hc, sizeof(hc), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PG_OK;
-}
-static RayQueue testQueue(PgScene *s, int n) {
-    RayQueue q;
-    q.o = (float4 *)s->tO.p; q.d = (float4 *)s->tD.p; q.counts = (int *)s->tCount.p; q.regionCap = regionCapFor(n);
-    return q;
-}
-
-static int intersectBatch(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, int32_t *prim, float *t, float *bary, int mem,
-                          void *streamPtr);
-int pg_intersect(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, int32_t *prim, float *t, float *bary, int mem,
-                 void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !prim || !t || !bary))) return setError(PG_ERR_INVALID, "pg_intersect: null argument");
-    if (n == 0) return PG_OK;
-    return withExactFallback(s, [&]() { return intersectBatch(s, n, o, d, tmax, prim, t, bary, mem, streamPtr); });
-}
-static int intersectBatch(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, int32_t *prim, float *t, float *bary, int mem,
-                          void *streamPtr) {
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = (hipStream_t)streamPtr;
-    int st = uploadRays(s, n, o, d, tmax, mem, stream);
-    if (st != PG_OK) return st;
-    HIP_TRY(s->tHit.alloc(sizeof(float4) * (size_t)n));
-    HIP_TRY(s->tT.alloc(sizeof(float) * (size_t)n));
-    RayQueue q = testQueue(s, n);
-    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
-    HIP_TRY(hipEventRecord(a, stream));
-    traceClosest(s, q, (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, stream);
-    HIP_TRY(hipEventRecord(b, stream));
-    HIP_TRY(hipGetLastError());
-    std::vector<float4> hits((size_t)n);
-    std::vector<float> ts((size_t)n);
-    HIP_TRY(hipMemcpyAsync(hits.data(), s->tHit.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(ts.data(), s->tT.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    std::vector<int32_t> hp((size_t)n);
-    std::vector<float> hb(3 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        memcpy(&hp[i], &hits[i].x, 4);
-        bool hit = hp[i] >= 0;
-        hb[3 * i] = hit ? hits[i].y : 0; hb[3 * i + 1] = hit ? hits[i].z : 0; hb[3 * i + 2] = hit ? hits[i].w : 0;
-    }
-    hipMemcpyKind kind = mem == PG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
-    HIP_TRY(hipMemcpy(prim, hp.data(), sizeof(int32_t) * (size_t)n, kind));
-    HIP_TRY(hipMemcpy(t, ts.data(), sizeof(float) * (size_t)n, kind));
-    HIP_TRY(hipMemcpy(bary, hb.data(), sizeof(float) * 3 * (size_t)n, kind));
-    TraceCounters tc[2];
-    HIP_TRY(hipMemcpy(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost));
-    PgCounters &c = s->counters;
-    c.closest_rays += (uint64_t)n;
-    c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
-    c.node_visits = tc[0].node_visits + tc[1].node_visits;
-    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    c.closest_launches += 1;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) c.closest_ms += ms;
-    return checkCullGuard(s);
-}
-
-int pg_intersect_p(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, uint8_t *occluded, int mem, void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p: null argument");
-    if (n == 0) return PG_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = (hipStream_t)streamPtr;
-    int st = uploadRays(s, n, o, d, tmax, mem, stream);
-    if (st != PG_OK) return st;
-    HIP_TRY(s->tOcc.alloc(sizeof(int) * (size_t)n));
-    RayQueue q = testQueue(s, n);
-    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
-    HIP_TRY(hipEventRecord(a, stream));
-    traceAnyhit(s, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, stream);
-    HIP_TRY(hipEventRecord(b, stream));
-    HIP_TRY(hipGetLastError());
-    std::vector<int> occ((size_t)n);
-    HIP_TRY(hipMemcpyAsync(occ.data(), s->tOcc.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    std::vector<uint8_t> o8((size_t)n);
-    for (int i = 0; i < n; ++i) o8[i] = occ[i] ? 1 : 0;
-    HIP_TRY(hipMemcpy(occluded, o8.data(), (size_t)n, mem == PG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost));
-    TraceCounters tc[2];
-    HIP_TRY(hipMemcpy(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost));
-    PgCounters &c = s->counters;
-    c.shadow_rays += (uint64_t)n;
-    c.shadow_node_visits = tc[1].node_visits; c.shadow_tri_tests = tc[1].tri_tests;
-    c.node_visits = tc[0].node_visits + tc[1].node_visits;
-    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    c.shadow_launches += 1;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) c.shadow_ms += ms;
-    return PG_OK;
-}
-
-// ---- the same with Ray::time, returning the SurfaceInteraction (pg_interaction.h) ------
-// The test-path buffers only grow here: DeviceBuffer::alloc frees first, and hipFree waits for the device
+// pg_intersect / pg_intersect_p (rays at time 0; primitive, t and barycentrics) and pg_intersect_at / pg_intersect_p_at (Ray::time; the
+// SurfaceInteraction, pg_interaction.h) are one device path, rayQuery: pack, trace, emit, account, one wait.
+// The test-path buffers only grow: DeviceBuffer::alloc frees first, and hipFree waits for the device
 static hipError_t reserve(DeviceBuffer &b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes); }
 // The rays into the test queue ON the device (k_pack_rays), their times behind `d` in PG_QUEUE_TIMES's layout -- for every scene: a still scene's
 // k_trace does not read them, the records report them.  Host rays are staged in tIn; the caller's arrays must outlive the stream's work, which the
@@ -1436,98 +1302,121 @@ static int packRays(PgScene *s, int n, const float *o, const float *d, const flo
         if (time) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + n, time, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
         o = in; d = in + n3; tmax = in + 2 * n3; time = time ? in + 2 * n3 + n : nullptr;
     }
-    q = testQueue(s, n);
+    q.o = (float4 *)s->tO.p; q.d = (float4 *)s->tD.p; q.counts = (int *)s->tCount.p; q.regionCap = regionCapFor(n);
     times = reinterpret_cast<float *>(q.d + N);
     launch_pack_rays(o, d, tmax, time, n, q, times, stream);
     return PG_OK;
 }
 
-static int intersectAtBatch(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *out, int mem,
-                            void *streamPtr) {
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = (hipStream_t)streamPtr;
-    RayQueue q;
-    float *times = nullptr;
-    if (int st = packRays(s, n, o, d, tmax, time, mem, stream, q, times)) return st;
-    HIP_TRY(reserve(s->tHit, sizeof(float4) * (size_t)n));
-    HIP_TRY(reserve(s->tT, sizeof(float) * (size_t)n));
-    // the launches see the scene as a frame's do -- the hits' instances, a moving one's matrices at the ray's time, rayTimes as the scene has it --
-    // over this call's own buffers (traceClosest clears all three for the unit entry points)
-    DScene dsc = s->d;
-    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
-    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * (size_t)n)); dsc.hitInst = (int *)s->tInst.p; }
-    if (dsc.hasMotion) {
-        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * (size_t)n * PG_XF_STRIDE * sizeof(float)));  // (hasNest: a second half for the inner transform)
-        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = n;
-    }
-    PgInteraction *dOut = out;  // PG_MEM_DEVICE: k_interaction writes the caller's records
-    if (mem != PG_MEM_DEVICE) { HIP_TRY(reserve(s->tOut, sizeof(PgInteraction) * (size_t)n)); dOut = (PgInteraction *)s->tOut.p; }
-    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
-    HIP_TRY(hipEventRecord(a, stream));
-    launch_closest(dsc, s->trace, q, (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-    HIP_TRY(hipEventRecord(b, stream));
-    launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dOut, stream);
-    HIP_TRY(hipGetLastError());
-    if (mem != PG_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(out, dOut, sizeof(PgInteraction) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    TraceCounters tc[2];
-    int guard = 0;
-    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait: the cull guard decides whether the records stand
-    PgCounters &c = s->counters;
-    c.closest_rays += (uint64_t)n;
-    c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
+// One call of the four entry points: the rays, and the caller's arrays (in `mem`) of the one kind of result it asks for
+struct RayQuery {
+    int32_t n;
+    const float *o, *d, *tmax, *time;  // time == nullptr: every ray at time 0
+    bool anyhit;                       // Scene::IntersectP
+    bool at;                           // the _at pair: the rays' times count, a closest hit's record is the PgInteraction
+    int32_t *prim; float *t, *bary;    // pg_intersect
+    PgInteraction *out;                // pg_intersect_at
+    uint8_t *occluded;                 // pg_intersect_p, pg_intersect_p_at
+    int mem;
+    void *stream;
+};
+// The statistics of one query launch, from the device's totals (tc[0] closest hit, tc[1] any hit) as read after it
+static void countQuery(PgCounters &c, bool anyhit, int n, const TraceCounters *tc, hipEvent_t a, hipEvent_t b) {
+    (anyhit ? c.shadow_rays : c.closest_rays) += (uint64_t)n;
+    (anyhit ? c.shadow_node_visits : c.closest_node_visits) = tc[anyhit].node_visits;
+    (anyhit ? c.shadow_tri_tests : c.closest_tri_tests) = tc[anyhit].tri_tests;
     c.node_visits = tc[0].node_visits + tc[1].node_visits;
     c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    c.closest_launches += 1;
+    (anyhit ? c.shadow_launches : c.closest_launches) += 1;
     float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) c.closest_ms += ms;
+    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) (anyhit ? c.shadow_ms : c.closest_ms) += ms;
+}
+static int rayQuery(PgScene *s, const RayQuery &r) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)r.stream;
+    const size_t n = (size_t)r.n;
+    const bool device = r.mem == PG_MEM_DEVICE;
+    RayQueue q;
+    float *times = nullptr;
+    if (int st = packRays(s, r.n, r.o, r.d, r.tmax, r.time, r.mem, stream, q, times)) return st;
+    // --- the scene and the tunables the launch sees, per entry point:
+    //   pg_intersect       no instance or matrix records (primitive, t and barycentrics are all it reports); rays at time 0
+    //   pg_intersect_p     rays at time 0 (an any-hit launch touches neither record)
+    //   pg_intersect_at    as a frame's launch -- the hits' instances, a moving one's matrices at the ray's time -- over this call's own buffers
+    //   pg_intersect_p_at  no records; the rays' times as the scene has them
+    // any hit: in the reference's visiting order, so that the counters are the reference's (tests compare them)
+    DScene dsc = s->d;
+    TraceConfig cfg = s->trace;
+    if (!r.at) dsc.rayTimes = 0;
+    if (r.at || !r.anyhit) { dsc.hitInst = nullptr; dsc.animXf = nullptr; }
+    if (r.anyhit) cfg.anyhitFree = 0;
+    if (r.at && !r.anyhit) {
+        dsc.nestXfOff = 0;
+        if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * n)); dsc.hitInst = (int *)s->tInst.p; }
+        if (dsc.hasMotion) {
+            HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * n * PG_XF_STRIDE * sizeof(float)));  // (hasNest: a second half for the inner transform)
+            dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = r.n;
+        }
+    }
+    if (r.anyhit) HIP_TRY(reserve(s->tOcc, sizeof(int) * n));
+    else { HIP_TRY(reserve(s->tHit, sizeof(float4) * n)); HIP_TRY(reserve(s->tT, sizeof(float) * n)); }
+    // --- the results: PG_MEM_DEVICE: the kernels write the caller's arrays; otherwise into tOut, copied to the caller below
+    const size_t outBytes = r.anyhit ? n : r.at ? sizeof(PgInteraction) * n : 5 * sizeof(float) * n;  // (pg_intersect: prim, t, three barycentrics)
+    if (!device) HIP_TRY(reserve(s->tOut, outBytes));
+    int32_t *dPrim = device ? r.prim : (int32_t *)s->tOut.p;
+    float *dT = device ? r.t : (float *)s->tOut.p + n, *dBary = device ? r.bary : (float *)s->tOut.p + 2 * n;
+    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
+    HIP_TRY(hipEventRecord(a, stream));
+    if (r.anyhit) launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
+    else launch_closest(dsc, cfg, q, (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+    HIP_TRY(hipEventRecord(b, stream));
+    if (r.anyhit) launch_occluded_bytes((const int *)s->tOcc.p, device ? r.occluded : (uint8_t *)s->tOut.p, r.n, stream);
+    else if (r.at) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, device ? r.out : (PgInteraction *)s->tOut.p, stream);
+    else launch_hit_arrays((const float4 *)s->tHit.p, (const float *)s->tT.p, dPrim, dT, dBary, r.n, stream);
+    HIP_TRY(hipGetLastError());
+    if (!device) {
+        if (r.anyhit || r.at) HIP_TRY(hipMemcpyAsync(r.anyhit ? (void *)r.occluded : (void *)r.out, s->tOut.p, outBytes, hipMemcpyDeviceToHost, stream));
+        else {
+            HIP_TRY(hipMemcpyAsync(r.prim, dPrim, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(r.t, dT, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(r.bary, dBary, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, stream));
+        }
+    }
+    TraceCounters tc[2];
+    int guard = 0;  // (only a closest-hit launch can raise it)
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    if (!r.anyhit) HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait: the cull guard decides whether the results stand
+    countQuery(s->counters, r.anyhit, r.n, tc, a, b);
     return cullGuardStatus(s, guard);
+}
+
+int pg_intersect(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, int32_t *prim, float *t, float *bary, int mem,
+                 void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !prim || !t || !bary))) return setError(PG_ERR_INVALID, "pg_intersect: null argument");
+    if (n == 0) return PG_OK;
+    const RayQuery r = {n, o, d, tmax, nullptr, false, false, prim, t, bary, nullptr, nullptr, mem, streamPtr};
+    return withExactFallback(s, [&]() { return rayQuery(s, r); });
+}
+int pg_intersect_p(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, uint8_t *occluded, int mem, void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p: null argument");
+    if (n == 0) return PG_OK;
+    return rayQuery(s, {n, o, d, tmax, nullptr, true, false, nullptr, nullptr, nullptr, nullptr, occluded, mem, streamPtr});
 }
 int pg_intersect_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *out, int mem,
                     void *streamPtr) {
     if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !out))) return setError(PG_ERR_INVALID, "pg_intersect_at: null argument");
     if (n == 0) return PG_OK;
-    return withExactFallback(s, [&]() { return intersectAtBatch(s, n, o, d, tmax, time, out, mem, streamPtr); });
+    const RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, out, nullptr, mem, streamPtr};
+    return withExactFallback(s, [&]() { return rayQuery(s, r); });
 }
-
 int pg_intersect_p_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, uint8_t *occluded, int mem,
                       void *streamPtr) {
     if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p_at: null argument");
     if (n == 0) return PG_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = (hipStream_t)streamPtr;
-    RayQueue q;
-    float *times = nullptr;
-    if (int st = packRays(s, n, o, d, tmax, time, mem, stream, q, times)) return st;
-    HIP_TRY(reserve(s->tOcc, sizeof(int) * (size_t)n));
-    uint8_t *dOcc = occluded;
-    if (mem != PG_MEM_DEVICE) { HIP_TRY(reserve(s->tOut, (size_t)n)); dOcc = (uint8_t *)s->tOut.p; }
-    // in the reference's visiting order, as traceAnyhit -- but with the rays' times (rayTimes as the scene has it)
-    TraceConfig cfg = s->trace;
-    cfg.anyhitFree = 0;
-    DScene dsc = s->d;
-    dsc.hitInst = nullptr; dsc.animXf = nullptr;  // (a closest hit's: an any-hit launch touches neither)
-    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
-    HIP_TRY(hipEventRecord(a, stream));
-    launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
-    HIP_TRY(hipEventRecord(b, stream));
-    launch_occluded_bytes((const int *)s->tOcc.p, dOcc, n, stream);
-    HIP_TRY(hipGetLastError());
-    if (mem != PG_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(occluded, dOcc, (size_t)n, hipMemcpyDeviceToHost, stream));
-    TraceCounters tc[2];
-    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    PgCounters &c = s->counters;
-    c.shadow_rays += (uint64_t)n;
-    c.shadow_node_visits = tc[1].node_visits; c.shadow_tri_tests = tc[1].tri_tests;
-    c.node_visits = tc[0].node_visits + tc[1].node_visits;
-    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    c.shadow_launches += 1;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) c.shadow_ms += ms;
-    return PG_OK;
+    return rayQuery(s, {n, o, d, tmax, time, true, true, nullptr, nullptr, nullptr, nullptr, occluded, mem, streamPtr});
 }
+
 
 int pg_counters(PgScene *s, PgCounters *out) {
     if (!s || !out) return setError(PG_ERR_INVALID, "pg_counters: null argument");

@@ -1,9 +1,10 @@
-// pg_interaction.h -- the kernels of the ray queries with per-ray time (pg_intersect_at / pg_intersect_p_at, pg_abi.hip): Scene::Intersect's
-// SurfaceInteraction written out per ray for an integrator whose Li stays on the host.  Included at the end of pg_kernels.hip, like pg_direct.h:
+// pg_interaction.h -- the kernels of the ray queries (pg_intersect[_p] and pg_intersect_at / pg_intersect_p_at, pg_abi.hip's rayQuery): the rays into
+// the test queue, the results out of it -- for the _at pair Scene::Intersect's SurfaceInteraction per ray at the ray's time, for an integrator whose
+// Li stays on the host.  Included at the end of pg_kernels.hip, like pg_direct.h:
 // the interaction is hit_isect's (pg_hit.h), under the transforms k_trace left for the hit (hitInst, animXf at the ray's time) -- the very functions
 // the shading kernels call, nothing restated.  No material is evaluated: Material::Bump belongs to ComputeScatteringFunctions, not to Intersect.
 //
-// The queue is the unit entry points' test queue: ray i is entry i (the regions are filled front to back), its time is float i behind `d`
+// The queue is the entry points' test queue: ray i is entry i (the regions are filled front to back), its time is float i behind `d`
 // (PG_QUEUE_TIMES's layout, kept for every scene: a still scene's k_trace does not read it, the record reports it).
 #ifndef PG_INTERACTION_H
 #define PG_INTERACTION_H
@@ -72,6 +73,23 @@ void launch_interaction(const DScene &sc, RayQueue q, const float4 *hits, const 
     const int nblk = PG_REGIONS * (q.regionCap / PG_BLOCK);
     if (nblk == 0) return;
     hipLaunchKernelGGL(k_interaction, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, q, hits, tHit, times, reinterpret_cast<float4 *>(out));
+}
+
+// pg_intersect's arrays from the closest-hit launch's records: the primitive, t = ray.tMax as k_trace left it, the barycentrics (0 on a miss)
+__global__ __launch_bounds__(PG_BLOCK) void k_hit_arrays(const float4 *__restrict__ hits, const float *__restrict__ tHit, int32_t *__restrict__ prim,
+                                                          float *__restrict__ t, float *__restrict__ bary, int n) {
+    const int i = blockIdx.x * PG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 h4 = hits[i];
+    const bool hit = __float_as_int(h4.x) >= 0;
+    const size_t k = 3 * (size_t)i;
+    prim[i] = __float_as_int(h4.x);
+    t[i] = tHit[i];
+    bary[k] = hit ? h4.y : 0.f; bary[k + 1] = hit ? h4.z : 0.f; bary[k + 2] = hit ? h4.w : 0.f;
+}
+void launch_hit_arrays(const float4 *hits, const float *tHit, int32_t *prim, float *t, float *bary, int n, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_hit_arrays, dim3((n + PG_BLOCK - 1) / PG_BLOCK), dim3(PG_BLOCK), 0, s, hits, tHit, prim, t, bary, n);
 }
 
 // k_trace's any-hit answers (one int per ray) as the entry point's bytes

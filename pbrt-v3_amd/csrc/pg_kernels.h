@@ -482,11 +482,13 @@ struct DirectStep {
 void launch_direct(const DScene &sc, const RenderParams &rp, PathState st, RayQueue qin, const float4 *hits, RayQueue qnext, RayQueue qshadow, RayQueue qmis,
                    unsigned long long *lightTriTests, const DirectStep &ds, hipStream_t s);
 void launch_direct_fold(float4 *src, float4 *dst, float divisor, int n, hipStream_t s);
-// ---- the ray queries with per-ray time (pg_interaction.h).  All pointers are device memory.
+// ---- the ray queries (pg_interaction.h).  All pointers are device memory.
 // n rays (o, d: three floats each; time == nullptr: 0) into the test queue q, ray i at entry i, with its region counters; times[i] = Ray::time
 void launch_pack_rays(const float *o, const float *d, const float *tmax, const float *time, int n, RayQueue q, float *times, hipStream_t s);
 // out[i] = the SurfaceInteraction of q's entry i after launch_closest(sc, ..., q, hits, tHit, ...) (sc.hitInst / sc.animXf as that launch had them)
 void launch_interaction(const DScene &sc, RayQueue q, const float4 *hits, const float *tHit, const float *times, PgInteraction *out, hipStream_t s);
+// prim[i], t[i] = tHit[i] and bary[3i .. 3i+2] (0 on a miss) of rays 0 .. n-1 after launch_closest(..., hits, tHit, ...)
+void launch_hit_arrays(const float4 *hits, const float *tHit, int32_t *prim, float *t, float *bary, int n, hipStream_t s);
 void launch_occluded_bytes(const int *occluded, uint8_t *out, int n, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

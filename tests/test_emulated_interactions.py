@@ -30,4 +30,4 @@ def test_ray_queries_on_the_emulated_device(emulated):
                        capture_output=True, text=True, timeout=1800)
     tail = p.stdout[-3000:] + p.stderr[-1500:]
     assert p.returncode == 0, tail
-    assert "11 passed" in tail and "failed" not in tail and "skipped" not in tail, tail
+    assert "19 passed" in tail and "failed" not in tail and "skipped" not in tail, tail

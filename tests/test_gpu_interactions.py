@@ -1,6 +1,7 @@
 """pg_intersect_at / pg_intersect_p_at: batched Scene::Intersect / IntersectP with Ray::time, returning the SurfaceInteraction (PgInteraction,
 csrc/pg_interaction.h).  Against the oracle at time 0, against closed forms in float32 NumPy for the fields the oracle has no entry for, and --
 what an implementation that forwards to the time-0 launches of pg_intersect would fail -- against static scenes at the two ends of a motion.
+Section 5b: pg_intersect / pg_intersect_p, which go through the same device path, with host and with device memory.
 tests/test_emulated_interactions.py runs a subset of this file without a GPU."""
 import ctypes as C
 import os
@@ -447,6 +448,115 @@ def test_device_memory_output_equals_host_output(shutter, gpu):
     assert np.array_equal(dev.get(5, np.uint8), host_occ)
     gs.intersect_at_device(n, po, pd, pt, None, pout)  # no times
     assert np.array_equal(dev.get(4, np.uint8), gs.intersect_at(o, d, tmax).view(np.uint8))
+
+
+# ---- 5b. pg_intersect / pg_intersect_p, the unit pair, go through the same device path ------------------------------------------------------------------
+@pytest.fixture(scope="module", params=["cornell_32", "shutter"])
+def unit_case(request, gpu, shutter):
+    """(scene on the device, 2049 rays that hit and miss) for the golden Cornell box and for the moving, instanced scene of `shutter`."""
+    if request.param == "shutter":
+        yield (shutter["gs"],) + motion_rays(2049, 23)
+        return
+    scene = gpu.HostScene(os.path.join(GOLD, "cornell_32.pbrt"))
+    gs = gpu.GpuScene(scene.desc)
+    o, d, tmax = scene_rays(scene, 2049, 17)
+    mix = np.random.default_rng(18).permutation(len(tmax))[:2049]  # the aimed rays among the random ones
+    yield gs, np.ascontiguousarray(o[mix]), np.ascontiguousarray(d[mix]), np.ascontiguousarray(tmax[mix])
+    gs.close()
+
+
+PAD = 64  # elements the device arrays are longer than the results, to catch a write past them
+
+
+def unit_pair_on_device(gpu, gs, o, d, tmax):
+    """pg_intersect and pg_intersect_p with PG_MEM_DEVICE: the four result arrays as bytes, each PAD elements longer than its result and pre-filled 0xAB."""
+    n = len(tmax)
+    dev = DeviceArrays()
+    po, pd, pt = dev.put(o), dev.put(d), dev.put(tmax)
+    out = [dev.put(np.full(size, 0xAB, np.uint8)) for size in (4 * (n + PAD), 4 * (n + PAD), 4 * (3 * n + PAD), n + PAD)]
+    lib = gpu.gpu_lib()
+    assert lib.pg_intersect(gs._h, n, po, pd, pt, out[0], out[1], out[2], gpu.PG_MEM_DEVICE, None) == 0, lib.pg_last_error()
+    assert lib.pg_intersect_p(gs._h, n, po, pd, pt, out[3], gpu.PG_MEM_DEVICE, None) == 0, lib.pg_last_error()
+    return [dev.get(3 + k, np.uint8) for k in range(4)]
+
+
+def test_unit_pair_device_memory_equals_host_memory(unit_case, gpu):
+    gs, o, d, tmax = unit_case
+    n = 1000  # three regions of 256 entries and part of a fourth
+    o, d, tmax = o[:n], d[:n], tmax[:n]
+    prim, t, bary = gs.intersect(o, d, tmax)
+    occ = gs.intersect_p(o, d, tmax)
+    hit = prim >= 0
+    assert hit.sum() > 100 and (~hit).sum() > 20
+    assert not bits(bary[~hit]).any() and same_bits(t[~hit], tmax[~hit])  # a miss: three zeros, the ray's own tmax
+    assert np.array_equal(occ != 0, hit)
+    dprim, dt, dbary, docc = unit_pair_on_device(gpu, gs, o, d, tmax)
+    for got, want in ((dprim, prim), (dt, t), (dbary, bary), (docc, occ)):
+        assert np.array_equal(got[:want.nbytes], want.view(np.uint8).reshape(-1))
+        assert len(got) - want.nbytes == PAD * want.itemsize and (got[want.nbytes:] == 0xAB).all()
+
+
+def test_unit_pair_counters_do_not_depend_on_the_memory_kind(unit_case, gpu):
+    gs, o, d, tmax = unit_case
+    o, d, tmax = o[:1000], d[:1000], tmax[:1000]
+    keys = [kind + what for kind in ("closest_", "shadow_") for what in ("rays", "node_visits", "tri_tests", "launches")]
+    gs.counters_reset()
+    unit_pair_on_device(gpu, gs, o, d, tmax)
+    device = gs.counters()
+    gs.counters_reset()
+    gs.intersect(o, d, tmax)
+    gs.intersect_p(o, d, tmax)
+    host = gs.counters()
+    assert [device[k] for k in keys] == [host[k] for k in keys]
+    assert host["closest_rays"] == host["shadow_rays"] == 1000 and host["closest_launches"] == host["shadow_launches"] == 1
+    assert host["closest_node_visits"] > 1000 and host["shadow_node_visits"] > 1000 and host["closest_tri_tests"] > 0 and host["shadow_tri_tests"] > 0
+
+
+def test_unit_pair_batch_sizes_are_prefixes_of_one_batch(unit_case):
+    """The buffers grow up to the largest batch and are then reused by a smaller one."""
+    gs, o, d, tmax = unit_case
+    sizes = (1, 63, 64, 65, 257, 1000, 2049, 1)
+    got = [gs.intersect(o[:n], d[:n], tmax[:n]) + (gs.intersect_p(o[:n], d[:n], tmax[:n]),) for n in sizes]
+    whole = got[sizes.index(2049)]
+    assert len(set(whole[0])) >= 8 and (whole[0] < 0).any()
+    for n, part in zip(sizes, got):
+        for a, b in zip(part, whole):
+            assert len(a) == n and a.tobytes() == b[:n].tobytes(), n
+
+
+def test_unit_pair_is_the_at_pair_without_times(shutter):
+    """On the moving scene: rays without a time are rays at time 0, whichever entry point takes them."""
+    o, d, tmax = shutter["rays"]
+    gs = shutter["gs"]
+    prim, t, _ = gs.intersect(o, d, tmax)
+    rec = gs.intersect_at(o, d, tmax, time=None)
+    assert np.array_equal(prim, rec["prim"]) and same_bits(t, rec["t"])
+    assert ((rec["instance"] >= 0) & (prim >= 0)).sum() > 300 and (prim < 0).any()
+    assert np.array_equal(gs.intersect_p(o, d, tmax), gs.intersect_p_at(o, d, tmax, time=None))
+
+
+def test_unit_pair_refused_arguments(shutter, gpu):
+    gs = shutter["gs"]
+    lib = gpu.gpu_lib()
+    o, d, tmax = (np.ascontiguousarray(x[:4]) for x in shutter["rays"])
+    prim, t, bary, occ = np.zeros(4, np.int32), np.zeros(4, F32), np.zeros((4, 3), F32), np.zeros(4, np.uint8)
+    before = gs.counters()
+    assert lib.pg_intersect(gs._h, 0, None, None, None, None, None, None, gpu.PG_MEM_HOST, None) == 0  # n == 0 touches nothing, not even its arguments
+    assert lib.pg_intersect_p(gs._h, 0, None, None, None, None, gpu.PG_MEM_HOST, None) == 0
+    assert gs.counters() == before
+    closest, anyhit = [a.ctypes.data for a in (o, d, tmax, prim, t, bary)], [a.ctypes.data for a in (o, d, tmax, occ)]
+    for mem in (gpu.PG_MEM_HOST, gpu.PG_MEM_DEVICE):
+        for k in range(len(closest)):
+            assert lib.pg_intersect(gs._h, 4, *closest[:k], None, *closest[k + 1:], mem, None) == -1  # PG_ERR_INVALID
+            assert b"pg_intersect:" in lib.pg_last_error()
+        for k in range(len(anyhit)):
+            assert lib.pg_intersect_p(gs._h, 4, *anyhit[:k], None, *anyhit[k + 1:], mem, None) == -1
+            assert b"pg_intersect_p:" in lib.pg_last_error()
+    assert gs.counters() == before and not prim.any() and not bits(t).any() and not bits(bary).any() and not occ.any()  # no device work followed
+    with pytest.raises(ValueError):
+        gs.intersect(o, d[:3], tmax)
+    with pytest.raises(ValueError):
+        gs.intersect_p(o[:3], d, tmax)
 
 
 # ---- 6. arguments --------------------------------------------------------------------------------------------------------------------------------
