@@ -1,14 +1,16 @@
 // pg_bxdf.h -- the BSDFs as device functions: the specialised Bsdf of matte / plastic / mirror / glass with its microfacet
 // trigonometry, and the BxDF-list LobeBsdfT over PgBxDF or PkLobe records (lobe_f / lobe_pdf / lobe_f_pdf / lobe_sample_f per BxDF,
-// lbsdf_f / lbsdf_pdf / lbsdf_sample_f over a list).
+// lbsdf_f / lbsdf_pdf / lbsdf_sample_f over a list), the one-lobe AdapterBsdf at a BSSRDF's exit point, and what EstimateDirect asks of any of
+// them (scatter_f_cos / scatter_pdf / scatter_sample; pg_medium.h has the phase function's).
 //
 // Used by k_shade, k_sss_exit (pg_kernels.hip) and k_direct (pg_direct.h).  lobe_f_pdf and lobe_sample_f are pinned on the host
-// (tests/test_device_headers_on_host.py) and on the device (tests/test_gpu_device_arithmetic.py).
+// (tests/test_device_headers_on_host.py) and on the device (tests/test_gpu_device_arithmetic.py), and so are AdapterBsdf's three functions.
 #ifndef PG_BXDF_H
 #define PG_BXDF_H
 #include "pg_device.h"
 #include "pg_kernels.h"
 #include "pg_texture.h"
+#include "pg_bssrdf.h"
 
 // BSDF: LambertianReflection and/or MicrofacetReflection(TrowbridgeReitz, FresnelDielectric(1.5, 1)) lobes in the order
 // the materials add them (matte.cpp:45-62, plastic.cpp:45-70); reflection.h:164-213, reflection.cpp:680-796.
@@ -671,6 +673,65 @@ template <class LB> PG_DEV Spec lbsdf_sample_f(const LobeBsdfT<LB> &b, V3 woWorl
     }
     if (matchingComps > 1) pdf /= matchingComps;
     return f;
+}
+
+// The BSDF at a BSSRDF's exit point: one SeparableBSSRDFAdapter (bssrdf.h:209-225), a BxDF of type BSDF_REFLECTION | BSDF_DIFFUSE
+// with f = Sw(wi) * eta^2 (TransportMode::Radiance) and BxDF's own cosine-hemisphere Sample_f / Pdf (reflection.cpp:383-394), under
+// BSDF::f / ::Pdf / ::Sample_f (reflection.cpp:680-796) for a list of one.
+struct AdapterBsdf { V3 ns, ng, ss, ts; float eta; };
+PG_DEV V3 ad_to_local(const AdapterBsdf &b, V3 v) { return mk(dot(v, b.ss), dot(v, b.ts), dot(v, b.ns)); }
+PG_DEV V3 ad_to_world(const AdapterBsdf &b, V3 v) {
+    return mk(b.ss.x * v.x + b.ts.x * v.y + b.ns.x * v.z, b.ss.y * v.x + b.ts.y * v.y + b.ns.y * v.z, b.ss.z * v.x + b.ts.z * v.y + b.ns.z * v.z);
+}
+PG_DEV Spec ad_lobe_f(const AdapterBsdf &b, V3 wiLocal) { return sp(bssrdf_adapter_f(b.eta, wiLocal.z, fr_dielectric(wiLocal.z, 1, b.eta))); }
+PG_DEV Spec ad_f(const AdapterBsdf &b, V3 woW, V3 wiW, int flags) {
+    const V3 wi = ad_to_local(b, wiW), wo = ad_to_local(b, woW);
+    if (wo.z == 0) return sp(0);
+    const int type = PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
+    const bool reflect = dot(wiW, b.ng) * dot(woW, b.ng) > 0;
+    return ((type & flags) == type && reflect) ? ad_lobe_f(b, wi) : sp(0);
+}
+PG_DEV float ad_pdf(const AdapterBsdf &b, V3 woW, V3 wiW, int flags) {
+    const V3 wo = ad_to_local(b, woW), wi = ad_to_local(b, wiW);
+    if (wo.z == 0) return 0.f;
+    const int type = PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
+    if ((type & flags) != type) return 0.f;
+    return same_hemisphere(wo, wi) ? fabsf(wi.z) * PG_INVPI : 0;
+}
+PG_DEV Spec ad_sample_f(const AdapterBsdf &b, V3 woW, V3 &wiW, float u0, float u1, float &pdf, int flags, int &sampledType) {
+    const int type = PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
+    sampledType = 0;
+    pdf = 0;
+    if ((type & flags) != type) return sp(0);  // matchingComps == 0
+    const float uR0 = pmin(u0 * 1 - 0, PG_ONE_MINUS_EPS);  // one matching component: comp = 0
+    const V3 wo = ad_to_local(b, woW);
+    if (wo.z == 0) return sp(0);
+    sampledType = type;
+    V3 wi = cosine_sample_hemisphere(uR0, u1);
+    if (wo.z < 0) wi.z *= -1;
+    pdf = same_hemisphere(wo, wi) ? fabsf(wi.z) * PG_INVPI : 0;
+    if (pdf == 0) { sampledType = 0; return sp(0); }
+    wiW = ad_to_world(b, wi);
+    return (dot(wiW, b.ng) * dot(woW, b.ng) > 0) ? ad_lobe_f(b, wi) : sp(0);
+}
+
+// ---- the scattering model at EstimateDirect's reference point (pg_estimate.h), one overload set per model: f * |wi . ns| and the pdf of a given
+// pair over the non-specular BxDFs (integrator.cpp:128-131 with bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR), and Sample_f's direction with its f * |cos|
+// and pdf (:170-174).  A model that samples nothing leaves wi as it came and pdf = 0.
+#define PG_BSDF_NON_SPECULAR (PG_BSDF_ALL & ~PG_BSDF_SPECULAR)
+template <class LB> PG_DEV Spec scatter_f_cos(const LobeBsdfT<LB> &b, V3 wo, V3 wi) { return lbsdf_f(b, wo, wi, PG_BSDF_NON_SPECULAR) * absdot(wi, b.ns); }
+template <class LB> PG_DEV float scatter_pdf(const LobeBsdfT<LB> &b, V3 wo, V3 wi) { return lbsdf_pdf(b, wo, wi, PG_BSDF_NON_SPECULAR); }
+template <class LB> PG_DEV Spec scatter_sample(const LobeBsdfT<LB> &b, V3 wo, V3 &wi, float u0, float u1, float &pdf) {
+    int sampledType;
+    const Spec f = lbsdf_sample_f(b, wo, wi, u0, u1, pdf, PG_BSDF_NON_SPECULAR, sampledType);
+    return f * absdot(wi, b.ns);
+}
+PG_DEV Spec scatter_f_cos(const AdapterBsdf &b, V3 wo, V3 wi) { return ad_f(b, wo, wi, PG_BSDF_NON_SPECULAR) * absdot(wi, b.ns); }
+PG_DEV float scatter_pdf(const AdapterBsdf &b, V3 wo, V3 wi) { return ad_pdf(b, wo, wi, PG_BSDF_NON_SPECULAR); }
+PG_DEV Spec scatter_sample(const AdapterBsdf &b, V3 wo, V3 &wi, float u0, float u1, float &pdf) {
+    int sampledType;
+    const Spec f = ad_sample_f(b, wo, wi, u0, u1, pdf, PG_BSDF_NON_SPECULAR, sampledType);
+    return f * absdot(wi, b.ns);
 }
 
 #endif  // PG_BXDF_H

@@ -1,7 +1,8 @@
 // pg_direct.h -- the DirectLightingIntegrator's kernels (integrators/directlighting.cpp:62-95 without its specular bounces, which pg_render_direct
 // refuses).  Included at the end of pg_kernels.hip: everything here is built from the pieces that file includes -- the interaction (hit_isect), an emitter's
-// L (area_light_l), the BxDF lists and the material evaluators, the light sampling with its shadow ray (shadow_ray_to), light.Pdf_Li of the
-// BSDF-sampled direction (mis_light_pdf), the queue appends -- and k_resolve itself finishes every EstimateDirect.  None of them is restated here.
+// L (area_light_l), the BxDF lists and the material evaluators, EstimateDirect's set-up (estimate_direct_setup, pg_estimate.h) with its shadow ray
+// (shadow_ray_to) and light.Pdf_Li of the BSDF-sampled direction (mis_light_pdf), the queue appends -- and k_resolve itself finishes every
+// EstimateDirect.  None of them is restated here: what k_direct adds is its choice of the light, its draws and where the step's terms go.
 //
 // A camera ray's closest hit stays in its main queue while the frame walks the (light, sample) steps: every step is ONE launch of k_direct over the
 // queue, which rebuilds the hit's interaction and BSDF, draws the step's uLight / uScattering, and leaves a shadow ray, a BSDF-sampled ray and the
@@ -107,43 +108,23 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
                     lightNum = ds.light;
                     if (ds.light == -2) { lightNum = (int)(uSel * sc.nLights); if (lightNum > sc.nLights - 1) lightNum = sc.nLights - 1; }  // integrator.cpp:95
                     // ---- EstimateDirect (integrator.cpp:108-215) with bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR, up to the two rays
-                    const int nonSpecular = PG_BSDF_ALL & ~PG_BSDF_SPECULAR;
-                    const LightHot lh = load_light_hot(sc, lightNum);
-                    const PgLight &light = sc.lights[lightNum];
-                    V3 wi = mk(0, 0, 0);
-                    float lightPdf = 0, scatteringPdf = 0;
-                    LightSample ls;
-                    const Spec Li = light_sample_li_hot<true>(sc, lh, light, is.p, is.pError, is.n, uL0, uL1, wi, lightPdf, ls);
-                    if (lightPdf > 0 && !is_black(Li)) {
-                        const Spec f = lbsdf_f(lb, is.wo, wi, nonSpecular) * absdot(wi, lb.ns);
-                        scatteringPdf = lbsdf_pdf(lb, is.wo, wi, nonSpecular);
-                        if (!is_black(f)) {
-                            shadow_ray_to(is.p, is.pError, is.n, ls, slot, shadowO, shadowD);
-                            pushShadow = true;
-                            const Spec c = PG_LIGHT_IS_DELTA(lh.type) ? (f * Li) / lightPdf : ((f * Li) * power_heuristic(1, lightPdf, 1, scatteringPdf)) / lightPdf;
-                            pdLight = make_float4(c.r, c.g, c.b, 1);
-                        }
+                    const DirectSetup ed = estimate_direct_setup<true>(sc, lb, is.p, is.pError, is.n, is.wo, lightNum, uL0, uL1, uS0, uS1);
+                    if (ed.light.shadow) {
+                        shadow_ray_to(is.p, is.pError, is.n, ed.light.ls, slot, shadowO, shadowD);
+                        pushShadow = true;
+                        const Spec c = direct_light_folded(ed.light);
+                        pdLight = make_float4(c.r, c.g, c.b, 1);
                     }
-                    if (lh.type == PG_LIGHT_AREA || lh.type == PG_LIGHT_INFINITE) {  // integrator.cpp:164: if (!IsDeltaLight(light.flags))
-                        V3 wi2 = wi;
-                        float sPdf2 = 0;
-                        int sampledType;
-                        Spec f2 = lbsdf_sample_f(lb, is.wo, wi2, uS0, uS1, sPdf2, nonSpecular, sampledType);
-                        f2 = f2 * absdot(wi2, lb.ns);
-                        if (!is_black(f2) && sPdf2 > 0) {
-                            V3 misRo;
-                            spawn_ray(is, wi2, misRo);
-                            int lightPrim;
-                            bool inside;
-                            mis_light_of(sc, lh, lightNum, is.p, is.pError, is.n, lightPrim, inside);
-                            const float lightPdf2 = mis_light_pdf<true>(sc, lightPrim, lh.area, inside, is.p, misRo, wi2, nLightTests);
-                            if (lightPdf2 != 0) {
-                                misO = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
-                                misD = make_float4(wi2.x, wi2.y, wi2.z, __int_as_float(slot));
-                                pushMis = true;
-                                pdMis = make_float4(f2.r, f2.g, f2.b, sPdf2);
-                                misWeight = power_heuristic(1, sPdf2, 1, lightPdf2);
-                            }
+                    if (ed.mis.cand) {  // light.Pdf_Li of the sampled direction at once: nothing else is live here
+                        V3 misRo;
+                        spawn_ray(is, ed.mis.wi, misRo);
+                        const float lightPdf2 = mis_light_pdf<true>(sc, ed.mis.lightPrim, ed.mis.area, ed.mis.inside, is.p, misRo, ed.mis.wi, nLightTests);
+                        if (lightPdf2 != 0) {
+                            misO = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
+                            misD = make_float4(ed.mis.wi.x, ed.mis.wi.y, ed.mis.wi.z, __int_as_float(slot));
+                            pushMis = true;
+                            pdMis = make_float4(ed.mis.f.r, ed.mis.f.g, ed.mis.f.b, ed.mis.pdf);
+                            misWeight = power_heuristic(1, ed.mis.pdf, 1, lightPdf2);
                         }
                     }
                 }
@@ -165,12 +146,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
     if (pushNext) { qnext.o[outPos[0]] = nextO; qnext.d[outPos[0]] = nextD; }
     if (pushShadow) { qshadow.o[outPos[1]] = shadowO; qshadow.d[outPos[1]] = shadowD; }
     if (pushMis) { qmis.o[outPos[2]] = misO; qmis.d[outPos[2]] = misD; }
-    if (sc.rayTimes) {  // the spawned rays carry the interaction's time = the ray's (interaction.h:77-95)
-        const float t = valid ? PG_QUEUE_TIMES(sc, qin)[i] : 0.f;
-        if (pushNext) PG_QUEUE_TIMES(sc, qnext)[outPos[0]] = t;
-        if (pushShadow) PG_QUEUE_TIMES(sc, qshadow)[outPos[1]] = t;
-        if (pushMis) PG_QUEUE_TIMES(sc, qmis)[outPos[2]] = t;
-    }
+    store_ray_times(sc, qin, i, outQ, outPred, outPos);
     if (valid) {  // k_resolve's pending terms, by queue position; its L += beta * (Ld / pdLight.w) is Ld itself here, added to the slot's accumulator
         st.pdInfo[i] = make_int4(outPos[1], outPos[2], lightNum, ~slot);
         if (pushShadow || pushMis) {
@@ -179,8 +155,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
             st.pdBeta[i] = make_float4(1, 1, 1, misWeight);
         }
     }
-    const unsigned long long nl = wave_sum(nLightTests);
-    if (lane_id() == 0 && nl) atomicAdd(lightTriTests + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE, nl);
+    flush_light_tests(lightTriTests, nLightTests);
 }
 void launch_direct(const DScene &sc, const RenderParams &rp, PathState st, RayQueue qin, const float4 *hits, RayQueue qnext, RayQueue qshadow, RayQueue qmis,
                    unsigned long long *lightTriTests, const DirectStep &ds, hipStream_t s) {

@@ -15,10 +15,11 @@
 // latency/bandwidth-bound gather over the node and triangle arrays.
 //
 // This file holds the kernels and their launch_* wrappers only.  The device functions they are built from live in headers, by subject:
-// pg_queue.h (queue append, statistics), pg_triangle.h (Tri, Isect, make_isect), pg_sampler.h, pg_camera.h, pg_bxdf.h (Bsdf, LobeBsdfT),
-// pg_material.h (MatEval), pg_light.h, pg_medium.h and pg_hit.h (the interaction of any hit; included last, it uses the others) -- beside
-// pg_device.h, pg_sphere.h, pg_texture.h, pg_motion.h, pg_bssrdf.h, pg_grid.h and pg_lens.h.  A helper of a single kernel (resolve_entry,
-// through_point, AdapterBsdf) stays with its kernel, and so do halton_batch and sample_discrete, below the includes.
+// pg_queue.h (queue append, statistics), pg_triangle.h (Tri, Isect, make_isect), pg_sampler.h, pg_camera.h, pg_bxdf.h (Bsdf, LobeBsdfT,
+// AdapterBsdf), pg_material.h (MatEval), pg_light.h, pg_medium.h, pg_hit.h (the interaction of any hit; it uses the others) and pg_estimate.h
+// (EstimateDirect's set-up over any of the scattering models; included last) -- beside pg_device.h, pg_sphere.h, pg_texture.h, pg_motion.h,
+// pg_bssrdf.h, pg_grid.h and pg_lens.h.  A helper of a single kernel (resolve_entry, through_point) stays with its kernel, and so do
+// halton_batch and sample_discrete, below the includes.
 #include "pg_device.h"
 #include "pg_sphere.h"
 #include "pg_kernels.h"
@@ -36,6 +37,7 @@
 #include "pg_light.h"
 #include "pg_medium.h"
 #include "pg_hit.h"
+#include "pg_estimate.h"
 
 // ---- the two device functions that stay here: each holds an empty `asm volatile` register-scheduling barrier, which the emulated-device
 // build (tests/emu/build_emulated.py) drops from this file by text, and only the kernels below call them ----------------------------
@@ -635,6 +637,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                 const V3 zero = mk(0, 0, 0), wo = -rayD;
                 const float *tab = (sc.nLights > 0 && !phaseB) ? light_distribution(sc, mediumP) : nullptr;
                 if (sc.nLights > 0 && !phaseB && !tab) deferred = true;
+                // (the statements below mirror estimate_direct_setup<true>(sc, HgPhase{g}, mediumP, 0, 0, wo, ...) of pg_estimate.h, which k_sss_exit and k_direct
+                // call: called here, the VOL instantiations lose registers they do not have -- MODE 2 with a grid medium a wave per SIMD; CHANGELOG.md)
                 if (tab) {  // UniformSampleOneLight(mi, ..., handleMedia = true), integrator.cpp:85-106
                     float lightSelPdf;
                     lightNum = sample_discrete(tab, sc.nLights, draw1(), lightSelPdf);
@@ -690,7 +694,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                 hg_sample_p(g, wo, wi, u0, u1);
                 s_ray[0][0][tid] = make_float4(mediumP.x, mediumP.y, mediumP.z, PG_INF);
                 s_ray[0][1][tid] = make_float4(wi.x, wi.y, wi.z, __int_as_float(slot));
-                nextBin = (wi.x < 0 ? 1 : 0) | (wi.y < 0 ? 2 : 0) | (wi.z < 0 ? 4 : 0);
+                nextBin = dir_octant(wi);
                 pushNext = true;  // the path stays in `med`
                 Spec rrBeta = beta * etaScale;  // volpath.cpp:178-184
                 if (max_component(rrBeta) < rd.rr_threshold && bounces > 3) {
@@ -832,6 +836,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                 if constexpr (EXT) hasNonSpecular = lbsdf_num_components(lb, nonSpecular) > 0;
                 else hasNonSpecular = bsdf.nBxDFs > 0 && !bsdf.specular;
                 // ---- direct lighting: UniformSampleOneLight (integrator.cpp:85-106) + EstimateDirect set-up
+                // (the statements mirror direct_light_half / direct_scatter_half of pg_estimate.h with this kernel's register relief between and inside them;
+                // called here, the plain instantiations keep their registers but the VOL ones do not -- CHANGELOG.md "one EstimateDirect set-up")
                 if (!VOL && hasNonSpecular && sc.nLights == 0) lightNum = -2;  // (still one of path.cpp:121's totalPaths -- and a zero-radiance one: k_resolve counts pdInfo.z != -1)
                 const bool wantLight = (VOL || hasNonSpecular) && sc.nLights > 0 && !phaseB;  // path.cpp:119: only with non-specular lobes (volpath.cpp:124-127: always)
                 const float *tab = wantLight ? light_distribution(sc, is.p) : nullptr;
@@ -928,7 +934,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                     spawn_ray(is, wi, nextO);
                     s_ray[0][0][tid] = make_float4(nextO.x, nextO.y, nextO.z, PG_INF);
                     s_ray[0][1][tid] = make_float4(wi.x, wi.y, wi.z, __int_as_float(slot));
-                    nextBin = (wi.x < 0 ? 1 : 0) | (wi.y < 0 ? 2 : 0) | (wi.z < 0 ? 4 : 0);
+                    nextBin = dir_octant(wi);
                     pushNext = true;
                     if constexpr (VOL) { newMed = dot(wi, is.n) > 0 ? mOut : mIn; if constexpr (!QSTATE) { if (!deferred) vs.medium[slot] = newMed; } }
                     bool throughBssrdf = false;
@@ -963,7 +969,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                             }
                         }
                     }
-                    // Russian roulette, path.cpp:176-184 (a path inside the BSSRDF branch: at its exit vertex, k_sss_exit)
+                    // Russian roulette, path.cpp:176-184 (a path inside the BSSRDF branch: at its exit vertex, k_sss_exit).  (Here and at the medium vertex the
+                    // statements mirror russian_roulette of pg_sampler.h: called, k_shade<1, VOL, ., GRID> spills one more register)
                     Spec rrBeta = beta * etaScale;
                     if (!throughBssrdf && max_component(rrBeta) < rd.rr_threshold && bounces > 3) {
                         float qq = pmax(.05f, 1 - max_component(rrBeta));
@@ -1033,12 +1040,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
     if (pushNext) { qnext.o[posNext] = s_ray[0][0][tid]; qnext.d[posNext] = s_ray[0][1][tid]; }
     if (pushShadow) { qshadow.o[posShadow] = s_ray[1][0][tid]; qshadow.d[posShadow] = s_ray[1][1][tid]; }
     if (pushMis) { qmis.o[posMis] = s_ray[2][0][tid]; qmis.d[posMis] = s_ray[2][1][tid]; }
-    if (sc.rayTimes) {  // scenes with moving shapes / instances: the spawned rays carry the interaction's time = the ray's (interaction.h:77-95)
-        const float t = valid ? PG_QUEUE_TIMES(sc, qin)[i] : 0.f;
-        if (pushNext) PG_QUEUE_TIMES(sc, qnext)[posNext] = t;
-        if (pushShadow) PG_QUEUE_TIMES(sc, qshadow)[posShadow] = t;
-        if (pushMis) PG_QUEUE_TIMES(sc, qmis)[posMis] = t;
-    }
+    store_ray_times(sc, qin, i, outQ, outPred, outPos);
     if constexpr (QSTATE) {
         if (valid && !deferred) {
             if (pushNext) {
@@ -1079,8 +1081,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
             }
         }
     }
-    unsigned long long nl = wave_sum(nLightTests);
-    if (lane_id() == 0 && nl) atomicAdd(lightTriTests + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE, nl);
+    flush_light_tests(lightTriTests, nLightTests);
     {   // the integrator's statistics (PgCounters, ABI 28).  "Path length" of the paths that end at this vertex: ReportValue(pathLength, bounces), path.cpp:186,
         // with `bounces` of the reference's loop = the count the path arrived with (a scattering vertex has raised the stored one since).  A path that goes on
         // through a BSSRDF reports in k_sss_exit; a grid scene's vertex reports in the phase that finishes it
@@ -1616,46 +1617,6 @@ void launch_sss_probe(const DScene &sc, SssState sss, int pass, RayQueue qin, co
     else hipLaunchKernelGGL((k_sss_probe<2, false>), dim3(nblk), dim3(PG_BLOCK), 0, s, sc, sss, qin, hits, qout, f);
 }
 
-// The BSDF at a BSSRDF's exit point: one SeparableBSSRDFAdapter (bssrdf.h:209-225), a BxDF of type BSDF_REFLECTION | BSDF_DIFFUSE
-// with f = Sw(wi) * eta^2 (TransportMode::Radiance) and BxDF's own cosine-hemisphere Sample_f / Pdf (reflection.cpp:383-394), under
-// BSDF::f / ::Pdf / ::Sample_f (reflection.cpp:680-796) for a list of one.
-struct AdapterBsdf { V3 ns, ng, ss, ts; float eta; };
-PG_DEV V3 ad_to_local(const AdapterBsdf &b, V3 v) { return mk(dot(v, b.ss), dot(v, b.ts), dot(v, b.ns)); }
-PG_DEV V3 ad_to_world(const AdapterBsdf &b, V3 v) {
-    return mk(b.ss.x * v.x + b.ts.x * v.y + b.ns.x * v.z, b.ss.y * v.x + b.ts.y * v.y + b.ns.y * v.z, b.ss.z * v.x + b.ts.z * v.y + b.ns.z * v.z);
-}
-PG_DEV Spec ad_lobe_f(const AdapterBsdf &b, V3 wiLocal) { return sp(bssrdf_adapter_f(b.eta, wiLocal.z, fr_dielectric(wiLocal.z, 1, b.eta))); }
-PG_DEV Spec ad_f(const AdapterBsdf &b, V3 woW, V3 wiW, int flags) {
-    const V3 wi = ad_to_local(b, wiW), wo = ad_to_local(b, woW);
-    if (wo.z == 0) return sp(0);
-    const int type = PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
-    const bool reflect = dot(wiW, b.ng) * dot(woW, b.ng) > 0;
-    return ((type & flags) == type && reflect) ? ad_lobe_f(b, wi) : sp(0);
-}
-PG_DEV float ad_pdf(const AdapterBsdf &b, V3 woW, V3 wiW, int flags) {
-    const V3 wo = ad_to_local(b, woW), wi = ad_to_local(b, wiW);
-    if (wo.z == 0) return 0.f;
-    const int type = PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
-    if ((type & flags) != type) return 0.f;
-    return same_hemisphere(wo, wi) ? fabsf(wi.z) * PG_INVPI : 0;
-}
-PG_DEV Spec ad_sample_f(const AdapterBsdf &b, V3 woW, V3 &wiW, float u0, float u1, float &pdf, int flags, int &sampledType) {
-    const int type = PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE;
-    sampledType = 0;
-    pdf = 0;
-    if ((type & flags) != type) return sp(0);  // matchingComps == 0
-    const float uR0 = pmin(u0 * 1 - 0, PG_ONE_MINUS_EPS);  // one matching component: comp = 0
-    const V3 wo = ad_to_local(b, woW);
-    if (wo.z == 0) return sp(0);
-    sampledType = type;
-    V3 wi = cosine_sample_hemisphere(uR0, u1);
-    if (wo.z < 0) wi.z *= -1;
-    pdf = same_hemisphere(wo, wi) ? fabsf(wi.z) * PG_INVPI : 0;
-    if (pdf == 0) { sampledType = 0; return sp(0); }
-    wiW = ad_to_world(b, wi);
-    return (dot(wiW, b.ng) * dot(woW, b.ng) > 0) ? ad_lobe_f(b, wi) : sp(0);
-}
-
 // The exit vertex pi of a path that went through a BSSRDF (path.cpp:157-174): Sp and its pdf (bssrdf.cpp:322-327), beta *= S / pdf,
 // direct lighting at pi under the adapter BSDF (UniformSampleOneLight / EstimateDirect: the shadow and MIS rays and their pending terms,
 // indexed by the job's queue position, resolved by k_resolve over the job queue), the next direction, Russian roulette (path.cpp:176-184).
@@ -1732,18 +1693,10 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
             AdapterBsdf ab;
             ab.ns = is.ns; ab.ng = is.n; ab.ss = normalize(is.sdpdu); ab.ts = cross(ab.ns, ab.ss); ab.eta = f0.w;
             is.wo = is.ns;
-            const int nonSpecular = PG_BSDF_ALL & ~PG_BSDF_SPECULAR;
             int mIn = 0, mOut = 0;  // VOL: pi's MediumInterface (the primitive's own, or the medium of the probe ray that found it)
             if constexpr (VOL) prim_interface(sc, prim, sss.medium[slot].y, mIn, mOut);
             // ---- L += beta * UniformSampleOneLight(pi, ...) (path.cpp:161-163; integrator.cpp:85-215)
-            if (phase != 2) {
-            const float *tab = sc.nLights > 0 ? light_distribution(sc, is.p) : nullptr;
-            bool misCand = false;
-            V3 misRo = mk(0, 0, 0), misWi = mk(0, 0, 1);
-            Spec misF = sp(0);
-            float misPdf = 0, misLightArea = 1;
-            int misLightPrim = 0;
-            bool misInside = false;
+            const float *tab = (phase != 2 && sc.nLights > 0) ? light_distribution(sc, is.p) : nullptr;
             if (tab) {
                 float lightSelPdf;
                 lightNum = sample_discrete(tab, sc.nLights, draw1(), lightSelPdf);
@@ -1751,66 +1704,36 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
                     float uL0, uL1, uS0, uS1;
                     draw2(uL0, uL1);
                     draw2(uS0, uS1);
-                    const LightHot lh = load_light_hot(sc, lightNum);
-                    const PgLight &light = sc.lights[lightNum];
-                    V3 wi = mk(0, 0, 0);
-                    float lightPdf = 0, scatteringPdf = 0;
+                    const DirectSetup ed = estimate_direct_setup<true>(sc, ab, is.p, is.pError, is.n, is.wo, lightNum, uL0, uL1, uS0, uS1);
                     float4 pdLight = make_float4(0, 0, 0, 0);
-                    LightSample ls;
-                    const Spec Li = light_sample_li_hot<true>(sc, lh, light, is.p, is.pError, is.n, uL0, uL1, wi, lightPdf, ls);
-                    if (lightPdf > 0 && !is_black(Li)) {
-                        const Spec f = ad_f(ab, is.wo, wi, nonSpecular) * absdot(wi, ab.ns);
-                        scatteringPdf = ad_pdf(ab, is.wo, wi, nonSpecular);
-                        if (!is_black(f)) {
-                            [[maybe_unused]] const V3 shD = shadow_ray_to(is.p, is.pError, is.n, ls, slot, s_ray[1][0][tid], s_ray[1][1][tid]);
-                            pushShadow = true;
-                            const bool isDelta = PG_LIGHT_IS_DELTA(lh.type);
-                            if constexpr (VOL) {
-                                volWeight = isDelta ? -1.f : power_heuristic(1, lightPdf, 1, scatteringPdf);
-                                pdLight = make_float4(f.r, f.g, f.b, 0);
-                                vs.pdLi[slot] = make_float4(Li.r, Li.g, Li.b, lightPdf);
-                                vs.p1[0][slot] = make_float4(ls.p.x, ls.p.y, ls.p.z, 0); vs.p1[1][slot] = make_float4(ls.pError.x, ls.pError.y, ls.pError.z, 0);
-                                vs.p1[2][slot] = make_float4(ls.n.x, ls.n.y, ls.n.z, 0);
-                                vs.trAcc[0][slot] = make_float4(1, 1, 1, __int_as_float(dot(shD, is.n) > 0 ? mOut : mIn));
-                            } else {
-                                const Spec c = isDelta ? (f * Li) / lightPdf : ((f * Li) * power_heuristic(1, lightPdf, 1, scatteringPdf)) / lightPdf;
-                                pdLight = make_float4(c.r, c.g, c.b, 0);
-                            }
+                    if (ed.light.shadow) {
+                        [[maybe_unused]] const V3 shD = shadow_ray_to(is.p, is.pError, is.n, ed.light.ls, slot, s_ray[1][0][tid], s_ray[1][1][tid]);
+                        pushShadow = true;
+                        if constexpr (VOL) {
+                            pdLight = make_float4(ed.light.f.r, ed.light.f.g, ed.light.f.b, 0);
+                            volWeight = store_vol_light_sample(vs, slot, ed.light, dot(shD, is.n) > 0 ? mOut : mIn);
+                        } else {
+                            const Spec c = direct_light_folded(ed.light);
+                            pdLight = make_float4(c.r, c.g, c.b, 0);
                         }
-                    }
-                    V3 wi2 = wi;
-                    float sPdf2 = 0;
-                    Spec fm = sp(0);
-                    if (lh.type == PG_LIGHT_AREA || lh.type == PG_LIGHT_INFINITE) {
-                        int st2;
-                        fm = ad_sample_f(ab, is.wo, wi2, uS0, uS1, sPdf2, nonSpecular, st2);
-                        fm = fm * absdot(wi2, ab.ns);
-                    }
-                    if (!is_black(fm) && sPdf2 > 0) {
-                        misCand = true;
-                        spawn_ray(is, wi2, misRo);
-                        misWi = wi2; misF = fm; misPdf = sPdf2;
-                        misLightArea = lh.area;
-                        mis_light_of(sc, lh, lightNum, is.p, is.pError, is.n, misLightPrim, misInside);
                     }
                     pdLight.w = lightSelPdf;
                     st.pdLight[pdi] = pdLight;
                     st.pdBeta[pdi] = make_float4(beta.r, beta.g, beta.b, 0.f);
+                    if (ed.mis.cand) {
+                        V3 misRo;
+                        spawn_ray(is, ed.mis.wi, misRo);
+                        const float lightPdf2 = mis_light_pdf<true>(sc, ed.mis.lightPrim, ed.mis.area, ed.mis.inside, is.p, misRo, ed.mis.wi, nLightTests);
+                        if (lightPdf2 != 0) {
+                            s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
+                            s_ray[2][1][tid] = make_float4(ed.mis.wi.x, ed.mis.wi.y, ed.mis.wi.z, __int_as_float(slot));
+                            pushMis = true;
+                            st.pdMis[pdi] = make_float4(ed.mis.f.r, ed.mis.f.g, ed.mis.f.b, ed.mis.pdf);
+                            st.pdBeta[pdi].w = power_heuristic(1, ed.mis.pdf, 1, lightPdf2);
+                            if constexpr (VOL) vs.trAcc[1][slot] = make_float4(1, 1, 1, __int_as_float(dot(ed.mis.wi, is.n) > 0 ? mOut : mIn));
+                        }
+                    }
                 }
-            }
-            int misMedium = 0;
-            if (VOL && misCand) misMedium = dot(misWi, is.n) > 0 ? mOut : mIn;
-            if (misCand) {
-                const float lightPdf2 = mis_light_pdf<true>(sc, misLightPrim, misLightArea, misInside, is.p, misRo, misWi, nLightTests);
-                if (lightPdf2 != 0) {
-                    s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
-                    s_ray[2][1][tid] = make_float4(misWi.x, misWi.y, misWi.z, __int_as_float(slot));
-                    pushMis = true;
-                    st.pdMis[pdi] = make_float4(misF.r, misF.g, misF.b, misPdf);
-                    st.pdBeta[pdi].w = power_heuristic(1, misPdf, 1, lightPdf2);
-                    if constexpr (VOL) vs.trAcc[1][slot] = make_float4(1, 1, 1, __int_as_float(misMedium));
-                }
-            }
             }
             int newFlags = phase == 1 ? (meta.w & 0xf0000) : 0;  // (phase 1 leaves the flags as they came)
             if (phase != 1) {
@@ -1827,15 +1750,9 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
                 spawn_ray(is, wi, nextO);
                 s_ray[0][0][tid] = make_float4(nextO.x, nextO.y, nextO.z, PG_INF);
                 s_ray[0][1][tid] = make_float4(wi.x, wi.y, wi.z, __int_as_float(slot));
-                nextBin = (wi.x < 0 ? 1 : 0) | (wi.y < 0 ? 2 : 0) | (wi.z < 0 ? 4 : 0);
-                pushNext = true;
+                nextBin = dir_octant(wi);
                 if constexpr (VOL) vs.medium[slot] = dot(wi, is.n) > 0 ? mOut : mIn;
-                const Spec rrBeta = beta * etaScale;
-                if (max_component(rrBeta) < rd.rr_threshold && bounces - 1 > 3) {  // (`bounces` of the reference's loop: this vertex's, before k_shade's increment)
-                    const float qq = pmax(.05f, 1 - max_component(rrBeta));
-                    if (draw1() < qq) pushNext = false;
-                    else beta = beta / (1 - qq);
-                }
+                pushNext = russian_roulette(beta, etaScale, bounces - 1, rd.rr_threshold, draw1);  // (`bounces` of the reference's loop: this vertex's, before k_shade's increment)
             }
             }
             outL = make_float4(L.r, L.g, L.b, L4.w);
@@ -1851,12 +1768,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
     if (pushNext) { qnext.o[posNext] = s_ray[0][0][tid]; qnext.d[posNext] = s_ray[0][1][tid]; }
     if (pushShadow) { qshadow.o[posShadow] = s_ray[1][0][tid]; qshadow.d[posShadow] = s_ray[1][1][tid]; }
     if (pushMis) { qmis.o[posMis] = s_ray[2][0][tid]; qmis.d[posMis] = s_ray[2][1][tid]; }
-    if (sc.rayTimes) {  // the rays leaving pi carry the path's time (the job's probe ray has it)
-        const float t = j >= 0 ? PG_QUEUE_TIMES(sc, sss.qjob)[j] : 0.f;
-        if (pushNext) PG_QUEUE_TIMES(sc, qnext)[posNext] = t;
-        if (pushShadow) PG_QUEUE_TIMES(sc, qshadow)[posShadow] = t;
-        if (pushMis) PG_QUEUE_TIMES(sc, qmis)[posMis] = t;
-    }
+    store_ray_times(sc, sss.qjob, j, outQ, outPred, outPos);  // the rays leaving pi carry the path's time (the job's probe ray has it)
     if (alive) {
         if constexpr (VOL) {  // by slot: L is there already (k_resolve_vol adds to it), beta and meta follow
             st.beta[slot] = outB; st.meta[slot] = outM;
@@ -1866,8 +1778,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
             st.pdInfo[j] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
         }
     }
-    unsigned long long nl = wave_sum(nLightTests);
-    if (lane_id() == 0 && nl) atomicAdd(lightTriTests + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE, nl);
+    flush_light_tests(lightTriTests, nLightTests);
     // "Path length" of the paths that end inside the BSSRDF branch (path.cpp:157-174: no probe hit, a black S or f, Russian roulette): the
     // reference's `bounces` is the entry vertex's, the stored count less k_shade's increment
     // (two phases: a job reports where it ends -- in phase 1 when the exit vertex did not come about, in phase 2 otherwise)

@@ -39,6 +39,16 @@ PG_DEV float hg_sample_p(float g, V3 wo, V3 &wi, float u0, float u1) {  // Henye
     wi = (v1 * (sinTheta * (float)cP) + v2 * (sinTheta * (float)sP)) + wo * cosTheta;  // SphericalDirection, geometry.h:1461-1466
     return phase_hg(cosTheta, g);
 }
+// The phase function as EstimateDirect's scattering model at a medium vertex (pg_estimate.h; integrator.cpp:135-141, :181-186): f = pdf = p(wo, wi),
+// without a cosine; a sampled direction's value and pdf are Sample_p's one number.  (k_shade's medium vertex spells the same out in place, for its
+// registers' sake; these are pinned by tests/test_device_headers_on_host.py and tests/test_gpu_device_arithmetic.py for the kernel that can call them)
+struct HgPhase { float g; };
+PG_DEV Spec scatter_f_cos(const HgPhase &m, V3 wo, V3 wi) { return sp(phase_hg(dot(wo, wi), m.g)); }
+PG_DEV float scatter_pdf(const HgPhase &m, V3 wo, V3 wi) { return phase_hg(dot(wo, wi), m.g); }
+PG_DEV Spec scatter_sample(const HgPhase &m, V3 wo, V3 &wi, float u0, float u1, float &pdf) {
+    pdf = hg_sample_p(m.g, wo, wi, u0, u1);
+    return sp(pdf);
+}
 // GeometricPrimitive::Intersect's mediumInterface (primitive.cpp:121-125): the primitive's own when it marks a transition,
 // else the ray's medium on both sides.  Media are index + 1, 0 = none.
 PG_DEV void prim_interface(const DScene &sc, int prim, int rayMedium, int &mIn, int &mOut) {

@@ -1,5 +1,6 @@
 // pg_queue.h -- what the wavefront kernels share about their SoA ray queues: block sizes, the per-block aggregated queue append
-// (block_push), the entry a thread consumes (queue_item, shade_position) and the wave-wide statistics counters.
+// (block_push) with the octant it bins by (dir_octant), the entry a thread consumes (queue_item, shade_position), the times of the rays a vertex
+// spawned (store_ray_times) and the wave-wide statistics counters (flush_light_tests, stats_*).
 //
 // Used by every kernel of pg_kernels.hip and pg_direct.h.  Device functions only: no kernel and no launcher lives in a header.
 #ifndef PG_QUEUE_H
@@ -83,6 +84,18 @@ PG_DEV int queue_item(const RayQueue &q) {
     return j < q.counts[r * PG_COUNT_STRIDE] ? r * q.regionCap + j : -1;
 }
 
+// block_push's bin of a continuation ray: the octant of its direction
+PG_DEV int dir_octant(V3 wi) { return (wi.x < 0 ? 1 : 0) | (wi.y < 0 ? 2 : 0) | (wi.z < 0 ? 4 : 0); }
+// Scenes with moving shapes / instances: the rays a vertex spawned (next, shadow, MIS: outQ[k] at pos[k] where pushed[k]) carry the interaction's time
+// = the time of the ray that found it, entry i of qsrc (interaction.h:77-95)
+PG_DEV void store_ray_times(const DScene &sc, const RayQueue &qsrc, int i, const RayQueue *outQ, const bool *pushed, const int *pos) {
+    if (!sc.rayTimes) return;
+    const float t = i >= 0 ? PG_QUEUE_TIMES(sc, qsrc)[i] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (pushed[k]) PG_QUEUE_TIMES(sc, outQ[k])[pos[k]] = t;
+}
+
 // A shading thread's POSITION in its launch's order (the index queue_item gave it, before RenderParams::order maps it to an entry; a
 // retry launch reads it back from the retry list): recomputed from the block and thread indices where it is needed, not kept in a register.
 PG_DEV int shade_position(const RenderParams &rp, const RayQueue &q) {
@@ -95,6 +108,11 @@ PG_DEV unsigned long long wave_sum(unsigned long long v) {
     return v;
 }
 
+// the wave's count of Shape::Pdf triangle tests (mis_light_pdf) to the block's shard of the counters: every lane of the block calls it
+PG_DEV void flush_light_tests(unsigned long long *shards, unsigned int n) {
+    const unsigned long long nl = wave_sum(n);
+    if (lane_id() == 0 && nl) atomicAdd(shards + (blockIdx.x & (PG_LIGHT_TEST_SHARDS - 1)) * PG_LIGHT_TEST_STRIDE, nl);
+}
 // ReportValue(pathLength, bounces) of the Li calls that end in this wave (path.cpp:186, volpath.cpp:187): every lane of the block calls it
 PG_DEV void stats_path_end(unsigned long long *shards, bool ended, int len) {
     const unsigned long long m = __ballot(ended);

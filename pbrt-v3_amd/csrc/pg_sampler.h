@@ -222,4 +222,17 @@ PG_DEV void ts_start_pixel(const DScene &sc, const PgRenderDesc &rd, TileSampler
     }
 }
 
+// Russian roulette on a path's next ray (path.cpp:176-184, volpath.cpp:178-184): whether the path survives, its beta divided by 1 - q when it does.
+// `bounces` is the reference loop's count at this vertex; a number is drawn (draw1) only when the test asks for one.
+template <class Draw>
+PG_DEV bool russian_roulette(Spec &beta, float etaScale, int bounces, float rrThreshold, Draw &&draw1) {
+    const Spec rrBeta = beta * etaScale;
+    if (max_component(rrBeta) < rrThreshold && bounces > 3) {
+        const float q = pmax(.05f, 1 - max_component(rrBeta));
+        if (draw1() < q) return false;
+        beta = beta / (1 - q);
+    }
+    return true;
+}
+
 #endif  // PG_SAMPLER_H

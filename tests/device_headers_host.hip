@@ -30,6 +30,7 @@ __host__ inline unsigned long long __brevll(unsigned long long v) { return __bui
 #include "../pbrt-v3_amd/csrc/pg_light.h"
 #include "../pbrt-v3_amd/csrc/pg_medium.h"
 #include "../pbrt-v3_amd/csrc/pg_hit.h"
+#include "scatter_probe.h"
 
 static V3 v3of(const float *p) { return mk(p[0], p[1], p[2]); }
 extern "C" {
@@ -144,4 +145,8 @@ void hostdev_camera_ray(const PgRenderDesc *rd, float fx, float fy, float lx, fl
 }
 // SeparableBSSRDFAdapter::f with the shading kernels' own FrDielectric
 float hostdev_bssrdf_adapter_f(float eta, float cosThetaI) { return bssrdf_adapter_f(eta, cosThetaI, fr_dielectric(cosThetaI, 1.f, eta)); }
+// The scattering models of EstimateDirect's set-up (pg_estimate.h) beyond the BxDF lists, and the roulette: tests/scatter_probe.h says what goes in and out
+void hostdev_adapter_bsdf(const float *in, int flags, float *out) { probe_adapter_bsdf(in, flags, out); }
+void hostdev_hg_phase(const float *in, float *out) { probe_hg_phase(in, out); }
+void hostdev_russian_roulette(const float *in, int bounces, float *out) { probe_russian_roulette(in, bounces, out); }
 }

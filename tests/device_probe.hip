@@ -15,6 +15,7 @@
 #include "../pbrt-v3_amd/csrc/pg_bxdf.h"
 #include "../pbrt-v3_amd/csrc/pg_medium.h"
 #include "libm_chunk.h"
+#include "scatter_probe.h"
 #include <vector>
 
 #define DP_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -250,6 +251,19 @@ __global__ void k_camera_ray(int n, const PgRenderDesc *rd, const float *fx, con
     float *q = out + 7 * i;
     q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = d.x; q[4] = d.y; q[5] = d.z; q[6] = tMax;
 }
+// ---- the scattering models of EstimateDirect's set-up beyond the BxDF lists, and the roulette (scatter_probe.h) -------------------------------
+__global__ void k_adapter_bsdf(int n, const float *in, const int *flags, float *out) {
+    DP_LANE();
+    probe_adapter_bsdf(in + SCATTER_ADAPTER_IN * i, flags[i], out + SCATTER_ADAPTER_OUT * i);
+}
+__global__ void k_hg_phase(int n, const float *in, float *out) {
+    DP_LANE();
+    probe_hg_phase(in + SCATTER_HG_IN * i, out + SCATTER_HG_OUT * i);
+}
+__global__ void k_russian_roulette(int n, const float *in, const int *bounces, float *out) {
+    DP_LANE();
+    probe_russian_roulette(in + SCATTER_RR_IN * i, bounces[i], out + SCATTER_RR_OUT * i);
+}
 }  // namespace
 
 #define F(k) as<float>(d[k])
@@ -396,5 +410,21 @@ int devprobe_camera_ray(int n, const PgRenderDesc *rd, const float *fx, const fl
     if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
     return run({{rd, sizeof(PgRenderDesc)}, {fx, FB(n)}, {fy, FB(n)}, {lx, FB(n)}, {ly, FB(n)}}, {{out, FB(7 * n)}},
                [&](void **d) { hipLaunchKernelGGL(k_camera_ray, blocks(n), dim3(LANES), 0, 0, n, as<PgRenderDesc>(d[0]), F(1), F(2), F(3), F(4), (float *)d[5]); });
+}
+// scatter_probe.h's three functions, one lane per input: in / out are n rows of its SCATTER_*_IN / _OUT floats
+int devprobe_adapter_bsdf(int n, const float *in, const int *flags, float *out) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{in, FB(SCATTER_ADAPTER_IN * n)}, {flags, n * sizeof(int)}}, {{out, FB(SCATTER_ADAPTER_OUT * n)}},
+               [&](void **d) { hipLaunchKernelGGL(k_adapter_bsdf, blocks(n), dim3(LANES), 0, 0, n, F(0), as<int>(d[1]), (float *)d[2]); });
+}
+int devprobe_hg_phase(int n, const float *in, float *out) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{in, FB(SCATTER_HG_IN * n)}}, {{out, FB(SCATTER_HG_OUT * n)}},
+               [&](void **d) { hipLaunchKernelGGL(k_hg_phase, blocks(n), dim3(LANES), 0, 0, n, F(0), (float *)d[1]); });
+}
+int devprobe_russian_roulette(int n, const float *in, const int *bounces, float *out) {
+    if (n <= 0) return n ? (int)hipErrorInvalidValue : 0;
+    return run({{in, FB(SCATTER_RR_IN * n)}, {bounces, n * sizeof(int)}}, {{out, FB(SCATTER_RR_OUT * n)}},
+               [&](void **d) { hipLaunchKernelGGL(k_russian_roulette, blocks(n), dim3(LANES), 0, 0, n, F(0), as<int>(d[1]), (float *)d[2]); });
 }
 }

@@ -66,6 +66,10 @@ def build_host_headers(directory):
     lib.hostdev_halton_index.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong]
     lib.hostdev_camera_ray.restype = None
     lib.hostdev_camera_ray.argtypes = [C.c_void_p] + [C.c_float] * 4 + [C.c_void_p]
+    lib.hostdev_adapter_bsdf.restype = lib.hostdev_hg_phase.restype = lib.hostdev_russian_roulette.restype = None
+    lib.hostdev_adapter_bsdf.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.hostdev_hg_phase.argtypes = [C.c_void_p, C.c_void_p]
+    lib.hostdev_russian_roulette.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return lib
 
 
@@ -494,6 +498,153 @@ def test_henyey_greenstein_equals_the_correctly_rounded_oracle(dev, oracle):
         pc = dev.hostdev_hg_sample_p(g, wo.ctypes.data, u[0], u[1], c.ctypes.data)
         assert bits([pa])[0] == bits([pc])[0] and np.array_equal(bits(a), bits(c)), (trial, g)
         assert bits([L.oracle_phase_hg(ct, g)])[0] == bits([dev.hostdev_phase_hg(ct, g)])[0]
+
+
+# ---- the scattering models EstimateDirect's set-up is written over (csrc/pg_estimate.h), beyond the BxDF lists: tests/scatter_probe.h ------------
+
+NON_SPECULAR = 31 & ~16  # PG_BSDF_ALL & ~PG_BSDF_SPECULAR
+ADAPTER_TYPE = 1 | 4     # PG_BSDF_REFLECTION | PG_BSDF_DIFFUSE
+ONE_MINUS_EPS = np.nextafter(np.float32(1), np.float32(0))
+
+
+def dot32(a, b):
+    """pg_device.h's dot(): float products summed left to right."""
+    return np.float32(np.float32(a[0] * b[0] + a[1] * b[1]) + a[2] * b[2])
+
+
+def adapter_bsdf_inputs():
+    """(rows of scatter_probe.h's 21 floats, flags), 840 each: the shading frame the axes (every second) or a random rotation; the geometric normal the
+    shading normal or tilted away from it, so that a pair can lie in one hemisphere of the one and in two of the other; eta 1, 1.33 and random ones; wo
+    with z == 0 (in the axes' frame, where that is exact) and z < 0; u0 = 0 and 1 - eps; the flags the kernels pass, BSDF_ALL, and a mask that leaves the lobe out."""
+    rng = np.random.default_rng(57)
+    rows, flags = [], []
+    for trial in range(840):
+        if trial % 2 == 0: ss, ts, ns = np.eye(3, dtype=np.float32)
+        else:
+            ns = unit(rng)
+            ss = np.cross(ns, unit(rng)); ss = (ss / np.linalg.norm(ss)).astype(np.float32)
+            ts = np.cross(ns, ss).astype(np.float32)
+        ng = ns
+        if trial % 3 != 0: ng = ns + np.float32(0.9) * unit(rng); ng = (ng / np.linalg.norm(ng)).astype(np.float32)
+        eta = np.float32([1.0, 1.33][trial % 4] if trial % 4 < 2 else 1.05 + 1.2 * rng.random())
+        wo, wi = unit(rng, flip=True if trial % 5 == 1 else None), unit(rng)
+        if trial % 10 == 0: wo[2] = 0; wo = (wo / np.linalg.norm(wo)).astype(np.float32)
+        u0 = np.float32([0.0, ONE_MINUS_EPS][trial % 6] if trial % 6 < 2 else rng.random())
+        rows.append(np.concatenate([ss, ts, ns, ng, [eta], wo, wi, [u0, np.float32(rng.random())]]).astype(np.float32))
+        flags.append(31 if trial % 7 == 0 else (16 | 1 if trial % 11 == 0 else NON_SPECULAR))
+    return np.ascontiguousarray(rows, np.float32), np.array(flags, np.int32)
+
+
+def test_adapter_bsdf_equals_the_oracles_adapter_lobe_under_bsdf_f_pdf_sample_f(dev, pkg, oracle):
+    """AdapterBsdf's ad_f / ad_pdf / ad_sample_f (BSDF::f / Pdf / Sample_f over the one SeparableBSSRDFAdapter, reflection.cpp:680-796) against the oracle's
+    adapter lobe in the local frame with BSDF's own rules around it -- nothing for wo.z == 0 or a mask without the lobe's type, f only for a pair in one
+    GEOMETRIC hemisphere, the pdf regardless of it -- and the scatter_* overloads against the expressions they replace in the kernels: the same three
+    with the non-specular mask, f times |wi . ns|."""
+    L = oracle.lib()
+    rows, flags = adapter_bsdf_inputs()
+    seen = {"wo.z == 0": 0, "wo.z < 0": 0, "other geometric hemisphere": 0, "u0 == 0": 0, "u0 == 1 - eps": 0, "eta 1": 0, "eta 1.33": 0, "sampled": 0}
+    for trial, (row, fl) in enumerate(zip(rows, flags)):
+        ss, ts, ns, ng, eta, wo, wi, u0, u1 = row[0:3], row[3:6], row[6:9], row[9:12], row[12], row[13:16], row[16:19], row[19], row[20]
+        out, plain = np.zeros(23, np.float32), np.zeros(23, np.float32)
+        dev.hostdev_adapter_bsdf(row.ctypes.data, int(fl), out.ctypes.data)
+        dev.hostdev_adapter_bsdf(row.ctypes.data, NON_SPECULAR, plain.ctypes.data)
+        lobe = pkg.abi.PgBxDF()
+        lobe.type = 100  # ORACLE_BXDF_BSSRDF_ADAPTER (oracle/pbrt_oracle.c): eta in eta_b
+        lobe.eta_b = float(eta)
+        local = lambda v: np.array([dot32(v, ss), dot32(v, ts), dot32(v, ns)], np.float32)
+        reflect = lambda w: dot32(w, ng) * dot32(wo, ng) > 0
+        wol, wil = local(wo), local(wi)
+        match = (fl & ADAPTER_TYPE) == ADAPTER_TYPE
+        a = np.zeros(4, np.float32)
+        L.oracle_lobe_f_pdf(C.addressof(lobe), wol.ctypes.data, wil.ctypes.data, a.ctypes.data)
+        want = np.zeros(12, np.float32)
+        want[8:11] = wi
+        if wol[2] != 0 and match:
+            if reflect(wi): want[0:3] = a[0:3]
+            want[3] = a[3]
+            s = np.zeros(7, np.float32)
+            L.oracle_lobe_sample_f(C.addressof(lobe), wol.ctypes.data, min(u0, ONE_MINUS_EPS), u1, s.ctypes.data)
+            if s[3] != 0:
+                v = s[4:7]
+                world = np.array([np.float32(ss[k] * v[0] + ts[k] * v[1]) + ns[k] * v[2] for k in range(3)], np.float32)
+                if reflect(world): want[4:7] = s[0:3]
+                want[7] = s[3]; want[8:11] = world; want[11] = ADAPTER_TYPE
+                seen["sampled"] += 1
+        assert np.array_equal(bits(out[:12]), bits(want)), (trial, out[:12], want)
+        cos_i, cos_s = np.abs(dot32(wi, ns)), np.abs(dot32(plain[8:11], ns))
+        overloads = np.concatenate([plain[0:3] * cos_i, plain[3:4], plain[4:7] * cos_s, plain[7:8], plain[8:11]]).astype(np.float32)
+        assert np.array_equal(bits(out[12:]), bits(overloads)), (trial, out[12:], overloads)
+        seen["wo.z == 0"] += wol[2] == 0; seen["wo.z < 0"] += wol[2] < 0; seen["u0 == 0"] += u0 == 0; seen["u0 == 1 - eps"] += u0 == ONE_MINUS_EPS
+        seen["other geometric hemisphere"] += bool(wol[2] * wil[2] > 0 and not reflect(wi)); seen["eta 1"] += eta == 1; seen["eta 1.33"] += eta == np.float32(1.33)
+    assert all(n >= 20 for n in seen.values()), seen
+
+
+def hg_phase_inputs():
+    """Rows of scatter_probe.h's 9 floats, 3 000: henyey_greenstein_inputs()' g, wo and u with a direction wi of their own."""
+    g, wo, u, _ = henyey_greenstein_inputs()
+    rng = np.random.default_rng(43)
+    wi = np.array([unit(rng) for _ in range(len(g))], np.float32)
+    return np.ascontiguousarray(np.concatenate([g[:, None], wo, wi, u], axis=1), np.float32)
+
+
+def test_hg_phase_overloads_equal_the_oracles_phase_function_without_a_cosine(dev, oracle):
+    """HgPhase as EstimateDirect's scattering model: f and the pdf are HenyeyGreenstein::p(wo, wi) itself in every channel (integrator.cpp:135-141: no
+    |cos| at a medium vertex), and a sampled direction's value and pdf are Sample_p's one number."""
+    L = oracle.lib()
+    for trial, row in enumerate(hg_phase_inputs()):
+        out = np.zeros(11, np.float32)
+        dev.hostdev_hg_phase(row.ctypes.data, out.ctypes.data)
+        g, wo, wi, u = row[0], row[1:4], row[4:7], row[7:9]
+        p = np.float32(L.oracle_phase_hg(dot32(wo, wi), g))
+        w = np.zeros(3, np.float32)
+        ps = np.float32(L.oracle_hg_sample_p(g, wo.ctypes.data, u.ctypes.data, w.ctypes.data))
+        want = np.concatenate([[p, p, p, p], [ps, ps, ps, ps], w]).astype(np.float32)
+        assert np.array_equal(bits(out), bits(want)), (trial, out, want)
+
+
+def russian_roulette_inputs():
+    """(rows of scatter_probe.h's 6 floats, bounces): the threshold's edge (max(beta * etaScale) equal to it and one ulp below), bounces 3 and 4 (the
+    roulette starts past 3), a draw equal to q and one ulp to either side of it, q at its floor of 0.05 and above it, etaScale lifting a path over the
+    threshold -- and 300 random ones around those values."""
+    f = np.float32
+    below = lambda x: np.nextafter(f(x), f(-np.inf))
+    above = lambda x: np.nextafter(f(x), f(np.inf))
+    q3 = f(1) - f(.3)
+    rows = [((1, .5, .25), 1, 1, .01, 4), ((below(1), .5, .25), 1, 1, .01, 4), ((below(1), .5, .25), 1, 1, .05, 4), ((below(1), .5, .25), 1, 1, below(.05), 4),
+            ((.2, .1, .3), 1, 1, q3, 4), ((.2, .1, .3), 1, 1, below(q3), 4), ((.2, .1, .3), 1, 1, above(q3), 4), ((.2, .1, .3), 1, 1, 0, 3), ((.2, .1, .3), 1, 1, 0, 4),
+            ((.2, .1, .3), 1, 1, 0, 5), ((.5, .1, .3), 2.25, 1, 0, 9), ((.4, .1, .3), 2.25, 1, 0, 9), ((.2, .6, .3), 1, .5, 0, 4), ((.2, .5, .3), 1, .5, 0, 4),
+            ((.2, below(.5), .3), 1, .5, 0, 4), ((0, 0, 0), 1, 1, below(1), 4), ((0, 0, 0), 1, 1, ONE_MINUS_EPS, 7), ((.2, .1, .3), 1, 0, 0, 4)]
+    rng = np.random.default_rng(71)
+    for trial in range(300):
+        beta = rng.random(3) * [1.2, 0.4, 0.9][trial % 3]
+        rows.append((beta, [1, 2.25, 1 / 2.25][trial % 3], [1, .5, 1][trial % 3], np.sqrt(rng.random()), int(rng.integers(2, 9))))
+    return (np.ascontiguousarray([np.concatenate([np.asarray(b, f), [e, t, u]]).astype(f) for b, e, t, u, _ in rows], f), np.array([r[4] for r in rows], np.int32))
+
+
+def test_russian_roulette_equals_the_statements_it_replaces(dev):
+    """russian_roulette against path.cpp:176-184 written out in float arithmetic: no roulette (and no number drawn) at the threshold or with bounces <= 3;
+    below it one number is drawn, a draw below q = max(.05, 1 - max) ends the path with beta as it was, a draw EQUAL to q does not, and the survivor's
+    beta is divided by 1 - q."""
+    f = np.float32
+    rows, bounces = russian_roulette_inputs()
+    kinds = {"skipped": 0, "died": 0, "survived": 0}
+    for trial, (row, b) in enumerate(zip(rows, bounces)):
+        out = np.zeros(5, f)
+        dev.hostdev_russian_roulette(row.ctypes.data, int(b), out.ctypes.data)
+        beta, eta_scale, threshold, u = row[0:3], row[3], row[4], row[5]
+        m = (beta * eta_scale).max()
+        want = np.concatenate([beta, [0, 1]]).astype(f)
+        kind = "skipped"
+        if m < threshold and b > 3:
+            q = max(f(.05), f(1) - m)
+            want[3] = 1
+            if u < q: want[4] = 0; kind = "died"
+            else: want[0:3] = beta / (f(1) - q); kind = "survived"
+        kinds[kind] += 1
+        assert np.array_equal(bits(out), bits(want)), (trial, row, b, out, want)
+    for row, b, kind in ((0, 4, "at the threshold"), (7, 3, "bounces 3"), (4, 4, "draw == q")):  # the named edges are what they say
+        assert bounces[row] == b, kind
+    assert min(kinds.values()) >= 40, kinds
 
 
 def halton_index_inputs(pkg):

@@ -45,7 +45,7 @@ def probe(gpu):
            "fresnel_moment1": [C.c_int, P, P], "invert_catmull_rom": [C.c_int, C.c_int] + [P] * 4, "bssrdf_pdf_sp": [C.c_int, P, P, C.c_longlong] + [P] * 5,
            "bssrdf_probe_segment": [C.c_int, P, P, C.c_longlong] + [P] * 7, "interpolate_trs": [C.c_int, C.c_int] + [P] * 6,
            "lobe_f_pdf": [C.c_int] + [P] * 4, "lobe_sample_f": [C.c_int] + [P] * 6, "henyey_greenstein": [C.c_int] + [P] * 7, "halton_index": [C.c_int] + [P] * 5,
-           "camera_ray": [C.c_int] + [P] * 6}
+           "camera_ray": [C.c_int] + [P] * 6, "adapter_bsdf": [C.c_int] + [P] * 3, "hg_phase": [C.c_int] + [P] * 2, "russian_roulette": [C.c_int] + [P] * 3}
     for name, argtypes in sig.items():
         fn = getattr(lib, "devprobe_" + name)
         fn.restype, fn.argtypes = C.c_int, argtypes
@@ -464,6 +464,51 @@ def case_henyey_greenstein(probe, host, pkg):
     return N, (p, wi, phase), device
 
 
+def case_adapter_bsdf(probe, host, pkg):
+    rows_in, flags = H.adapter_bsdf_inputs()
+    N = len(flags)
+    assert N == 840
+    out = np.zeros((N, 23), F32)
+    for i in range(N):
+        host.hostdev_adapter_bsdf(ptr(rows_in[i]), int(flags[i]), ptr(out[i]))
+
+    def device(n):
+        dout = np.zeros((n, 23), F32)
+        run(probe, "adapter_bsdf", n, rows(rows_in, n), rows(flags, n), dout)
+        return (dout,)
+    return N, (out,), device
+
+
+def case_hg_phase(probe, host, pkg):
+    rows_in = H.hg_phase_inputs()
+    N = len(rows_in)
+    assert N == 3000
+    out = np.zeros((N, 11), F32)
+    for i in range(N):
+        host.hostdev_hg_phase(ptr(rows_in[i]), ptr(out[i]))
+
+    def device(n):
+        dout = np.zeros((n, 11), F32)
+        run(probe, "hg_phase", n, rows(rows_in, n), dout)
+        return (dout,)
+    return N, (out,), device
+
+
+def case_russian_roulette(probe, host, pkg):
+    rows_in, bounces = H.russian_roulette_inputs()
+    N = len(bounces)
+    assert N == 318
+    out = np.zeros((N, 5), F32)
+    for i in range(N):
+        host.hostdev_russian_roulette(ptr(rows_in[i]), int(bounces[i]), ptr(out[i]))
+
+    def device(n):
+        dout = np.zeros((n, 5), F32)
+        run(probe, "russian_roulette", n, rows(rows_in, n), rows(bounces, n), dout)
+        return (dout,)
+    return N, (out,), device
+
+
 def case_halton_index(probe, host, pkg):
     per_golden = []
     for golden, scene, rd, pixels in H.halton_index_inputs(pkg):
@@ -507,7 +552,7 @@ CASES = {"tri_test": case_tri_test, "offset_ray_origin": case_offset_ray_origin,
          "fresnel_moment1": case_fresnel_moment1, "invert_catmull_rom": case_invert_catmull_rom, "bssrdf_pdf_sp": case_bssrdf_spatial("bssrdf_pdf_sp"),
          "bssrdf_probe_segment": case_bssrdf_spatial("bssrdf_probe_segment"), "interpolate_trs": case_interpolate_trs(0), "interpolate_trs_inverse": case_interpolate_trs(1)}
 CASES.update({"lobe_f_pdf": case_lobe_f_pdf, "lobe_sample_f": case_lobe_sample_f, "henyey_greenstein": case_henyey_greenstein, "halton_index": case_halton_index,
-              "camera_ray": case_camera_ray})
+              "camera_ray": case_camera_ray, "adapter_bsdf": case_adapter_bsdf, "hg_phase": case_hg_phase, "russian_roulette": case_russian_roulette})
 CASES.update({"quadric_test_" + kind: case_quadric_test(kind) for kind in ("sphere", "cylinder", "disk", "cone", "paraboloid", "hyperboloid")})
 
 
