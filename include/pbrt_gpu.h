@@ -761,6 +761,35 @@ int pg_intersect_at(PgScene *scene, int32_t n, const float *o, const float *d, c
 int pg_intersect_p_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
                       uint8_t *occluded, int mem, void *stream);
 
+/* The BSDF at one ray's closest hit, evaluated or sampled: 64 bytes, written by the device as four float4.  It is the BSDF PathIntegrator::Li holds
+ * after isect.ComputeScatteringFunctions(ray, arena, true): TransportMode::Radiance, allowMultipleLobes = true, and a ray without differentials, so every
+ * texture footprint is zero (ComputeDifferentials' early-out).  TransportMode::Importance is not built.  A BSSRDF is not reported; the BSDF of a
+ * subsurface material is.  The BxDFType bits are the reference's (reflection.h:120-128): REFLECTION 1, TRANSMISSION 2, DIFFUSE 4, GLOSSY 8, SPECULAR 16. */
+typedef struct PgScatter {
+    int32_t prim;          /* -1 = miss: every other field is 0.  Otherwise as pg_intersect_at reports it */
+    int32_t n_bxdfs;       /* BSDF::NumComponents(BSDF_ALL); 0 for a primitive without material (medium boundary) or an all-black material */
+    int32_t n_matching;    /* BSDF::NumComponents(flags) */
+    int32_t sampled_type;  /* sample query: the BxDFType bits of the sampled BxDF, 0 = no sample; f query: 0 */
+    float f[3];            /* BSDF::f(wo, wi, flags), or Sample_f's return value */
+    float pdf;             /* BSDF::Pdf(wo, wi, flags), or Sample_f's pdf (0 = no sample) */
+    float wi[3];           /* f query: wi as given; sample query: the sampled direction (world), 0 when pdf == 0 */
+    float eta;             /* BSDF::eta */
+    float shading_n[3];    /* the BSDF's ns: the shading normal AFTER Material::Bump */
+    uint32_t types;        /* PgBxDFType of BxDF i in bits 4i .. 4i+3, in Add() order */
+} PgScatter;
+
+/* Batched BSDF::f and BSDF::Pdf (reflection.cpp:680-693, :781-796) at the rays' closest hits, for an integrator whose Li stays on the host: the rays,
+ * mem and stream exactly as pg_intersect_at takes them; wi: three floats per ray, world space, used as given (not normalised, as in the reference); wo is
+ * the interaction's wo; flags: one BxDFType mask for the whole call, 0 .. 31.  isect may be NULL; otherwise isect[i] receives exactly the bytes
+ * pg_intersect_at writes for ray i (Scene::Intersect's interaction, before bump mapping), so that a vertex costs one trace.  A hit on a primitive
+ * without material (PG_MAT_NONE) gives prim >= 0 and every other field 0.  PgCounters as pg_intersect_at: closest_rays += n, one closest launch. */
+int pg_scatter_f_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                    const float *wi, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
+/* Batched BSDF::Sample_f (reflection.cpp:714-779) at the rays' closest hits: as pg_scatter_f_at, with u: two floats per ray, the Point2f of Sample_f
+ * (u[0] picks the component and is remapped inside, as in the reference). */
+int pg_scatter_sample_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                         const float *u, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
+
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);
 int pg_scene_set_option(PgScene *scene, int32_t option, int32_t value);

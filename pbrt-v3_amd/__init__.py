@@ -36,6 +36,11 @@ INTERACTION_DTYPE = np.dtype([("prim", np.int32), ("instance", np.int32), ("inst
                               ("p", np.float32, 3), ("p_error", np.float32, 3), ("n", np.float32, 3), ("wo", np.float32, 3),
                               ("shading_n", np.float32, 3), ("shading_dpdu", np.float32, 3), ("shading_dpdv", np.float32, 3), ("reserved", np.float32, 2)])
 
+# one record of pg_scatter_f_at / pg_scatter_sample_at: abi.PgScatter field for field (64 bytes)
+SCATTER_DTYPE = np.dtype([("prim", np.int32), ("n_bxdfs", np.int32), ("n_matching", np.int32), ("sampled_type", np.int32),
+                          ("f", np.float32, 3), ("pdf", np.float32), ("wi", np.float32, 3), ("eta", np.float32),
+                          ("shading_n", np.float32, 3), ("types", np.uint32)])
+
 _host = None
 _gpu = None
 
@@ -322,6 +327,37 @@ class GpuScene:
     def intersect_p_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, occluded_ptr, stream=None):
         """pg_intersect_p_at on caller-owned device buffers: n bytes written at occluded_ptr."""
         _check(gpu_lib().pg_intersect_p_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, occluded_ptr, PG_MEM_DEVICE, stream), "pg_intersect_p_at")
+
+    def _scatter(self, name, o, d, tmax, extra, per, time, flags, with_interaction):
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        extra = np.ascontiguousarray(extra, np.float32)
+        if extra.size != per * n:
+            raise ValueError(("wi holds three floats" if per == 3 else "u holds two floats") + " per ray")
+        out = np.empty(n, SCATTER_DTYPE)
+        isect = np.empty(n, INTERACTION_DTYPE) if with_interaction else None
+        _check(getattr(gpu_lib(), name)(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                        extra.ctypes.data, int(flags), None if isect is None else isect.ctypes.data, out.ctypes.data, PG_MEM_HOST, None), name)
+        return (out, isect) if with_interaction else out
+
+    def scatter_f_at(self, o, d, tmax, wi, time=None, flags=31, with_interaction=False):
+        """Batched BSDF::f and BSDF::Pdf at the rays' closest hits (pg_scatter_f_at) on host arrays: the rays as intersect_at takes them, wi three floats per
+        ray (world space, used as given), flags one BxDFType mask (0 .. 31) for all rays.  Returns the records as a structured array of SCATTER_DTYPE, or
+        -- with_interaction -- (records, what intersect_at returns for the same rays) from the one trace."""
+        return self._scatter("pg_scatter_f_at", o, d, tmax, wi, 3, time, flags, with_interaction)
+
+    def scatter_sample_at(self, o, d, tmax, u, time=None, flags=31, with_interaction=False):
+        """Batched BSDF::Sample_f at the rays' closest hits (pg_scatter_sample_at): as scatter_f_at, with u two floats per ray (Sample_f's Point2f)."""
+        return self._scatter("pg_scatter_sample_at", o, d, tmax, u, 2, time, flags, with_interaction)
+
+    def scatter_f_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, flags, isect_ptr, out_ptr, stream=None):
+        """pg_scatter_f_at on caller-owned device buffers (raw pointers, as intersect_at_device takes them): 3 n floats at wi_ptr, n records of
+        SCATTER_DTYPE written at out_ptr and, unless isect_ptr is None, n of INTERACTION_DTYPE at isect_ptr.  Nothing visits the host."""
+        _check(gpu_lib().pg_scatter_f_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, int(flags), isect_ptr, out_ptr, PG_MEM_DEVICE, stream), "pg_scatter_f_at")
+
+    def scatter_sample_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, flags, isect_ptr, out_ptr, stream=None):
+        """pg_scatter_sample_at on caller-owned device buffers: 2 n floats at u_ptr, the outputs as scatter_f_at_device's."""
+        _check(gpu_lib().pg_scatter_sample_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, int(flags), isect_ptr, out_ptr, PG_MEM_DEVICE, stream),
+               "pg_scatter_sample_at")
 
     def counters(self):
         c = PgCounters()

@@ -175,6 +175,12 @@ class PgInteraction(C.Structure):
                 ("shading_n", C.c_float * 3), ("shading_dpdu", C.c_float * 3), ("shading_dpdv", C.c_float * 3), ("reserved", C.c_float * 2)]
 
 
+class PgScatter(C.Structure):
+    _fields_ = [("prim", C.c_int32), ("n_bxdfs", C.c_int32), ("n_matching", C.c_int32), ("sampled_type", C.c_int32),
+                ("f", C.c_float * 3), ("pdf", C.c_float), ("wi", C.c_float * 3), ("eta", C.c_float),
+                ("shading_n", C.c_float * 3), ("types", C.c_uint32)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -217,6 +223,10 @@ GPU_SYMBOLS = {
                                   C.c_void_p]),
     "pg_intersect_p_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p]),
+    "pg_scatter_f_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_int, C.c_void_p]),
+    "pg_scatter_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -1280,27 +1280,31 @@ int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *des
 }
 
 // ---- batched Scene::Intersect / IntersectP -------------------------------------------
-// pg_intersect / pg_intersect_p (rays at time 0; primitive, t and barycentrics) and pg_intersect_at / pg_intersect_p_at (Ray::time; the
-// SurfaceInteraction, pg_interaction.h) are one device path, rayQuery: pack, trace, emit, account, one wait.
+// pg_intersect / pg_intersect_p (rays at time 0; primitive, t and barycentrics), pg_intersect_at / pg_intersect_p_at (Ray::time; the
+// SurfaceInteraction, pg_interaction.h) and pg_scatter_f_at / pg_scatter_sample_at (the BSDF at the closest hit, pg_scatter.h) are one device path,
+// rayQuery: pack, trace, emit, account, one wait.
 // The test-path buffers only grow: DeviceBuffer::alloc frees first, and hipFree waits for the device
 static hipError_t reserve(DeviceBuffer &b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes); }
 // The rays into the test queue ON the device (k_pack_rays), their times behind `d` in PG_QUEUE_TIMES's layout -- for every scene: a still scene's
 // k_trace does not read them, the records report them.  Host rays are staged in tIn; the caller's arrays must outlive the stream's work, which the
-// entry points wait for before they return
-static int packRays(PgScene *s, int n, const float *o, const float *d, const float *tmax, const float *time, int mem, hipStream_t stream, RayQueue &q, float *&times) {
+// entry points wait for before they return.  `extra`: a scattering query's per-ray input (extraPer floats per ray: wi or u), staged behind the rays
+static int packRays(PgScene *s, int n, const float *o, const float *d, const float *tmax, const float *time, const float *&extra, int extraPer, int mem,
+                    hipStream_t stream, RayQueue &q, float *&times) {
     const size_t N = (size_t)regionCapFor(n) * PG_REGIONS;
     HIP_TRY(reserve(s->tO, N * sizeof(float4)));
     HIP_TRY(reserve(s->tD, N * (sizeof(float4) + sizeof(float))));
     HIP_TRY(reserve(s->tCount, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));
     if (mem != PG_MEM_DEVICE) {
         const size_t n3 = 3 * (size_t)n;
-        HIP_TRY(reserve(s->tIn, (2 * n3 + 2 * (size_t)n) * sizeof(float)));
+        HIP_TRY(reserve(s->tIn, (2 * n3 + (2 + (size_t)extraPer) * (size_t)n) * sizeof(float)));
         float *in = (float *)s->tIn.p;
         HIP_TRY(hipMemcpyAsync(in, o, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(in + n3, d, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(in + 2 * n3, tmax, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
         if (time) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + n, time, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (extra) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + 2 * (size_t)n, extra, (size_t)extraPer * (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
         o = in; d = in + n3; tmax = in + 2 * n3; time = time ? in + 2 * n3 + n : nullptr;
+        if (extra) extra = in + 2 * n3 + 2 * (size_t)n;
     }
     q.o = (float4 *)s->tO.p; q.d = (float4 *)s->tD.p; q.counts = (int *)s->tCount.p; q.regionCap = regionCapFor(n);
     times = reinterpret_cast<float *>(q.d + N);
@@ -1308,17 +1312,22 @@ static int packRays(PgScene *s, int n, const float *o, const float *d, const flo
     return PG_OK;
 }
 
-// One call of the four entry points: the rays, and the caller's arrays (in `mem`) of the one kind of result it asks for
+// One call of the six entry points: the rays, and the caller's arrays (in `mem`) of the kind of result it asks for
 struct RayQuery {
     int32_t n;
     const float *o, *d, *tmax, *time;  // time == nullptr: every ray at time 0
     bool anyhit;                       // Scene::IntersectP
     bool at;                           // the _at pair: the rays' times count, a closest hit's record is the PgInteraction
     int32_t *prim; float *t, *bary;    // pg_intersect
-    PgInteraction *out;                // pg_intersect_at
+    PgInteraction *out;                // pg_intersect_at; the scattering queries' `isect` (may be nullptr there)
     uint8_t *occluded;                 // pg_intersect_p, pg_intersect_p_at
     int mem;
     void *stream;
+    // the scattering queries (at, not anyhit): scatter != nullptr, the records; scatterIn = wi (three floats per ray) or -- sample -- u (two)
+    PgScatter *scatter = nullptr;
+    const float *scatterIn = nullptr;
+    bool sample = false;
+    int32_t flags = 0;
 };
 // The statistics of one query launch, from the device's totals (tc[0] closest hit, tc[1] any hit) as read after it
 static void countQuery(PgCounters &c, bool anyhit, int n, const TraceCounters *tc, hipEvent_t a, hipEvent_t b) {
@@ -1338,11 +1347,13 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     const bool device = r.mem == PG_MEM_DEVICE;
     RayQueue q;
     float *times = nullptr;
-    if (int st = packRays(s, r.n, r.o, r.d, r.tmax, r.time, r.mem, stream, q, times)) return st;
+    const float *scatterIn = r.scatterIn;
+    if (int st = packRays(s, r.n, r.o, r.d, r.tmax, r.time, scatterIn, !r.scatter ? 0 : r.sample ? 2 : 3, r.mem, stream, q, times)) return st;
     // --- the scene and the tunables the launch sees, per entry point:
     //   pg_intersect       no instance or matrix records (primitive, t and barycentrics are all it reports); rays at time 0
     //   pg_intersect_p     rays at time 0 (an any-hit launch touches neither record)
     //   pg_intersect_at    as a frame's launch -- the hits' instances, a moving one's matrices at the ray's time -- over this call's own buffers
+    //   pg_scatter_*_at    as pg_intersect_at
     //   pg_intersect_p_at  no records; the rays' times as the scene has them
     // any hit: in the reference's visiting order, so that the counters are the reference's (tests compare them)
     DScene dsc = s->d;
@@ -1361,8 +1372,12 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     if (r.anyhit) HIP_TRY(reserve(s->tOcc, sizeof(int) * n));
     else { HIP_TRY(reserve(s->tHit, sizeof(float4) * n)); HIP_TRY(reserve(s->tT, sizeof(float) * n)); }
     // --- the results: PG_MEM_DEVICE: the kernels write the caller's arrays; otherwise into tOut, copied to the caller below
-    const size_t outBytes = r.anyhit ? n : r.at ? sizeof(PgInteraction) * n : 5 * sizeof(float) * n;  // (pg_intersect: prim, t, three barycentrics)
+    // (a scattering query: the PgScatter records first, the interactions it was asked for behind them)
+    const size_t scatterBytes = r.scatter ? sizeof(PgScatter) * n : 0, isectBytes = r.at && !r.anyhit && r.out ? sizeof(PgInteraction) * n : 0;
+    const size_t outBytes = r.anyhit ? n : r.at ? scatterBytes + isectBytes : 5 * sizeof(float) * n;  // (pg_intersect: prim, t, three barycentrics)
     if (!device) HIP_TRY(reserve(s->tOut, outBytes));
+    PgScatter *dScatter = device ? r.scatter : (PgScatter *)s->tOut.p;
+    PgInteraction *dIsect = device ? r.out : (PgInteraction *)((char *)s->tOut.p + scatterBytes);
     int32_t *dPrim = device ? r.prim : (int32_t *)s->tOut.p;
     float *dT = device ? r.t : (float *)s->tOut.p + n, *dBary = device ? r.bary : (float *)s->tOut.p + 2 * n;
     hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
@@ -1371,12 +1386,18 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     else launch_closest(dsc, cfg, q, (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
     HIP_TRY(hipEventRecord(b, stream));
     if (r.anyhit) launch_occluded_bytes((const int *)s->tOcc.p, device ? r.occluded : (uint8_t *)s->tOut.p, r.n, stream);
-    else if (r.at) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, device ? r.out : (PgInteraction *)s->tOut.p, stream);
+    else if (r.at) {
+        if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, dScatter, stream);
+        if (r.out) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dIsect, stream);
+    }
     else launch_hit_arrays((const float4 *)s->tHit.p, (const float *)s->tT.p, dPrim, dT, dBary, r.n, stream);
     HIP_TRY(hipGetLastError());
     if (!device) {
-        if (r.anyhit || r.at) HIP_TRY(hipMemcpyAsync(r.anyhit ? (void *)r.occluded : (void *)r.out, s->tOut.p, outBytes, hipMemcpyDeviceToHost, stream));
-        else {
+        if (r.anyhit) HIP_TRY(hipMemcpyAsync(r.occluded, s->tOut.p, outBytes, hipMemcpyDeviceToHost, stream));
+        else if (r.at) {
+            if (r.scatter) HIP_TRY(hipMemcpyAsync(r.scatter, dScatter, scatterBytes, hipMemcpyDeviceToHost, stream));
+            if (r.out) HIP_TRY(hipMemcpyAsync(r.out, dIsect, isectBytes, hipMemcpyDeviceToHost, stream));
+        } else {
             HIP_TRY(hipMemcpyAsync(r.prim, dPrim, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipMemcpyAsync(r.t, dT, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipMemcpyAsync(r.bary, dBary, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, stream));
@@ -1415,6 +1436,24 @@ int pg_intersect_p_at(PgScene *s, int32_t n, const float *o, const float *d, con
     if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p_at: null argument");
     if (n == 0) return PG_OK;
     return rayQuery(s, {n, o, d, tmax, time, true, true, nullptr, nullptr, nullptr, nullptr, occluded, mem, streamPtr});
+}
+// The two scattering queries: pg_intersect_at's call with the BSDF's records beside (or instead of) the interactions
+static int scatterQuery(const char *name, PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *in, bool sample,
+                        int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !in || !out))) return setError(PG_ERR_INVALID, "%s: null argument", name);
+    if (flags < 0 || flags > 31) return setError(PG_ERR_INVALID, "%s: flags %d is not a BxDFType mask (0 .. 31)", name, flags);
+    if (n == 0) return PG_OK;
+    RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
+    r.scatter = out; r.scatterIn = in; r.sample = sample; r.flags = flags;
+    return withExactFallback(s, [&]() { return rayQuery(s, r); });
+}
+int pg_scatter_f_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *wi, int32_t flags,
+                    PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    return scatterQuery("pg_scatter_f_at", s, n, o, d, tmax, time, wi, false, flags, isect, out, mem, streamPtr);
+}
+int pg_scatter_sample_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *u, int32_t flags,
+                         PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    return scatterQuery("pg_scatter_sample_at", s, n, o, d, tmax, time, u, true, flags, isect, out, mem, streamPtr);
 }
 
 

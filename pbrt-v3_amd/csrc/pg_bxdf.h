@@ -3,7 +3,7 @@
 // lbsdf_f / lbsdf_pdf / lbsdf_sample_f over a list), the one-lobe AdapterBsdf at a BSSRDF's exit point, and what EstimateDirect asks of any of
 // them (scatter_f_cos / scatter_pdf / scatter_sample; pg_medium.h has the phase function's).
 //
-// Used by k_shade, k_sss_exit (pg_kernels.hip) and k_direct (pg_direct.h).  lobe_f_pdf and lobe_sample_f are pinned on the host
+// Used by k_shade, k_sss_exit (pg_kernels.hip), k_direct (pg_direct.h) and k_scatter (pg_scatter.h).  lobe_f_pdf and lobe_sample_f are pinned on the host
 // (tests/test_device_headers_on_host.py) and on the device (tests/test_gpu_device_arithmetic.py), and so are AdapterBsdf's three functions.
 #ifndef PG_BXDF_H
 #define PG_BXDF_H

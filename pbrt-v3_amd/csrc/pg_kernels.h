@@ -490,5 +490,9 @@ void launch_interaction(const DScene &sc, RayQueue q, const float4 *hits, const 
 // prim[i], t[i] = tHit[i] and bary[3i .. 3i+2] (0 on a miss) of rays 0 .. n-1 after launch_closest(..., hits, tHit, ...)
 void launch_hit_arrays(const float4 *hits, const float *tHit, int32_t *prim, float *t, float *bary, int n, hipStream_t s);
 void launch_occluded_bytes(const int *occluded, uint8_t *out, int n, hipStream_t s);
+// ---- the scattering queries (pg_scatter.h)
+// out[i] = the BSDF at the closest hit of q's entry i after the same launch_closest: evaluated for wi = in[3i .. 3i+2] (BSDF::f, BSDF::Pdf), or -- sample --
+// sampled with u = in[2i], in[2i+1] (BSDF::Sample_f); flags: one BxDFType mask for all rays
+void launch_scatter(const DScene &sc, RayQueue q, const float4 *hits, const float *in, bool sample, int flags, PgScatter *out, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

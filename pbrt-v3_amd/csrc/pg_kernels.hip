@@ -10,6 +10,7 @@
 //   k_light_tables  SpatialLightDistribution::ComputeDistribution per voxel (lightdistrib.cpp:232-300)
 //   k_direct     DirectLightingIntegrator::Li, one (light, sample) step per launch (directlighting.cpp:62-95; pg_direct.h, included at the end)
 //   k_interaction  Scene::Intersect's SurfaceInteraction per ray, for pg_intersect_at (pg_interaction.h, included at the end)
+//   k_scatter    BSDF::f / Pdf / Sample_f at a ray's closest hit, for pg_scatter_f_at / pg_scatter_sample_at (pg_scatter.h, included at the end)
 //
 // No MFMA: there is no dense contraction on this path; traversal is a
 // latency/bandwidth-bound gather over the node and triangle arrays.
@@ -2114,3 +2115,4 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
 
 #include "pg_direct.h"  // the kernels of the DirectLightingIntegrator, built from the pieces above
 #include "pg_interaction.h"  // the kernels of the ray queries with per-ray time (pg_intersect_at / pg_intersect_p_at)
+#include "pg_scatter.h"  // the kernel of the scattering queries (pg_scatter_f_at / pg_scatter_sample_at)

@@ -1,7 +1,7 @@
 // pg_material.h -- Material::ComputeScatteringFunctions on the device: MatEval appends a material's BxDFs, textured parameters
 // evaluated at the hit (pg_texture.h), to a raw PgBxDF array (LobeOutRaw) or to k_material's packed records (LobeOutPacked).
 //
-// Used by k_shade<2>, k_material (pg_kernels.hip) and k_direct (pg_direct.h).
+// Used by k_shade<2>, k_material (pg_kernels.hip), k_direct (pg_direct.h) and k_scatter (pg_scatter.h).
 #ifndef PG_MATERIAL_H
 #define PG_MATERIAL_H
 #include "pg_bxdf.h"
