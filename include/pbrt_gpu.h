@@ -790,6 +790,45 @@ int pg_scatter_f_at(PgScene *scene, int32_t n, const float *o, const float *d, c
 int pg_scatter_sample_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
                          const float *u, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
 
+/* Light::Sample_Li(ref, u, &wi, &pdf, &vis) and vis.Unoccluded(scene) for one reference point: 64 bytes, written by the device as four float4.
+ * With pdf == 0 (no sample: shape.cpp:63-69 / diffuse.cpp:74-77, infinite.cpp:107 / :121) Li, wi, p_light and n_light are 0: the reference leaves wi
+ * and the tester unset there. */
+typedef struct PgLightSample {
+    int32_t light;       /* the index given; -1 = no sample drawn (ref.prim < 0, or the index is outside 0 .. n_lights-1): every other field 0 */
+    int32_t visibility;  /* 1 = unoccluded, 0 = occluded, -1 = not tested (pdf == 0 or Li black: EstimateDirect tests neither, integrator.cpp:128-151) */
+    float pdf;
+    float Li[3];
+    float wi[3];         /* world, as the light returns it */
+    float p_light[3];    /* VisibilityTester::P1().p (distant / infinite: the point outside the scene, distant.cpp:55-58, infinite.cpp:119-120) */
+    float n_light[3];    /* P1().n: the emitter's normal for an area light (diffuse.cpp:68-81), else 0 */
+    float reserved;      /* written as 0 */
+} PgLightSample;
+
+/* Batched Light::Sample_Li (point.cpp:43-52, spot.cpp:51-60, distant.cpp:50-60, projection.cpp:76-85, goniometric.cpp:43-52, diffuse.cpp:68-81,
+ * infinite.cpp:99-125) followed by VisibilityTester::Unoccluded (light.cpp:59-61) for the samples EstimateDirect would test, for an integrator whose
+ * Li stays on the host.  ref: the records pg_intersect_at writes, of which only prim, p, p_error, n and time are read -- prim >= 0 marks a valid point,
+ * so a caller may fill those fields itself (a medium vertex: n = 0); light[i]: the lights[] index to sample at ref[i] (the caller holds lights[] and
+ * chooses: no light-selection distribution is built); u: two floats per sample, the Point2f of Sample_Li.  shadow may be NULL; otherwise eight floats
+ * per sample, the ray of p0.SpawnRayTo(p1) (interaction.h:73-78): origin[3], tMax = 1 - ShadowEpsilon, d[3], time -- zeros where visibility is -1 --,
+ * with which a caller can march Tr itself or trace the ray again.  Occlusion is Scene::IntersectP's at ref.time, the scene seen as pg_intersect_p_at
+ * sees it: a medium boundary occludes, as in Unoccluded; VisibilityTester::Tr is not built, nor are Sample_Le / Pdf_Le.  mem and stream as
+ * pg_intersect_at takes them: with PG_MEM_DEVICE no input and no result visits the host; the call synchronises once.  PgCounters: shadow_rays += the
+ * number of samples tested (light >= 0 and visibility >= 0), one shadow launch, the any-hit statistics as pg_intersect_p_at moves them; nothing else. */
+int pg_light_sample_at(PgScene *scene, int32_t n, const PgInteraction *ref, const int32_t *light, const float *u,
+                       PgLightSample *out, float *shadow, int mem, void *stream);
+/* Batched Light::Pdf_Li(ref, wi) (light.h:92-93): ref and light as pg_light_sample_at takes them, wi three floats per sample (world space, used as
+ * given).  0 for the delta lights (point, spot, projection, goniometric, distant); Shape::Pdf(ref, wi) against the emitter's own shape alone for an
+ * area light (diffuse.cpp:83-87, shape.cpp:72-87 on the ray ref.SpawnRay(wi); spheres: Sphere::Pdf, sphere.cpp:292-305); InfiniteAreaLight::Pdf_Li
+ * (infinite.cpp:127-135).  An invalid ref or light index gives 0.  This call moves NO counter of PgCounters (the renderer's light_tri_tests included). */
+int pg_light_pdf_at(PgScene *scene, int32_t n, const PgInteraction *ref, const int32_t *light, const float *wi,
+                    float *pdf, int mem, void *stream);
+/* The emitted radiance each ray meets, three floats per ray in Le: at its closest hit isect.Le(-ray.d) (interaction.cpp:149-152, diffuse.h:56-58: the
+ * primitive's DiffuseAreaLight against the hit's normal; 0 for a primitive that does not emit), and for a ray that escapes the sum over the infinite
+ * lights, in lights[] order from 0, of Le(ray) (path.cpp:81-85, infinite.cpp:93-97).  The rays, time, mem, stream and PgCounters exactly as
+ * pg_intersect_at's; isect may be NULL, otherwise isect[i] receives exactly the bytes pg_intersect_at writes for ray i, from the same trace. */
+int pg_light_le_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                   PgInteraction *isect, float *Le, int mem, void *stream);
+
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);
 int pg_scene_set_option(PgScene *scene, int32_t option, int32_t value);

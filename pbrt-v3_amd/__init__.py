@@ -41,6 +41,10 @@ SCATTER_DTYPE = np.dtype([("prim", np.int32), ("n_bxdfs", np.int32), ("n_matchin
                           ("f", np.float32, 3), ("pdf", np.float32), ("wi", np.float32, 3), ("eta", np.float32),
                           ("shading_n", np.float32, 3), ("types", np.uint32)])
 
+# one record of pg_light_sample_at: abi.PgLightSample field for field (64 bytes)
+LIGHT_SAMPLE_DTYPE = np.dtype([("light", np.int32), ("visibility", np.int32), ("pdf", np.float32), ("Li", np.float32, 3), ("wi", np.float32, 3),
+                               ("p_light", np.float32, 3), ("n_light", np.float32, 3), ("reserved", np.float32)])
+
 _host = None
 _gpu = None
 
@@ -358,6 +362,62 @@ class GpuScene:
         """pg_scatter_sample_at on caller-owned device buffers: 2 n floats at u_ptr, the outputs as scatter_f_at_device's."""
         _check(gpu_lib().pg_scatter_sample_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, int(flags), isect_ptr, out_ptr, PG_MEM_DEVICE, stream),
                "pg_scatter_sample_at")
+
+    @staticmethod
+    def _light_inputs(ref, light, extra, per):
+        ref = np.ascontiguousarray(ref, INTERACTION_DTYPE)
+        light = np.ascontiguousarray(light, np.int32)
+        extra = np.ascontiguousarray(extra, np.float32)
+        n = ref.size
+        if light.size != n or extra.size != per * n:
+            raise ValueError("light holds one index and " + ("wi three floats" if per == 3 else "u two floats") + " per reference point")
+        return ref, light, extra, n
+
+    def light_sample_at(self, ref, light, u, with_shadow_rays=False):
+        """Batched Light::Sample_Li + VisibilityTester::Unoccluded (pg_light_sample_at) on host arrays: ref the records intersect_at returns (only prim, p,
+        p_error, n and time are read; prim >= 0 marks a valid point), light one lights[] index and u two floats per reference point.  Returns the
+        records as a structured array of LIGHT_SAMPLE_DTYPE, or -- with_shadow_rays -- (records, (n, 8) float32: origin, tMax, direction, time of
+        the tested samples' shadow rays, zeros elsewhere)."""
+        ref, light, u, n = self._light_inputs(ref, light, u, 2)
+        out = np.empty(n, LIGHT_SAMPLE_DTYPE)
+        shadow = np.empty((n, 8), np.float32) if with_shadow_rays else None
+        _check(gpu_lib().pg_light_sample_at(self._h, n, ref.ctypes.data, light.ctypes.data, u.ctypes.data, out.ctypes.data,
+                                            None if shadow is None else shadow.ctypes.data, PG_MEM_HOST, None), "pg_light_sample_at")
+        return (out, shadow) if with_shadow_rays else out
+
+    def light_pdf_at(self, ref, light, wi):
+        """Batched Light::Pdf_Li(ref, wi) (pg_light_pdf_at) on host arrays: ref and light as light_sample_at takes them, wi three floats per reference
+        point (world space, used as given).  Returns float32 (n,); moves no counter."""
+        ref, light, wi, n = self._light_inputs(ref, light, wi, 3)
+        pdf = np.empty(n, np.float32)
+        _check(gpu_lib().pg_light_pdf_at(self._h, n, ref.ctypes.data, light.ctypes.data, wi.ctypes.data, pdf.ctypes.data, PG_MEM_HOST, None), "pg_light_pdf_at")
+        return pdf
+
+    def light_le_at(self, o, d, tmax, time=None, with_interaction=False):
+        """The emitted radiance each ray meets (pg_light_le_at) on host arrays: the rays as intersect_at takes them; float32 (n, 3) -- isect.Le(-ray.d) at
+        the closest hit, the infinite lights' Le(ray) summed in light order for an escaped ray -- or, with_interaction, (Le, what intersect_at
+        returns for the same rays) from the one trace."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        le = np.empty((n, 3), np.float32)
+        isect = np.empty(n, INTERACTION_DTYPE) if with_interaction else None
+        _check(gpu_lib().pg_light_le_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                        None if isect is None else isect.ctypes.data, le.ctypes.data, PG_MEM_HOST, None), "pg_light_le_at")
+        return (le, isect) if with_interaction else le
+
+    def light_sample_at_device(self, n, ref_ptr, light_ptr, u_ptr, out_ptr, shadow_ptr=None, stream=None):
+        """pg_light_sample_at on caller-owned device buffers (raw pointers, as intersect_at_device takes them): n records of INTERACTION_DTYPE at ref_ptr,
+        n int32 at light_ptr, 2 n floats at u_ptr; n records of LIGHT_SAMPLE_DTYPE written at out_ptr and, unless shadow_ptr is None, 8 n floats at
+        shadow_ptr.  Nothing visits the host."""
+        _check(gpu_lib().pg_light_sample_at(self._h, n, ref_ptr, light_ptr, u_ptr, out_ptr, shadow_ptr, PG_MEM_DEVICE, stream), "pg_light_sample_at")
+
+    def light_pdf_at_device(self, n, ref_ptr, light_ptr, wi_ptr, pdf_ptr, stream=None):
+        """pg_light_pdf_at on caller-owned device buffers: 3 n floats at wi_ptr, n floats written at pdf_ptr."""
+        _check(gpu_lib().pg_light_pdf_at(self._h, n, ref_ptr, light_ptr, wi_ptr, pdf_ptr, PG_MEM_DEVICE, stream), "pg_light_pdf_at")
+
+    def light_le_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, isect_ptr, le_ptr, stream=None):
+        """pg_light_le_at on caller-owned device buffers: the rays as intersect_at_device takes them, 3 n floats written at le_ptr and, unless isect_ptr is
+        None, n records of INTERACTION_DTYPE at isect_ptr."""
+        _check(gpu_lib().pg_light_le_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, isect_ptr, le_ptr, PG_MEM_DEVICE, stream), "pg_light_le_at")
 
     def counters(self):
         c = PgCounters()

@@ -181,6 +181,11 @@ class PgScatter(C.Structure):
                 ("shading_n", C.c_float * 3), ("types", C.c_uint32)]
 
 
+class PgLightSample(C.Structure):
+    _fields_ = [("light", C.c_int32), ("visibility", C.c_int32), ("pdf", C.c_float), ("Li", C.c_float * 3), ("wi", C.c_float * 3),
+                ("p_light", C.c_float * 3), ("n_light", C.c_float * 3), ("reserved", C.c_float)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -227,6 +232,9 @@ GPU_SYMBOLS = {
                                   C.c_int, C.c_void_p]),
     "pg_scatter_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p]),
+    "pg_light_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_light_pdf_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_light_le_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

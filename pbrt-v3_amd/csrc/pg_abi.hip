@@ -1281,8 +1281,9 @@ int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *des
 
 // ---- batched Scene::Intersect / IntersectP -------------------------------------------
 // pg_intersect / pg_intersect_p (rays at time 0; primitive, t and barycentrics), pg_intersect_at / pg_intersect_p_at (Ray::time; the
-// SurfaceInteraction, pg_interaction.h) and pg_scatter_f_at / pg_scatter_sample_at (the BSDF at the closest hit, pg_scatter.h) are one device path,
-// rayQuery: pack, trace, emit, account, one wait.
+// SurfaceInteraction, pg_interaction.h), pg_scatter_f_at / pg_scatter_sample_at (the BSDF at the closest hit, pg_scatter.h) and pg_light_le_at (the
+// radiance the ray meets, pg_lightquery.h) are one device path, rayQuery: pack, trace, emit, account, one wait.  The two light queries that take
+// reference points instead of rays, pg_light_sample_at / pg_light_pdf_at, are lightQuery below.
 // The test-path buffers only grow: DeviceBuffer::alloc frees first, and hipFree waits for the device
 static hipError_t reserve(DeviceBuffer &b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes); }
 // The rays into the test queue ON the device (k_pack_rays), their times behind `d` in PG_QUEUE_TIMES's layout -- for every scene: a still scene's
@@ -1312,14 +1313,14 @@ static int packRays(PgScene *s, int n, const float *o, const float *d, const flo
     return PG_OK;
 }
 
-// One call of the six entry points: the rays, and the caller's arrays (in `mem`) of the kind of result it asks for
+// One call of the seven entry points: the rays, and the caller's arrays (in `mem`) of the kind of result it asks for
 struct RayQuery {
     int32_t n;
     const float *o, *d, *tmax, *time;  // time == nullptr: every ray at time 0
     bool anyhit;                       // Scene::IntersectP
     bool at;                           // the _at pair: the rays' times count, a closest hit's record is the PgInteraction
     int32_t *prim; float *t, *bary;    // pg_intersect
-    PgInteraction *out;                // pg_intersect_at; the scattering queries' `isect` (may be nullptr there)
+    PgInteraction *out;                // pg_intersect_at; the scattering queries' and pg_light_le_at's `isect` (may be nullptr there)
     uint8_t *occluded;                 // pg_intersect_p, pg_intersect_p_at
     int mem;
     void *stream;
@@ -1328,6 +1329,7 @@ struct RayQuery {
     const float *scatterIn = nullptr;
     bool sample = false;
     int32_t flags = 0;
+    float *le = nullptr;  // pg_light_le_at (at, not anyhit): three floats per ray
 };
 // The statistics of one query launch, from the device's totals (tc[0] closest hit, tc[1] any hit) as read after it
 static void countQuery(PgCounters &c, bool anyhit, int n, const TraceCounters *tc, hipEvent_t a, hipEvent_t b) {
@@ -1353,7 +1355,7 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     //   pg_intersect       no instance or matrix records (primitive, t and barycentrics are all it reports); rays at time 0
     //   pg_intersect_p     rays at time 0 (an any-hit launch touches neither record)
     //   pg_intersect_at    as a frame's launch -- the hits' instances, a moving one's matrices at the ray's time -- over this call's own buffers
-    //   pg_scatter_*_at    as pg_intersect_at
+    //   pg_scatter_*_at, pg_light_le_at  as pg_intersect_at
     //   pg_intersect_p_at  no records; the rays' times as the scene has them
     // any hit: in the reference's visiting order, so that the counters are the reference's (tests compare them)
     DScene dsc = s->d;
@@ -1372,12 +1374,14 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     if (r.anyhit) HIP_TRY(reserve(s->tOcc, sizeof(int) * n));
     else { HIP_TRY(reserve(s->tHit, sizeof(float4) * n)); HIP_TRY(reserve(s->tT, sizeof(float) * n)); }
     // --- the results: PG_MEM_DEVICE: the kernels write the caller's arrays; otherwise into tOut, copied to the caller below
-    // (a scattering query: the PgScatter records first, the interactions it was asked for behind them)
+    // (a scattering query: the PgScatter records first, the interactions it was asked for behind them; pg_light_le_at: interactions, then Le)
     const size_t scatterBytes = r.scatter ? sizeof(PgScatter) * n : 0, isectBytes = r.at && !r.anyhit && r.out ? sizeof(PgInteraction) * n : 0;
-    const size_t outBytes = r.anyhit ? n : r.at ? scatterBytes + isectBytes : 5 * sizeof(float) * n;  // (pg_intersect: prim, t, three barycentrics)
+    const size_t leBytes = r.le ? 3 * sizeof(float) * n : 0;
+    const size_t outBytes = r.anyhit ? n : r.at ? scatterBytes + isectBytes + leBytes : 5 * sizeof(float) * n;  // (pg_intersect: prim, t, three barycentrics)
     if (!device) HIP_TRY(reserve(s->tOut, outBytes));
     PgScatter *dScatter = device ? r.scatter : (PgScatter *)s->tOut.p;
     PgInteraction *dIsect = device ? r.out : (PgInteraction *)((char *)s->tOut.p + scatterBytes);
+    float *dLe = device ? r.le : (float *)((char *)s->tOut.p + scatterBytes + isectBytes);
     int32_t *dPrim = device ? r.prim : (int32_t *)s->tOut.p;
     float *dT = device ? r.t : (float *)s->tOut.p + n, *dBary = device ? r.bary : (float *)s->tOut.p + 2 * n;
     hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
@@ -1389,6 +1393,7 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     else if (r.at) {
         if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, dScatter, stream);
         if (r.out) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dIsect, stream);
+        if (r.le) launch_emitted(dsc, q, (const float4 *)s->tHit.p, dLe, stream);
     }
     else launch_hit_arrays((const float4 *)s->tHit.p, (const float *)s->tT.p, dPrim, dT, dBary, r.n, stream);
     HIP_TRY(hipGetLastError());
@@ -1397,6 +1402,7 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
         else if (r.at) {
             if (r.scatter) HIP_TRY(hipMemcpyAsync(r.scatter, dScatter, scatterBytes, hipMemcpyDeviceToHost, stream));
             if (r.out) HIP_TRY(hipMemcpyAsync(r.out, dIsect, isectBytes, hipMemcpyDeviceToHost, stream));
+            if (r.le) HIP_TRY(hipMemcpyAsync(r.le, dLe, leBytes, hipMemcpyDeviceToHost, stream));
         } else {
             HIP_TRY(hipMemcpyAsync(r.prim, dPrim, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipMemcpyAsync(r.t, dT, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
@@ -1454,6 +1460,108 @@ int pg_scatter_f_at(PgScene *s, int32_t n, const float *o, const float *d, const
 int pg_scatter_sample_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *u, int32_t flags,
                          PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
     return scatterQuery("pg_scatter_sample_at", s, n, o, d, tmax, time, u, true, flags, isect, out, mem, streamPtr);
+}
+int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *isect, float *Le, int mem,
+                   void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !Le))) return setError(PG_ERR_INVALID, "pg_light_le_at: null argument");
+    if (n == 0) return PG_OK;
+    RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
+    r.le = Le;
+    return withExactFallback(s, [&]() { return rayQuery(s, r); });
+}
+
+// ---- batched Light::Sample_Li + VisibilityTester::Unoccluded, and Light::Pdf_Li, at reference points ----
+// One call of pg_light_sample_at (out != nullptr: u, two floats per sample) or pg_light_pdf_at (pdf != nullptr: wi, three)
+struct LightQuery {
+    int32_t n;
+    const PgInteraction *ref;
+    const int32_t *light;
+    const float *in;
+    PgLightSample *out; float *shadow;  // pg_light_sample_at (shadow may be nullptr)
+    float *pdf;                         // pg_light_pdf_at
+    int mem;
+    void *stream;
+};
+// Stage, sample, trace, visibility, copy back, one wait.  The sample kernel appends the rays of the samples EstimateDirect would test to the test
+// queue; the any-hit launch sees the scene as pg_intersect_p_at's does (the rays' times as the scene has them, the reference's visiting order)
+static int lightQuery(PgScene *s, const LightQuery &r) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)r.stream;
+    const size_t n = (size_t)r.n;
+    const bool device = r.mem == PG_MEM_DEVICE, sample = r.out != nullptr;
+    const size_t inPer = sample ? 2 : 3;
+    const PgInteraction *ref = r.ref;
+    const int32_t *light = r.light;
+    const float *in = r.in;
+    if (!device) {  // the reference points, the per-sample input and the light indices, in this order (16-byte aligned records first)
+        HIP_TRY(reserve(s->tIn, n * (sizeof(PgInteraction) + (inPer + 1) * sizeof(float))));
+        char *base = (char *)s->tIn.p;
+        HIP_TRY(hipMemcpyAsync(base, r.ref, n * sizeof(PgInteraction), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(base + n * sizeof(PgInteraction), r.in, n * inPer * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(base + n * (sizeof(PgInteraction) + inPer * sizeof(float)), r.light, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        ref = (const PgInteraction *)base;
+        in = (const float *)(base + n * sizeof(PgInteraction));
+        light = (const int32_t *)(base + n * (sizeof(PgInteraction) + inPer * sizeof(float)));
+    }
+    DScene dsc = s->d;
+    dsc.hitInst = nullptr; dsc.animXf = nullptr;
+    if (!sample) {
+        if (!device) HIP_TRY(reserve(s->tOut, n * sizeof(float)));
+        float *dPdf = device ? r.pdf : (float *)s->tOut.p;
+        launch_light_pdf(dsc, ref, light, in, r.n, dPdf, stream);
+        HIP_TRY(hipGetLastError());
+        if (!device) HIP_TRY(hipMemcpyAsync(r.pdf, dPdf, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return PG_OK;
+    }
+    // the test queue, empty: k_light_sample appends to it
+    const int cap = regionCapFor(r.n);
+    const size_t N = (size_t)cap * PG_REGIONS;
+    HIP_TRY(reserve(s->tO, N * sizeof(float4)));
+    HIP_TRY(reserve(s->tD, N * (sizeof(float4) + sizeof(float))));
+    HIP_TRY(reserve(s->tCount, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));
+    HIP_TRY(reserve(s->tOcc, sizeof(int) * N));  // (answers by queue entry: the regions are not filled front to back here)
+    RayQueue q;
+    q.o = (float4 *)s->tO.p; q.d = (float4 *)s->tD.p; q.counts = (int *)s->tCount.p; q.regionCap = cap;
+    float *times = reinterpret_cast<float *>(q.d + N);
+    HIP_TRY(hipMemsetAsync(q.counts, 0, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int), stream));
+    const size_t recBytes = n * sizeof(PgLightSample), shadowBytes = r.shadow ? n * 8 * sizeof(float) : 0;
+    if (!device) HIP_TRY(reserve(s->tOut, recBytes + shadowBytes));
+    PgLightSample *dOut = device ? r.out : (PgLightSample *)s->tOut.p;
+    float *dShadow = !r.shadow ? nullptr : device ? r.shadow : (float *)((char *)s->tOut.p + recBytes);
+    launch_light_sample(dsc, ref, light, in, r.n, q, times, dOut, dShadow, stream);
+    TraceConfig cfg = s->trace;
+    cfg.anyhitFree = 0;
+    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
+    HIP_TRY(hipEventRecord(a, stream));
+    launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
+    HIP_TRY(hipEventRecord(b, stream));
+    launch_light_visibility(q, (const int *)s->tOcc.p, dOut, stream);
+    HIP_TRY(hipGetLastError());
+    if (!device) {
+        HIP_TRY(hipMemcpyAsync(r.out, dOut, recBytes, hipMemcpyDeviceToHost, stream));
+        if (r.shadow) HIP_TRY(hipMemcpyAsync(r.shadow, dShadow, shadowBytes, hipMemcpyDeviceToHost, stream));
+    }
+    TraceCounters tc[2];
+    int counts[PG_REGIONS * PG_COUNT_STRIDE];
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(counts, q.counts, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
+    int tested = 0;
+    for (int k = 0; k < PG_REGIONS; ++k) tested += counts[k * PG_COUNT_STRIDE];
+    countQuery(s->counters, true, tested, tc, a, b);
+    return PG_OK;
+}
+int pg_light_sample_at(PgScene *s, int32_t n, const PgInteraction *ref, const int32_t *light, const float *u, PgLightSample *out, float *shadow, int mem,
+                       void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!ref || !light || !u || !out))) return setError(PG_ERR_INVALID, "pg_light_sample_at: null argument");
+    if (n == 0) return PG_OK;
+    return lightQuery(s, {n, ref, light, u, out, shadow, nullptr, mem, streamPtr});
+}
+int pg_light_pdf_at(PgScene *s, int32_t n, const PgInteraction *ref, const int32_t *light, const float *wi, float *pdf, int mem, void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!ref || !light || !wi || !pdf))) return setError(PG_ERR_INVALID, "pg_light_pdf_at: null argument");
+    if (n == 0) return PG_OK;
+    return lightQuery(s, {n, ref, light, wi, nullptr, nullptr, pdf, mem, streamPtr});
 }
 
 

@@ -2,8 +2,8 @@
 // in world space (hit_isect), an emitter's L there, the shadow ray and light pdf of EstimateDirect, what textures read of the hit
 // (tex_hit_setup) and Material::Bump.
 //
-// Used by k_shade, k_material, k_through, k_sss_* (pg_kernels.hip), k_direct (pg_direct.h) and k_scatter (pg_scatter.h).  Built from all the other pieces:
-// included last.
+// Used by k_shade, k_material, k_through, k_sss_* (pg_kernels.hip), k_direct (pg_direct.h), k_scatter (pg_scatter.h) and the light queries' kernels
+// (pg_lightquery.h).  Built from all the other pieces: included last.
 #ifndef PG_HIT_H
 #define PG_HIT_H
 #include "pg_triangle.h"

@@ -494,5 +494,16 @@ void launch_occluded_bytes(const int *occluded, uint8_t *out, int n, hipStream_t
 // out[i] = the BSDF at the closest hit of q's entry i after the same launch_closest: evaluated for wi = in[3i .. 3i+2] (BSDF::f, BSDF::Pdf), or -- sample --
 // sampled with u = in[2i], in[2i+1] (BSDF::Sample_f); flags: one BxDFType mask for all rays
 void launch_scatter(const DScene &sc, RayQueue q, const float4 *hits, const float *in, bool sample, int flags, PgScatter *out, hipStream_t s);
+// ---- the light queries (pg_lightquery.h)
+// out[i] = Light::Sample_Li(ref[i], u[2i], u[2i+1]) of light[i] (and, unless null, shadow[8i ..] = the VisibilityTester's ray); the rays of the samples
+// EstimateDirect would test are appended to q (counters zeroed by the caller; times: the floats behind q.d) with i as tag, for launch_anyhit ...
+void launch_light_sample(const DScene &sc, const PgInteraction *ref, const int32_t *light, const float *u, int n, RayQueue q, float *times, PgLightSample *out,
+                         float *shadow, hipStream_t s);
+// ... whose answers (occluded[entry]) become out[tag].visibility
+void launch_light_visibility(RayQueue q, const int *occluded, PgLightSample *out, hipStream_t s);
+// pdf[i] = Light::Pdf_Li(ref[i], wi[3i .. 3i+2]) of light[i]
+void launch_light_pdf(const DScene &sc, const PgInteraction *ref, const int32_t *light, const float *wi, int n, float *pdf, hipStream_t s);
+// Le[3i .. 3i+2] = the radiance ray i of q meets after the same launch_closest: isect.Le(-ray.d) at a hit, the infinite lights' Le(ray) on a miss
+void launch_emitted(const DScene &sc, RayQueue q, const float4 *hits, float *Le, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

@@ -2,7 +2,8 @@
 // (triangles and quadrics) and infinite area lights, the hot record of the light a lane sampled (LightHot), and the light
 // distributions (light_distribution; sample_discrete stays in pg_kernels.hip).
 //
-// Used by k_shade, k_sss_exit, k_resolve*, k_light_tables* (pg_kernels.hip), k_direct (pg_direct.h) and mis_light_pdf (pg_hit.h).
+// Used by k_shade, k_sss_exit, k_resolve*, k_light_tables* (pg_kernels.hip), k_direct (pg_direct.h), mis_light_pdf (pg_hit.h) and the light queries'
+// k_light_sample / k_emitted (pg_lightquery.h).
 #ifndef PG_LIGHT_H
 #define PG_LIGHT_H
 #include "pg_device.h"
