@@ -6,8 +6,8 @@
 //   k_trace      BVHAccel::Intersect / IntersectP + Triangle::Intersect[P]  (pg_traverse.hip)
 //   k_shade      PathIntegrator::Li loop body + EstimateDirect set-up      (path.cpp:81-187, integrator.cpp:85-215)
 //   k_resolve    EstimateDirect's visibility / MIS terms once rays are back (integrator.cpp:143-212)
-//   k_film       SamplerIntegrator::Render's scrub + FilmTile::AddSample    (integrator.cpp:294-320, film.h:121-161)
-//   k_light_tables  SpatialLightDistribution::ComputeDistribution per voxel (lightdistrib.cpp:232-300)
+//   k_film       SamplerIntegrator::Render's scrub + FilmTile::AddSample    (integrator.cpp:294-320, film.h:121-161; pg_film.h)
+//   k_light_tables  SpatialLightDistribution::ComputeDistribution per voxel (lightdistrib.cpp:232-300; pg_lightdistrib.h)
 //   k_direct     DirectLightingIntegrator::Li, one (light, sample) step per launch (directlighting.cpp:62-95; pg_direct.h, included at the end)
 //   k_interaction  Scene::Intersect's SurfaceInteraction per ray, for pg_intersect_at (pg_interaction.h, included at the end)
 //   k_scatter    BSDF::f / Pdf / Sample_f at a ray's closest hit, for pg_scatter_f_at / pg_scatter_sample_at (pg_scatter.h, included at the end)
@@ -19,8 +19,9 @@
 //
 // This file holds the kernels and their launch_* wrappers only.  The device functions they are built from live in headers, by subject:
 // pg_queue.h (queue append, statistics), pg_triangle.h (Tri, Isect, make_isect), pg_sampler.h, pg_camera.h, pg_bxdf.h (Bsdf, LobeBsdfT,
-// AdapterBsdf), pg_material.h (MatEval), pg_light.h, pg_medium.h, pg_hit.h (the interaction of any hit; it uses the others) and pg_estimate.h
-// (EstimateDirect's set-up over any of the scattering models; included last) -- beside pg_device.h, pg_sphere.h, pg_texture.h, pg_motion.h,
+// AdapterBsdf), pg_material.h (MatEval), pg_light.h, pg_medium.h, pg_hit.h (the interaction of any hit; it uses the others), pg_estimate.h
+// (EstimateDirect's set-up over any of the scattering models), pg_film.h (FilmTile::AddSample and the sample scrub of the three film kernels) and
+// pg_lightdistrib.h (ComputeDistribution of the two light-table kernels) -- beside pg_device.h, pg_sphere.h, pg_texture.h, pg_motion.h,
 // pg_bssrdf.h, pg_grid.h and pg_lens.h.  A helper of a single kernel (resolve_entry, through_point) stays with its kernel, and so do
 // halton_batch and sample_discrete, below the includes.
 #include "pg_device.h"
@@ -41,6 +42,8 @@
 #include "pg_medium.h"
 #include "pg_hit.h"
 #include "pg_estimate.h"
+#include "pg_film.h"
+#include "pg_lightdistrib.h"
 
 // ---- the two device functions that stay here: each holds an empty `asm volatile` register-scheduling barrier, which the emulated-device
 // build (tests/emu/build_emulated.py) drops from this file by text, and only the kernels below call them ----------------------------
@@ -1812,45 +1815,23 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film(RenderParams rp, PathState st
     const int slot0 = (tileInBatch * rp.sCount) * 256 + pix;
     if (!slot_to_pixel(rp, slot0, px, py, sn)) return;
     const int local = rp.tileLocal0 + tileInBatch;
-    const int t = rd.tile_first + local * rd.tile_step;
-    const int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    const int x0 = rd.sample_bounds[0] + tx * 16, y0 = rd.sample_bounds[1] + ty * 16;
-    const int x1 = min(x0 + 16, rd.sample_bounds[2]), y1 = min(y0 + 16, rd.sample_bounds[3]);
+    const FilmTileBounds tile = film_tile_bounds(rd, rp.nTilesX, local);
     const float frx = rd.filter_radius[0], fry = rd.filter_radius[1];
-    // FilmTile pixel bounds, film.cpp:95-106
-    const int tp0x = max((int)ceilf((float)x0 - 0.5f - frx), rd.cropped_pixel_bounds[0]);
-    const int tp0y = max((int)ceilf((float)y0 - 0.5f - fry), rd.cropped_pixel_bounds[1]);
-    const int tp1x = min((int)floorf((float)x1 - 0.5f + frx) + 1, rd.cropped_pixel_bounds[2]);
-    const int tp1y = min((int)floorf((float)y1 - 0.5f + fry) + 1, rd.cropped_pixel_bounds[3]);
     PgFilmPixel *fp = &film[(size_t)local * 256 + pix];
     float r = fp->rgb[0], g = fp->rgb[1], b = fp->rgb[2], w = fp->weight;
     for (int sIdx = 0; sIdx < rp.sCount; ++sIdx) {
         const int slot = (tileInBatch * rp.sCount + sIdx) * 256 + pix;
         const float4 L4 = st.L[slot];
         const float pFilmX = L4.w, pFilmY = st.beta[slot].w;
-        Spec L = sp3(L4.x, L4.y, L4.z);
-        // integrator.cpp:294-315
-        if (isnan(L.r) || isnan(L.g) || isnan(L.b)) L = sp(0);
-        else if ((double)lum(L) < -1e-5) L = sp(0);
-        else if (isinf(lum(L))) L = sp(0);
-        // FilmTile::AddSample, film.h:121-161; box filter => every filterTable entry is 1, sampleWeight = rayWeight = 1
-        if (lum(L) > rd.max_sample_luminance) L = L * (rd.max_sample_luminance / lum(L));
+        const Spec L = film_sample_radiance(rd, sp3(L4.x, L4.y, L4.z));
         const float dx = pFilmX - 0.5f, dy = pFilmY - 0.5f;
-        const int p0x = max((int)ceilf(dx - frx), tp0x), p0y = max((int)ceilf(dy - fry), tp0y);
-        const int p1x = min((int)floorf(dx + frx) + 1, tp1x), p1y = min((int)floorf(dy + fry) + 1, tp1y);
-        Spec c = (L * (WEIGHTED ? lens_frame(st.L)->weights[slot] : 1.f)) * 1.f;
+        int p0x, p0y, p1x, p1y;
+        film_footprint(dx, dy, frx, fry, tile, p0x, p0y, p1x, p1y);
+        const Spec c = film_contribution(L, film_sample_weight<WEIGHTED>(st, slot), 1.f);  // box filter => every filterTable entry is 1
         for (int y = p0y; y < p1y; ++y)
             for (int x = p0x; x < p1x; ++x) {
                 if (x == px && y == py) { r += c.r; g += c.g; b += c.b; w += 1.f; }
-                else {
-                    int k = atomicAdd(nStrays, 1);
-                    if (k < maxStrays) {
-                        PgStraySample s;
-                        s.px = x; s.py = y; s.src_px = px; s.src_py = py;
-                        s.rgb[0] = c.r; s.rgb[1] = c.g; s.rgb[2] = c.b; s.weight = 1.f;
-                        strays[k] = s;
-                    }
-                }
+                else film_stray_append(strays, maxStrays, nStrays, x, y, px, py, c);
             }
     }
     fp->rgb[0] = r; fp->rgb[1] = g; fp->rgb[2] = b; fp->weight = w;
@@ -1867,18 +1848,11 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, Path
     const int tileInBatch = blockIdx.x;
     const PgRenderDesc &rd = rp.rd;
     const int local = rp.tileLocal0 + tileInBatch;
-    const int t = rd.tile_first + local * rd.tile_step;
-    const int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    const int x0 = rd.sample_bounds[0] + tx * 16, y0 = rd.sample_bounds[1] + ty * 16;
-    const int x1 = min(x0 + 16, rd.sample_bounds[2]), y1 = min(y0 + 16, rd.sample_bounds[3]);
+    const FilmTileBounds tile = film_tile_bounds(rd, rp.nTilesX, local);
+    const FilmBlock blk = film_block(rd, tile);
+    const int x0 = tile.x0, y0 = tile.y0, x1 = tile.x1, y1 = tile.y1;
     const float frx = rd.filter_radius[0], fry = rd.filter_radius[1];
     const float invRx = 1 / frx, invRy = 1 / fry;  // FilmTile::invFilterRadius, film.h:113
-    // FilmTile pixel bounds, film.cpp:95-106
-    const int tp0x = max((int)ceilf((float)x0 - 0.5f - frx), rd.cropped_pixel_bounds[0]);
-    const int tp0y = max((int)ceilf((float)y0 - 0.5f - fry), rd.cropped_pixel_bounds[1]);
-    const int tp1x = min((int)floorf((float)x1 - 0.5f + frx) + 1, rd.cropped_pixel_bounds[2]);
-    const int tp1y = min((int)floorf((float)y1 - 0.5f + fry) + 1, rd.cropped_pixel_bounds[3]);
-    const int tw = 16 + rd.tile_halo[0] + rd.tile_halo[2];
     // source pixels that can reach a pixel: a sample of pixel p has pFilmDiscrete in [p - 0.5, p + 0.5] and covers the pixels
     // ceil(d - r) .. floor(d + r); one more than floor(0.5 + r) against the rounding of those sums -- which a radius <= 0.5 (the box
     // filter on this path: frames whose film positions can round onto the next pixel) cannot need: p + 0.5 + r <= p + 1 is exact
@@ -1896,8 +1870,8 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, Path
                 for (int sIdx = 0; sIdx < rp.sCount && !reaches; ++sIdx) {
                     const int slot = (tileInBatch * rp.sCount + sIdx) * 256 + pix;
                     const float dx = st.L[slot].w - 0.5f, dy = st.beta[slot].w - 0.5f;  // pFilmDiscrete
-                    const int p0x = max((int)ceilf(dx - frx), tp0x), p1x = min((int)floorf(dx + frx) + 1, tp1x);
-                    const int p0y = max((int)ceilf(dy - fry), tp0y), p1y = min((int)floorf(dy + fry) + 1, tp1y);
+                    int p0x, p0y, p1x, p1y;
+                    film_footprint(dx, dy, frx, fry, tile, p0x, p0y, p1x, p1y);
                     reaches = p0x < px || p1x > px + 1 || p0y < py || p1y > py + 1;
                 }
             s_reaches[pix] = reaches ? 1 : 0;
@@ -1905,8 +1879,8 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, Path
         __syncthreads();
     }
     for (int e = threadIdx.x; e < rd.tile_pixels; e += PG_BLOCK) {
-        const int X = x0 - rd.tile_halo[0] + e % tw, Y = y0 - rd.tile_halo[1] + e / tw;
-        if (X < tp0x || X >= tp1x || Y < tp0y || Y >= tp1y) continue;
+        const int X = blk.bx0 + e % blk.tw, Y = blk.by0 + e / blk.tw;
+        if (X < tile.tp0x || X >= tile.tp1x || Y < tile.tp0y || Y >= tile.tp1y) continue;
         float r = 0, g = 0, b = 0, w = 0;
         for (int py = max(y0, Y - reachY); py <= min(y1 - 1, Y + reachY); ++py)
             for (int px = max(x0, X - reachX); px <= min(x1 - 1, X + reachX); ++px) {
@@ -1918,20 +1892,14 @@ __global__ __launch_bounds__(PG_BLOCK) void k_film_general(RenderParams rp, Path
                     const int slot = (tileInBatch * rp.sCount + sIdx) * 256 + pix;
                     const float4 L4 = st.L[slot];
                     const float dx = L4.w - 0.5f, dy = st.beta[slot].w - 0.5f;  // pFilmDiscrete
-                    const int p0x = max((int)ceilf(dx - frx), tp0x), p1x = min((int)floorf(dx + frx) + 1, tp1x);
-                    if (X < p0x || X >= p1x) continue;
-                    const int p0y = max((int)ceilf(dy - fry), tp0y), p1y = min((int)floorf(dy + fry) + 1, tp1y);
-                    if (Y < p0y || Y >= p1y) continue;
-                    Spec L = sp3(L4.x, L4.y, L4.z);
-                    // integrator.cpp:294-315
-                    if (isnan(L.r) || isnan(L.g) || isnan(L.b)) L = sp(0);
-                    else if ((double)lum(L) < -1e-5) L = sp(0);
-                    else if (isinf(lum(L))) L = sp(0);
-                    if (lum(L) > rd.max_sample_luminance) L = L * (rd.max_sample_luminance / lum(L));
-                    const float fx = fabsf(((float)X - dx) * invRx * 16), fy = fabsf(((float)Y - dy) * invRy * 16);
-                    const int ifx = min((int)floorf(fx), 15), ify = min((int)floorf(fy), 15);
-                    const float fw = rd.filter_table[ify * 16 + ifx];
-                    const Spec c = (L * (WEIGHTED ? lens_frame(st.L)->weights[slot] : 1.f)) * fw;
+                    int p0, p1;
+                    film_footprint_axis(dx, frx, tile.tp0x, tile.tp1x, p0, p1);
+                    if (X < p0 || X >= p1) continue;
+                    film_footprint_axis(dy, fry, tile.tp0y, tile.tp1y, p0, p1);
+                    if (Y < p0 || Y >= p1) continue;
+                    const Spec L = film_sample_radiance(rd, sp3(L4.x, L4.y, L4.z));
+                    const float fw = film_filter_weight(rd, X, Y, dx, dy, invRx, invRy);
+                    const Spec c = film_contribution(L, film_sample_weight<WEIGHTED>(st, slot), fw);
                     r += c.r; g += c.g; b += c.b; w += fw;
                 }
             }
@@ -1947,58 +1915,34 @@ __global__ void k_ts_film(DScene sc, RenderParams rp, PathState st, PgFilmPixel 
     if (local >= rp.nTilesBatch || !sc.ts[local].active) return;
     const PgRenderDesc &rd = rp.rd;
     const int px = sc.ts[local].px, py = sc.ts[local].py;
-    const int t = rd.tile_first + local * rd.tile_step;
-    const int tx = t % rp.nTilesX, ty = t / rp.nTilesX;
-    const int x0 = rd.sample_bounds[0] + tx * 16, y0 = rd.sample_bounds[1] + ty * 16;
-    const int x1 = min(x0 + 16, rd.sample_bounds[2]), y1 = min(y0 + 16, rd.sample_bounds[3]);
+    const FilmTileBounds tile = film_tile_bounds(rd, rp.nTilesX, local);
     const float frx = rd.filter_radius[0], fry = rd.filter_radius[1];
-    const int tp0x = max((int)ceilf((float)x0 - 0.5f - frx), rd.cropped_pixel_bounds[0]);
-    const int tp0y = max((int)ceilf((float)y0 - 0.5f - fry), rd.cropped_pixel_bounds[1]);
-    const int tp1x = min((int)floorf((float)x1 - 0.5f + frx) + 1, rd.cropped_pixel_bounds[2]);
-    const int tp1y = min((int)floorf((float)y1 - 0.5f + fry) + 1, rd.cropped_pixel_bounds[3]);
     const float4 L4 = st.L[local];
     const float pFilmX = L4.w, pFilmY = st.beta[local].w;
-    Spec L = sp3(L4.x, L4.y, L4.z);
-    if (isnan(L.r) || isnan(L.g) || isnan(L.b)) L = sp(0);  // integrator.cpp:294-315
-    else if ((double)lum(L) < -1e-5) L = sp(0);
-    else if (isinf(lum(L))) L = sp(0);
-    if (lum(L) > rd.max_sample_luminance) L = L * (rd.max_sample_luminance / lum(L));
+    const Spec L = film_sample_radiance(rd, sp3(L4.x, L4.y, L4.z));
     const float dx = pFilmX - 0.5f, dy = pFilmY - 0.5f;
-    const int p0x = max((int)ceilf(dx - frx), tp0x), p0y = max((int)ceilf(dy - fry), tp0y);
-    const int p1x = min((int)floorf(dx + frx) + 1, tp1x), p1y = min((int)floorf(dy + fry) + 1, tp1y);
-    const float sampleWeight = WEIGHTED ? lens_frame(st.L)->weights[local] : 1.f;
+    int p0x, p0y, p1x, p1y;
+    film_footprint(dx, dy, frx, fry, tile, p0x, p0y, p1x, p1y);
+    const float sampleWeight = film_sample_weight<WEIGHTED>(st, local);
     if (rd.filter_general) {
-        const int tw = 16 + rd.tile_halo[0] + rd.tile_halo[2];
+        const FilmBlock blk = film_block(rd, tile);
         const float invRx = 1 / frx, invRy = 1 / fry;
-        for (int y = p0y; y < p1y; ++y) {
-            const float fy = fabsf(((float)y - dy) * invRy * 16);
-            const int ify = min((int)floorf(fy), 15);
+        for (int y = p0y; y < p1y; ++y)
             for (int x = p0x; x < p1x; ++x) {
-                const float fx = fabsf(((float)x - dx) * invRx * 16);
-                const int ifx = min((int)floorf(fx), 15);
-                const float fw = rd.filter_table[ify * 16 + ifx];
-                const Spec c = (L * sampleWeight) * fw;
-                PgFilmPixel *fp = &film[(size_t)local * rd.tile_pixels + (size_t)(y - (y0 - rd.tile_halo[1])) * tw + (x - (x0 - rd.tile_halo[0]))];
+                const float fw = film_filter_weight(rd, x, y, dx, dy, invRx, invRy);
+                const Spec c = film_contribution(L, sampleWeight, fw);
+                PgFilmPixel *fp = &film[(size_t)local * rd.tile_pixels + (size_t)(y - blk.by0) * blk.tw + (x - blk.bx0)];
                 fp->rgb[0] += c.r; fp->rgb[1] += c.g; fp->rgb[2] += c.b; fp->weight += fw;
             }
-        }
         return;
     }
-    const Spec c = (L * sampleWeight) * 1.f;
+    const Spec c = film_contribution(L, sampleWeight, 1.f);
     for (int y = p0y; y < p1y; ++y)
         for (int x = p0x; x < p1x; ++x) {
             if (x == px && y == py) {
-                PgFilmPixel *fp = &film[(size_t)local * 256 + (py - y0) * 16 + (px - x0)];
+                PgFilmPixel *fp = &film[(size_t)local * 256 + (py - tile.y0) * 16 + (px - tile.x0)];
                 fp->rgb[0] += c.r; fp->rgb[1] += c.g; fp->rgb[2] += c.b; fp->weight += 1.f;
-            } else {
-                const int k = atomicAdd(nStrays, 1);
-                if (k < maxStrays) {
-                    PgStraySample s;
-                    s.px = x; s.py = y; s.src_px = px; s.src_py = py;
-                    s.rgb[0] = c.r; s.rgb[1] = c.g; s.rgb[2] = c.b; s.weight = 1.f;
-                    strays[k] = s;
-                }
-            }
+            } else film_stray_append(strays, maxStrays, nStrays, x, y, px, py, c);
         }
 }
 void launch_ts_film(const DScene &sc, const RenderParams &rp, PathState st, PgFilmPixel *film, PgStraySample *strays, int maxStrays, int *nStrays,
@@ -2029,38 +1973,14 @@ __global__ __launch_bounds__(PG_BLOCK) void k_light_tables(DScene sc, float *tab
     if (v >= nDistributions) return;
     const int nl = sc.nLights;
     float *func = table + (size_t)v * (2 * nl + 2), *cdf = func + nl;
-    int pi0 = v % sc.nVoxels[0], pi1 = (v / sc.nVoxels[0]) % sc.nVoxels[1], pi2 = v / (sc.nVoxels[0] * sc.nVoxels[1]);
-    V3 p0 = mk((float)pi0 / (float)sc.nVoxels[0], (float)pi1 / (float)sc.nVoxels[1], (float)pi2 / (float)sc.nVoxels[2]);
-    V3 p1 = mk((float)(pi0 + 1) / (float)sc.nVoxels[0], (float)(pi1 + 1) / (float)sc.nVoxels[1], (float)(pi2 + 1) / (float)sc.nVoxels[2]);
-    V3 a = mk(plerp(p0.x, sc.bmin[0], sc.bmax[0]), plerp(p0.y, sc.bmin[1], sc.bmax[1]), plerp(p0.z, sc.bmin[2], sc.bmax[2]));
-    V3 b = mk(plerp(p1.x, sc.bmin[0], sc.bmax[0]), plerp(p1.y, sc.bmin[1], sc.bmax[1]), plerp(p1.z, sc.bmin[2], sc.bmax[2]));
-    V3 vmin = mk(pmin(a.x, b.x), pmin(a.y, b.y), pmin(a.z, b.z)), vmax = mk(pmax(a.x, b.x), pmax(a.y, b.y), pmax(a.z, b.z));
+    V3 vmin, vmax;
+    voxel_bounds(sc.nVoxels, sc.bmin, sc.bmax, v, vmin, vmax);
     for (int j = 0; j < nl; ++j) func[j] = 0;
-    const int nSamples = 128;
-    for (int i = 0; i < nSamples; ++i) {
-        V3 t = mk(radical_inverse_base2(i), radical_inverse(3, i), radical_inverse(5, i));
-        V3 po = mk(plerp(t.x, vmin.x, vmax.x), plerp(t.y, vmin.y, vmax.y), plerp(t.z, vmin.z, vmax.z));
-        float u0 = radical_inverse(7, i), u1 = radical_inverse(11, i);
-        for (int j = 0; j < nl; ++j) {
-            float pdf;
-            V3 wi;
-            LightSample ls;
-            Spec Li = light_sample_li<true>(sc, sc.lights[j], po, mk(0, 0, 0), mk(0, 0, 0), u0, u1, wi, pdf, ls);  // Interaction(po, Normal3f(), Vector3f(), ...)
-            if (pdf > 0) func[j] += lum(Li) / pdf;
-        }
+    for (int i = 0; i < PG_VOXEL_SAMPLES; ++i) {
+        const VoxelSample s = voxel_sample(vmin, vmax, i);
+        for (int j = 0; j < nl; ++j) voxel_light_contribution(sc, sc.lights[j], s, func[j]);
     }
-    float sumContrib = 0;
-    for (int j = 0; j < nl; ++j) sumContrib = sumContrib + func[j];
-    float avgContrib = sumContrib / (float)((size_t)nSamples * (size_t)nl);
-    float minContrib = (avgContrib > 0) ? (float)(.001 * (double)avgContrib) : 1.f;
-    for (int j = 0; j < nl; ++j) func[j] = pmax(func[j], minContrib);
-    // Distribution1D ctor, sampling.h:57-70
-    cdf[0] = 0;
-    for (int i = 1; i < nl + 1; ++i) cdf[i] = cdf[i - 1] + func[i - 1] / nl;
-    float funcInt = cdf[nl];
-    if (funcInt == 0) { for (int i = 1; i < nl + 1; ++i) cdf[i] = (float)i / (float)nl; }
-    else { for (int i = 1; i < nl + 1; ++i) cdf[i] /= funcInt; }
-    func[2 * nl + 1] = funcInt;
+    distribution_finish(func, cdf, nl, PG_VOXEL_SAMPLES);
 }
 // The same for a list of voxels, one BLOCK per voxel (sparse tables: few voxels, possibly thousands of lights): the lights are
 // spread over the block's threads -- func[j] is a sum over the 128 sample points in order, independent of the other lights --
@@ -2069,40 +1989,16 @@ __global__ __launch_bounds__(PG_BLOCK) void k_light_tables_sparse(DScene sc, flo
     const int v = requests[blockIdx.x];
     const int nl = sc.nLights;
     float *func = pool + (size_t)(firstSlot + (int)blockIdx.x) * (2 * nl + 2), *cdf = func + nl;
-    int pi0 = v % sc.nVoxels[0], pi1 = (v / sc.nVoxels[0]) % sc.nVoxels[1], pi2 = v / (sc.nVoxels[0] * sc.nVoxels[1]);
-    V3 p0 = mk((float)pi0 / (float)sc.nVoxels[0], (float)pi1 / (float)sc.nVoxels[1], (float)pi2 / (float)sc.nVoxels[2]);
-    V3 p1 = mk((float)(pi0 + 1) / (float)sc.nVoxels[0], (float)(pi1 + 1) / (float)sc.nVoxels[1], (float)(pi2 + 1) / (float)sc.nVoxels[2]);
-    V3 a = mk(plerp(p0.x, sc.bmin[0], sc.bmax[0]), plerp(p0.y, sc.bmin[1], sc.bmax[1]), plerp(p0.z, sc.bmin[2], sc.bmax[2]));
-    V3 b = mk(plerp(p1.x, sc.bmin[0], sc.bmax[0]), plerp(p1.y, sc.bmin[1], sc.bmax[1]), plerp(p1.z, sc.bmin[2], sc.bmax[2]));
-    V3 vmin = mk(pmin(a.x, b.x), pmin(a.y, b.y), pmin(a.z, b.z)), vmax = mk(pmax(a.x, b.x), pmax(a.y, b.y), pmax(a.z, b.z));
-    const int nSamples = 128;
+    V3 vmin, vmax;
+    voxel_bounds(sc.nVoxels, sc.bmin, sc.bmax, v, vmin, vmax);
     for (int j = threadIdx.x; j < nl; j += PG_BLOCK) {
         float f = 0;
-        for (int i = 0; i < nSamples; ++i) {
-            V3 t = mk(radical_inverse_base2(i), radical_inverse(3, i), radical_inverse(5, i));
-            V3 po = mk(plerp(t.x, vmin.x, vmax.x), plerp(t.y, vmin.y, vmax.y), plerp(t.z, vmin.z, vmax.z));
-            float u0 = radical_inverse(7, i), u1 = radical_inverse(11, i);
-            float pdf;
-            V3 wi;
-            LightSample ls;
-            Spec Li = light_sample_li<true>(sc, sc.lights[j], po, mk(0, 0, 0), mk(0, 0, 0), u0, u1, wi, pdf, ls);
-            if (pdf > 0) f += lum(Li) / pdf;
-        }
+        for (int i = 0; i < PG_VOXEL_SAMPLES; ++i) voxel_light_contribution(sc, sc.lights[j], voxel_sample(vmin, vmax, i), f);
         func[j] = f;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float sumContrib = 0;
-        for (int j = 0; j < nl; ++j) sumContrib = sumContrib + func[j];
-        float avgContrib = sumContrib / (float)((size_t)nSamples * (size_t)nl);
-        float minContrib = (avgContrib > 0) ? (float)(.001 * (double)avgContrib) : 1.f;
-        for (int j = 0; j < nl; ++j) func[j] = pmax(func[j], minContrib);
-        cdf[0] = 0;  // Distribution1D ctor, sampling.h:57-70
-        for (int i = 1; i < nl + 1; ++i) cdf[i] = cdf[i - 1] + func[i - 1] / nl;
-        float funcInt = cdf[nl];
-        if (funcInt == 0) { for (int i = 1; i < nl + 1; ++i) cdf[i] = (float)i / (float)nl; }
-        else { for (int i = 1; i < nl + 1; ++i) cdf[i] /= funcInt; }
-        func[2 * nl + 1] = funcInt;
+        distribution_finish(func, cdf, nl, PG_VOXEL_SAMPLES);
         sc.voxelSlot[v] = firstSlot + (int)blockIdx.x;  // published at the end of the launch (kernel boundary)
     }
 }

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: the device arithmetic headers of the product (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h, pg_grid.h, pg_bssrdf.h, pg_motion.h and the device library of the shading kernels: pg_queue.h ... pg_hit.h) compiled for the HOST
+// TEST INFRASTRUCTURE: the device arithmetic headers of the product (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h, pg_grid.h, pg_bssrdf.h, pg_motion.h and the device library of the kernels: pg_queue.h ... pg_hit.h, pg_film.h, pg_lightdistrib.h) compiled for the HOST
 // (hipcc --cuda-host-only), so that the very source the HIP kernels execute can be run without a GPU and compared with the oracle
 // -- tests/test_device_headers_on_host.py.  Every PG_DEV function becomes __host__ __device__ (the attribute macro is redefined
 // after the runtime header has been read), and the handful of device-only intrinsics they call get host overloads (clang overloads
@@ -30,7 +30,10 @@ __host__ inline unsigned long long __brevll(unsigned long long v) { return __bui
 #include "../pbrt-v3_amd/csrc/pg_light.h"
 #include "../pbrt-v3_amd/csrc/pg_medium.h"
 #include "../pbrt-v3_amd/csrc/pg_hit.h"
+#include "../pbrt-v3_amd/csrc/pg_film.h"
+#include "../pbrt-v3_amd/csrc/pg_lightdistrib.h"
 #include "scatter_probe.h"
+#include "film_probe.h"
 
 static V3 v3of(const float *p) { return mk(p[0], p[1], p[2]); }
 extern "C" {
@@ -149,4 +152,10 @@ float hostdev_bssrdf_adapter_f(float eta, float cosThetaI) { return bssrdf_adapt
 void hostdev_adapter_bsdf(const float *in, int flags, float *out) { probe_adapter_bsdf(in, flags, out); }
 void hostdev_hg_phase(const float *in, float *out) { probe_hg_phase(in, out); }
 void hostdev_russian_roulette(const float *in, int bounces, float *out) { probe_russian_roulette(in, bounces, out); }
+// The film kernels' AddSample pieces (pg_film.h) and the light-table kernels' ComputeDistribution pieces (pg_lightdistrib.h): tests/film_probe.h says what goes in and out
+void hostdev_film_tile(const PgRenderDesc *rd, int nTilesX, int local, const float *pFilm, int *out) { probe_film_tile(*rd, nTilesX, local, pFilm, out); }
+void hostdev_film_radiance(const PgRenderDesc *rd, const float *in, float *out) { probe_film_radiance(*rd, in, out); }
+float hostdev_film_filter_weight(const PgRenderDesc *rd, int X, int Y, const float *in) { return probe_film_filter_weight(*rd, X, Y, in); }
+void hostdev_voxel(const int *nVoxels, const float *bmin, const float *bmax, int v, int i, float *out) { probe_voxel(nVoxels, bmin, bmax, v, i, out); }
+void hostdev_distribution_finish(float *table, int nl, int nSamples) { probe_distribution_finish(table, nl, nSamples); }
 }

@@ -1,5 +1,5 @@
 """The device arithmetic the HIP kernels execute, run WITHOUT a GPU: tests/device_headers_host.hip compiles the product's device headers
-(pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h ... and the shading kernels' device library, pg_queue.h ... pg_hit.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
+(pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h ... and the kernels' device library, pg_queue.h ... pg_hit.h, pg_film.h, pg_lightdistrib.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
 file compares their functions with the oracle bit for bit -- on inputs far outside what the golden scenes contain (coordinates from
 1e-8 to 1e8, quadric radii from 1e-4 to 1e4), including exactly the ray sets of the GPU tests test_triangle_reintersect_on_device /
 test_quadric_reintersect_on_device.  That the gfx950 build of the same source returns the same bits is tests/test_gpu_device_arithmetic.py: it
@@ -70,6 +70,13 @@ def build_host_headers(directory):
     lib.hostdev_adapter_bsdf.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.hostdev_hg_phase.argtypes = [C.c_void_p, C.c_void_p]
     lib.hostdev_russian_roulette.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.hostdev_film_tile.restype = lib.hostdev_film_radiance.restype = lib.hostdev_voxel.restype = lib.hostdev_distribution_finish.restype = None
+    lib.hostdev_film_tile.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hostdev_film_radiance.argtypes = [C.c_void_p] * 3
+    lib.hostdev_film_filter_weight.restype = C.c_float
+    lib.hostdev_film_filter_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.hostdev_voxel.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]
+    lib.hostdev_distribution_finish.argtypes = [C.c_void_p, C.c_int, C.c_int]
     return lib
 
 
@@ -645,6 +652,257 @@ def test_russian_roulette_equals_the_statements_it_replaces(dev):
     for row, b, kind in ((0, 4, "at the threshold"), (7, 3, "bounces 3"), (4, 4, "draw == q")):  # the named edges are what they say
         assert bounces[row] == b, kind
     assert min(kinds.values()) >= 40, kinds
+
+
+# ---- the film kernels' AddSample (csrc/pg_film.h) and the light-table kernels' ComputeDistribution (csrc/pg_lightdistrib.h): tests/film_probe.h ----
+
+F = np.float32
+FILM_RADII = ((0.5, 0.5), (0.25, 0.5), (2, 2), (1.5, 3))
+FILM_WINDOW = (1880, 1056, 1920, 1080)  # 40 x 24 samples: three tiles across, the last 8 wide; two down, the last 8 high; its last column is pixel 1919
+
+
+def film_tile_inputs(pkg):
+    """[(PgRenderDesc, nTilesX, local tiles, pFilm)], one per filter radius with and without a crop window: the 40 x 24 sample window FILM_WINDOW; of
+    every tile the pixels of its first and last row and column and two inside; at each pixel the film positions pixel + 0 (a radius of 0.5 then
+    reaches the pixel before: the stray case), pixel + (1 - eps) (at 1919 the sum rounds to 1920.0), mixed, the centre and two random ones."""
+    sx0, sy0, sx1, sy1 = FILM_WINDOW
+    rng = np.random.default_rng(81)
+    offsets = [(F(0), F(0)), (ONE_MINUS_EPS, ONE_MINUS_EPS), (F(0), ONE_MINUS_EPS), (F(0.5), F(0.5))]
+    cases = []
+    for rx, ry in FILM_RADII:
+        for crop in (False, True):
+            rd = pkg.abi.PgRenderDesc()
+            rd.sample_bounds[:] = FILM_WINDOW
+            hx, hy = max(0, int(np.ceil(rx - 0.5))), max(0, int(np.ceil(ry - 0.5)))  # the film whose sample window this is: Film::GetSampleBounds, film.cpp:80-89
+            rd.cropped_pixel_bounds[:] = (sx0 + 5, sy0 + 3, sx1 - 7, sy1 - 5) if crop else (sx0 + hx, sy0 + hy, sx1 - hx, sy1 - hy)
+            rd.filter_radius[:] = (rx, ry)
+            rd.tile_halo[:] = (hx, hy, hx + 1, hy + 2)  # (four different numbers: the block's width and origin name three of them)
+            rd.tile_first, rd.tile_step = 0, 1
+            local, pfilm = [], []
+            for t in range(6):
+                x0, y0 = sx0 + (t % 3) * 16, sy0 + (t // 3) * 16
+                x1, y1 = min(x0 + 16, sx1), min(y0 + 16, sy1)
+                pixels = [(x0, y0), (x1 - 1, y0), (x0, y1 - 1), (x1 - 1, y1 - 1), ((x0 + x1) // 2, y0), ((x0 + x1) // 2, y1 - 1), (x0, (y0 + y1) // 2), (x1 - 1, (y0 + y1) // 2),
+                          (x0 + 3, y0 + 2), (x1 - 3, y1 - 4)]
+                for px, py in pixels:
+                    for ux, uy in offsets + [(F(rng.random()), F(rng.random())) for _ in range(2)]:
+                        local.append(t)
+                        pfilm.append((F(px) + ux, F(py) + uy))  # (float)pixel + u, sampler.cpp:46-52
+            cases.append((rd, 3, np.array(local, np.int32), np.ascontiguousarray(pfilm, F)))
+    return cases
+
+
+def film_tile_restated(rd, n_tiles_x, local, pfilm):
+    """tests/film_probe.h's 19 ints in float32 NumPy: the tile's samples (integrator.cpp:246-252), Film::GetFilmTile's pixel bounds (film.cpp:95-106), the
+    film block, and FilmTile::AddSample's raster bounds of a sample (film.h:126-132)."""
+    sb, cb, halo = list(rd.sample_bounds), list(rd.cropped_pixel_bounds), list(rd.tile_halo)
+    r = [F(rd.filter_radius[0]), F(rd.filter_radius[1])]
+    t = rd.tile_first + int(local) * rd.tile_step
+    tile = (t % n_tiles_x, t // n_tiles_x)
+    lo = [sb[k] + tile[k] * 16 for k in range(2)]
+    hi = [min(lo[k] + 16, sb[2 + k]) for k in range(2)]
+    tp0 = [max(int(np.ceil(F(F(lo[k]) - F(0.5)) - r[k])), cb[k]) for k in range(2)]
+    tp1 = [min(int(np.floor(F(F(hi[k]) - F(0.5)) + r[k])) + 1, cb[2 + k]) for k in range(2)]
+    d = [F(pfilm[k]) - F(0.5) for k in range(2)]
+    p0 = [max(int(np.ceil(d[k] - r[k])), tp0[k]) for k in range(2)]
+    p1 = [min(int(np.floor(d[k] + r[k])) + 1, tp1[k]) for k in range(2)]
+    return np.array(lo + hi + tp0 + tp1 + [16 + halo[0] + halo[2], lo[0] - halo[0], lo[1] - halo[1]] + p0 + p1 + [p0[0], p1[0], p0[1], p1[1]], np.int32)
+
+
+def test_film_tile_bounds_and_sample_footprints_equal_their_restatement(dev, pkg):
+    """film_tile_bounds, film_block, film_footprint and film_footprint_axis of pg_film.h against film.cpp:95-106 and film.h:126-132 written out in float32:
+    tiles clipped by the window's right and bottom edge, by the film and by a crop window; radii of a box filter (0.5, and 0.25 / 0.5), 2 / 2 and 1.5 / 3;
+    positions on a pixel's corner, one ulp before the next pixel, and at 1919 + (1 - eps), which IS 1920; pixels of every tile's first and last row and column."""
+    seen = {"tile clipped by the window": 0, "tile bounds clipped by the crop window": 0, "sample reaches another pixel of a box filter": 0,
+            "position rounded onto the next pixel": 0, "footprint clipped by the tile": 0, "nothing left of the footprint": 0}
+    for rd, ntx, local, pfilm in film_tile_inputs(pkg):
+        crop = rd.cropped_pixel_bounds[0] == FILM_WINDOW[0] + 5
+        for k in range(len(local)):
+            out = np.zeros(19, np.int32)
+            dev.hostdev_film_tile(C.byref(rd), ntx, int(local[k]), pfilm[k].ctypes.data, out.ctypes.data)
+            want = film_tile_restated(rd, ntx, local[k], pfilm[k])
+            assert np.array_equal(out, want), (list(rd.filter_radius), crop, k, pfilm[k], out, want)
+            x0, y0, x1, y1, tp0x, tp0y, tp1x, tp1y = out[:8]
+            p0x, p0y, p1x, p1y = out[11:15]
+            rx, ry = F(rd.filter_radius[0]), F(rd.filter_radius[1])
+            seen["tile clipped by the window"] += x1 - x0 < 16 or y1 - y0 < 16
+            seen["tile bounds clipped by the crop window"] += crop and (tp0x == rd.cropped_pixel_bounds[0] or tp1y == rd.cropped_pixel_bounds[3])
+            seen["sample reaches another pixel of a box filter"] += rx <= 0.5 and ry <= 0.5 and (p1x - p0x) * (p1y - p0y) > 1
+            seen["position rounded onto the next pixel"] += pfilm[k][0] == 1920
+            seen["footprint clipped by the tile"] += p0x == tp0x and int(np.ceil(F(pfilm[k][0] - F(0.5)) - rx)) < tp0x
+            seen["nothing left of the footprint"] += p1x <= p0x or p1y <= p0y
+    assert all(n >= 8 for n in seen.values()), seen
+
+
+def lum32(L):
+    """Spectrum::y of an RGB spectrum (spectrum.h:462-465) in float32, summed left to right"""
+    with np.errstate(all="ignore"):
+        return F(F(F(0.212671) * L[0]) + F(F(0.715160) * L[1])) + F(F(0.072169) * L[2])
+
+
+FILM_L0 = np.array([0.7, 1.9, 0.3], F)  # the radiance whose luminance the clamps of film_radiance_inputs are set around
+
+
+def film_radiance_inputs(pkg):
+    """([PgRenderDesc] that differ in max_sample_luminance: +inf, the luminance of FILM_L0, one ulp below it, 10; rows of tests/film_probe.h's 5 floats; the
+    description each row goes with): every row with every description.  The rows: a NaN in each channel; grey values whose luminance lies within a few
+    ulps of -1e-5 on either side; +inf in a channel; +inf and -inf (the luminance a NaN, no channel one); FLT_MAX in every channel -- the largest
+    luminance finite channels have: the weights sum to 1, it is FLT_MAX and does not overflow --; FILM_L0, whose luminance equals the second
+    description's clamp and lies one ulp above the third's, and 100 times it; 60 random radiances from 1e-3 to 1e3 with random weights."""
+    y0 = lum32(FILM_L0)
+    rds = []
+    for m in (F(np.inf), y0, np.nextafter(y0, F(0)), F(10)):
+        rd = pkg.abi.PgRenderDesc()
+        rd.max_sample_luminance = float(m)
+        rds.append(rd)
+    nan, inf, big = F(np.nan), F(np.inf), np.finfo(F).max
+    rows = [(nan, 1, 1), (1, nan, 1), (1, 1, nan), (inf, 0, 0), (0, inf, 1), (inf, -inf, 0), (big, big, big), tuple(FILM_L0), tuple(FILM_L0 * F(100)), (0, 0, 0), (-1, 2, -3)]
+    v = F(-1e-5)
+    for _ in range(6): v = np.nextafter(v, F(0))
+    for _ in range(13):
+        rows.append((v, v, v))
+        v = np.nextafter(v, F(-np.inf))
+    rng = np.random.default_rng(83)
+    rows = [tuple(r) + (1, 1) for r in rows] + [tuple(r) + (2.5, 0.375) for r in rows[:11]]
+    rows += [tuple(10.0 ** rng.uniform(-3, 3, 3)) + (rng.random() * 2, rng.random()) for _ in range(60)]
+    rows = np.ascontiguousarray(rows, F)
+    return rds, np.ascontiguousarray(np.repeat(rows, len(rds), axis=0)), np.tile(np.arange(len(rds), dtype=np.int32), len(rows))
+
+
+def test_film_sample_radiance_and_contribution_equal_their_restatement(dev, pkg):
+    """film_sample_radiance against integrator.cpp:294-315 (black for a NaN channel, else for a luminance below -1e-5 compared in double, else for an
+    infinite one) followed by film.h:124-125 (L *= maxSampleLuminance / L.y() above the clamp, not at it), and film_contribution against
+    film.h:158's L * sampleWeight * filterWeight, left to right -- in float32 NumPy, bit for bit."""
+    rds, rows, which = film_radiance_inputs(pkg)
+    seen = {"NaN channel": 0, "below -1e-5": 0, "negative, not below -1e-5": 0, "infinite luminance": 0, "NaN luminance kept": 0, "clamped": 0, "at the clamp": 0,
+            "one ulp above the clamp": 0, "no clamp at all": 0}
+    for k, (row, w) in enumerate(zip(rows, which)):
+        out = np.zeros(6, F)
+        dev.hostdev_film_radiance(C.byref(rds[w]), row.ctypes.data, out.ctypes.data)
+        L, max_lum = row[:3].copy(), F(rds[w].max_sample_luminance)
+        y = lum32(L)
+        if np.isnan(L).any(): L[:] = 0; seen["NaN channel"] += 1
+        elif float(y) < -1e-5: L[:] = 0; seen["below -1e-5"] += 1
+        elif np.isinf(y): L[:] = 0; seen["infinite luminance"] += 1
+        else: seen["negative, not below -1e-5"] += y < 0; seen["NaN luminance kept"] += bool(np.isnan(y))
+        y = lum32(L)
+        with np.errstate(all="ignore"):
+            if y > max_lum: L = (L * F(max_lum / y)).astype(F); seen["clamped"] += 1; seen["one ulp above the clamp"] += np.nextafter(y, F(0)) == max_lum
+            else: seen["at the clamp"] += y == max_lum; seen["no clamp at all"] += bool(np.isinf(max_lum) and y > 1e30)
+            want = np.concatenate([L, (L * row[3]).astype(F) * row[4]]).astype(F)
+        assert np.array_equal(bits(out), bits(want)), (k, row, float(max_lum), out, want)
+    assert all(n >= 1 for n in seen.values()) and seen["below -1e-5"] >= 4 and seen["negative, not below -1e-5"] >= 4 and seen["clamped"] >= 60, seen
+
+
+def film_filter_weight_inputs(pkg):
+    """(PgRenderDesc with a table of 256 different values, (X, Y) pixels, rows of tests/film_probe.h's 4 floats): for the radii 2 / 2 -- where
+    (X - d) / r * 16 is exact -- every offset k / 8, k = -16 .. 16: each bin's edge and, at k = +-16, fx = 16 itself (the min(., 15)), in x against y;
+    for 1.5 / 3, 0.5 / 0.5 and 2 / 2, 500 random positions within the radius of a pixel at coordinates up to 1919."""
+    rd = pkg.abi.PgRenderDesc()
+    rd.filter_table[:] = [float(F(1) + F(k) / F(256)) for k in range(256)]
+    rng = np.random.default_rng(85)
+    xy, rows = [], []
+    for kx in range(-16, 17):
+        for ky in (-16, -9, 0, 1, 8, 15, 16):
+            X, Y = 1900 + kx, 7 - ky
+            xy.append((X, Y)); rows.append((F(X) - F(kx) / F(8), F(Y) - F(ky) / F(8), F(1) / F(2), F(1) / F(2)))
+    for rx, ry in ((1.5, 3), (0.5, 0.5), (2, 2)):
+        for _ in range(500):
+            X, Y = int(rng.integers(0, 1920)), int(rng.integers(0, 1080))
+            xy.append((X, Y)); rows.append((F(X + rng.uniform(-rx, rx)), F(Y + rng.uniform(-ry, ry)), F(1) / F(rx), F(1) / F(ry)))
+    return rd, np.ascontiguousarray(xy, np.int32), np.ascontiguousarray(rows, F)
+
+
+def test_film_filter_weight_equals_its_restatement(dev, pkg):
+    """film_filter_weight against film.h:137-154 in float32 NumPy: |(x - pFilmDiscrete.x) * invFilterRadius.x * filterTableSize| floored, at most 15, the
+    table row from y -- offsets on every bin edge and at the radius itself, where the index is the last bin's."""
+    rd, xy, rows = film_filter_weight_inputs(pkg)
+    table = np.array(list(rd.filter_table), F)
+    assert len(set(table.tolist())) == 256
+    used, at_radius = set(), 0
+    for k, ((X, Y), row) in enumerate(zip(xy, rows)):
+        got = F(dev.hostdev_film_filter_weight(C.byref(rd), int(X), int(Y), row.ctypes.data))
+        fx, fy = np.abs((F(X) - row[0]) * row[2] * F(16)), np.abs((F(Y) - row[1]) * row[3] * F(16))
+        assert fx.dtype == F and fy.dtype == F
+        ifx, ify = min(int(np.floor(fx)), 15), min(int(np.floor(fy)), 15)
+        assert bits([got])[0] == bits([table[ify * 16 + ifx]])[0], (k, X, Y, row, got, ifx, ify)
+        used.add(ify * 16 + ifx); at_radius += fx == 16 or fy == 16
+    assert len(used) == 256 and at_radius >= 20, (len(used), at_radius)
+
+
+def pairwise32(a):
+    return a[0] if len(a) == 1 else F(pairwise32(a[:len(a) // 2]) + pairwise32(a[len(a) // 2:]))
+
+
+def distribution_finish_inputs():
+    """[lightContrib] for nl = 1, 2, 3 and 257 lights, 18 each: all zeros (avgContrib == 0: minContrib = 1); one contribution among zeros, first, last and
+    in the middle (the others are raised to .001 avgContrib); 14 random ones over twelve orders of magnitude, whose sum from left to right is not
+    the pairwise one."""
+    rng = np.random.default_rng(87)
+    cases = []
+    for nl in (1, 2, 3, 257):
+        cases.append(np.zeros(nl, F))
+        for at in (0, nl - 1, nl // 2):
+            c = np.zeros(nl, F)
+            c[at] = F(10.0 ** rng.uniform(-3, 6))
+            cases.append(c)
+        for _ in range(14):
+            cases.append((10.0 ** rng.uniform(-6, 6, nl)).astype(F))
+    return cases
+
+
+def test_distribution_finish_equals_the_oracles_tail_of_compute_distribution(dev, oracle):
+    """distribution_finish of pg_lightdistrib.h against the oracle's own tail of SpatialLightDistribution::ComputeDistribution (lightdistrib.cpp:285-299,
+    the Distribution1D constructor of sampling.h:57-70) over the same contributions: func, cdf and funcInt bit for bit."""
+    L = oracle.lib()
+    order_matters = {3: 0, 257: 0}
+    for k, contrib in enumerate(distribution_finish_inputs()):
+        nl = len(contrib)
+        a, b = np.zeros(2 * nl + 2, F), np.zeros(2 * nl + 2, F)
+        a[:nl] = b[:nl] = contrib
+        L.oracle_spatial_finish_distribution(a.ctypes.data, nl, 128)
+        dev.hostdev_distribution_finish(b.ctypes.data, nl, 128)
+        assert np.array_equal(bits(a), bits(b)), (k, nl, a, b)
+        assert a[nl] == 0 and a[2 * nl] == 1 and (a[:nl] > 0).all()
+        if not contrib.any(): assert (a[:nl] == 1).all() and a[2 * nl + 1] == 1  # minContrib = 1
+        elif (contrib == 0).any(): assert np.array_equal(a[:nl][contrib == 0], np.full((contrib == 0).sum(), F(.001 * float(F(contrib.sum() / F(128 * nl)))), F))
+        if nl in order_matters:
+            seq = F(0)
+            for c in contrib: seq = F(seq + c)
+            order_matters[nl] += seq != pairwise32(list(contrib))
+    assert order_matters[3] >= 1 and order_matters[257] >= 5, order_matters
+
+
+def voxel_inputs():
+    """[(nVoxels, bmin, bmax, voxels, sample points)]: one voxel; a 5 x 3 x 2 grid over bounds of both signs; a 64 x 33 x 7 grid over a scene that is flat in
+    y, with a bound at 1e4 -- every sample point 0 .. 127 among them, voxels at random and the grid's first and last."""
+    rng = np.random.default_rng(89)
+    cases = []
+    for nv, lo, hi in (((1, 1, 1), (-1, -1, -1), (1, 1, 1)), ((5, 3, 2), (-7.3, 0.01, -250), (12.9, 0.02, -1.5)), ((64, 33, 7), (-1e4, 2, 0), (3.7, 2, 555.5))):
+        total = nv[0] * nv[1] * nv[2]
+        v = np.concatenate([[0, total - 1], rng.integers(0, total, 254)]).astype(np.int32)
+        i = (np.arange(256) % 128).astype(np.int32)
+        cases.append((np.array(nv, np.int32), np.array(lo, F), np.array(hi, F), v, i))
+    return cases
+
+
+def test_voxel_box_and_sample_points_equal_their_restatement(dev, oracle):
+    """voxel_bounds and voxel_sample of pg_lightdistrib.h against lightdistrib.cpp:238-247 and :258-265 in float32 NumPy, with the oracle's RadicalInverse
+    of the first five bases: the voxel's box (Bounds3::Lerp of pi / nVoxels and (pi + 1) / nVoxels, the Bounds3 constructor's min / max) and
+    sample point i in it with the pair every light is sampled with."""
+    L = oracle.lib()
+    lerp = lambda t, a, b: F(F(F(1) - t) * a) + F(t * b)  # pbrt.h:417
+    for nv, lo, hi, vs, idx in voxel_inputs():
+        for v, i in zip(vs, idx):
+            out = np.zeros(11, F)
+            dev.hostdev_voxel(nv.ctypes.data, lo.ctypes.data, hi.ctypes.data, int(v), int(i), out.ctypes.data)
+            pi = (int(v) % nv[0], (int(v) // nv[0]) % nv[1], int(v) // (nv[0] * nv[1]))
+            a = [lerp(F(pi[k]) / F(nv[k]), lo[k], hi[k]) for k in range(3)]
+            b = [lerp(F(pi[k] + 1) / F(nv[k]), lo[k], hi[k]) for k in range(3)]
+            vmin, vmax = [min(a[k], b[k]) for k in range(3)], [max(a[k], b[k]) for k in range(3)]
+            u = [F(L.oracle_radical_inverse(base, int(i))) for base in range(5)]
+            want = np.array(vmin + vmax + [lerp(u[k], vmin[k], vmax[k]) for k in range(3)] + u[3:], F)
+            assert np.array_equal(bits(out), bits(want)), (nv, v, i, out, want)
 
 
 def halton_index_inputs(pkg):

@@ -11,7 +11,7 @@ tests/device_probe.hip (pbrt-v3_amd/libpg_devprobe.so, compiled with the product
   * the header functions on the inputs of tests/test_device_headers_on_host.py, and pg_motion.h's interpolate_trs, compared word for word
     with tests/device_headers_host.hip's build, at batch sizes around the wave width and at the full count -- the device library of the
     shading kernels among them: every BxDF (pg_bxdf.h), Henyey-Greenstein (pg_medium.h), the Halton sample index (pg_sampler.h) and the
-    camera ray (pg_camera.h).
+    camera ray (pg_camera.h) -- and the film kernels' AddSample (pg_film.h) and the light-table kernels' ComputeDistribution (pg_lightdistrib.h).
 
 PG_DEVPROBE_LIB names another build of the probe (to see these tests fail on one compiled with other flags)."""
 import ctypes as C
@@ -45,7 +45,9 @@ def probe(gpu):
            "fresnel_moment1": [C.c_int, P, P], "invert_catmull_rom": [C.c_int, C.c_int] + [P] * 4, "bssrdf_pdf_sp": [C.c_int, P, P, C.c_longlong] + [P] * 5,
            "bssrdf_probe_segment": [C.c_int, P, P, C.c_longlong] + [P] * 7, "interpolate_trs": [C.c_int, C.c_int] + [P] * 6,
            "lobe_f_pdf": [C.c_int] + [P] * 4, "lobe_sample_f": [C.c_int] + [P] * 6, "henyey_greenstein": [C.c_int] + [P] * 7, "halton_index": [C.c_int] + [P] * 5,
-           "camera_ray": [C.c_int] + [P] * 6, "adapter_bsdf": [C.c_int] + [P] * 3, "hg_phase": [C.c_int] + [P] * 2, "russian_roulette": [C.c_int] + [P] * 3}
+           "camera_ray": [C.c_int] + [P] * 6, "adapter_bsdf": [C.c_int] + [P] * 3, "hg_phase": [C.c_int] + [P] * 2, "russian_roulette": [C.c_int] + [P] * 3,
+           "film_tile": [C.c_int, P, C.c_int, P, P, P], "film_radiance": [C.c_int, P, C.c_int, P, P, P], "film_filter_weight": [C.c_int] + [P] * 4,
+           "voxel": [C.c_int] + [P] * 6, "distribution_finish": [C.c_int, P, C.c_int, P, P, C.c_int, P]}
     for name, argtypes in sig.items():
         fn = getattr(lib, "devprobe_" + name)
         fn.restype, fn.argtypes = C.c_int, argtypes
@@ -509,6 +511,97 @@ def case_russian_roulette(probe, host, pkg):
     return N, (out,), device
 
 
+def case_film_tile(probe, host, pkg):
+    per_frame = []
+    for rd, ntx, local, pfilm in H.film_tile_inputs(pkg):
+        N = len(local)
+        assert N == 360
+        out = np.zeros((N, 19), np.int32)
+        for i in range(N):
+            host.hostdev_film_tile(C.addressof(rd), ntx, int(local[i]), ptr(pfilm[i]), ptr(out[i]))
+
+        def device(n, rd=rd, ntx=ntx, local=local, pfilm=pfilm):
+            dout = np.zeros((n, 19), np.int32)
+            run(probe, "film_tile", n, C.addressof(rd), ntx, rows(local, n), rows(pfilm, n), dout)
+            return (dout,)
+        per_frame.append((N, (out,), device))
+    assert len(per_frame) == 8
+    return per_frame
+
+
+def case_film_radiance(probe, host, pkg):
+    rds, rows_in, which = H.film_radiance_inputs(pkg)
+    N = len(which)
+    arr = (pkg.abi.PgRenderDesc * len(rds))(*rds)
+    out = np.zeros((N, 6), F32)
+    for i in range(N):
+        host.hostdev_film_radiance(C.addressof(arr[which[i]]), ptr(rows_in[i]), ptr(out[i]))
+
+    def device(n):
+        dout = np.zeros((n, 6), F32)
+        run(probe, "film_radiance", n, C.addressof(arr), len(rds), rows(which, n), rows(rows_in, n), dout)
+        return (dout,)
+    return N, (out,), device
+
+
+def case_film_filter_weight(probe, host, pkg):
+    rd, xy, rows_in = H.film_filter_weight_inputs(pkg)
+    N = len(xy)
+    out = np.array([host.hostdev_film_filter_weight(C.addressof(rd), int(xy[i, 0]), int(xy[i, 1]), ptr(rows_in[i])) for i in range(N)], F32)
+
+    def device(n):
+        dout = np.zeros(n, F32)
+        run(probe, "film_filter_weight", n, C.addressof(rd), rows(xy, n), rows(rows_in, n), dout)
+        return (dout,)
+    return N, (out,), device
+
+
+def case_voxel(probe, host, pkg):
+    per_grid = []
+    for nv, lo, hi, v, idx in H.voxel_inputs():
+        N = len(v)
+        out = np.zeros((N, 11), F32)
+        for i in range(N):
+            host.hostdev_voxel(ptr(nv), ptr(lo), ptr(hi), int(v[i]), int(idx[i]), ptr(out[i]))
+
+        def device(n, nv=nv, lo=lo, hi=hi, v=v, idx=idx):
+            dout = np.zeros((n, 11), F32)
+            run(probe, "voxel", n, nv, lo, hi, rows(v, n), rows(idx, n), dout)
+            return (dout,)
+        per_grid.append((N, (out,), device))
+    return per_grid
+
+
+def case_distribution_finish(probe, host, pkg):
+    """Every distribution of the host test in one buffer, a lane each: the output is the buffer, so a batch of n compares the first n tables."""
+    contribs = H.distribution_finish_inputs()
+    N = len(contribs)
+    nl = np.array([len(c) for c in contribs], np.int32)
+    size = 2 * nl + 2
+    offset = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int32)
+    tables = np.zeros(int(size.sum()), F32)
+    for c, o in zip(contribs, offset):
+        tables[o:o + len(c)] = c
+    out = tables.copy()
+    for o, k in zip(offset, nl):
+        host.hostdev_distribution_finish(ptr(out[o:]), int(k), 128)
+    end = np.concatenate([offset[1:], [len(tables)]])
+    per_lane = [out[o:e] for o, e in zip(offset, end)]
+    want = np.zeros((N, int(size.max())), F32)
+    for i, t in enumerate(per_lane):
+        want[i, :len(t)] = t
+
+    def device(n):
+        dout = np.zeros(len(tables), F32)
+        run(probe, "distribution_finish", n, tables, len(tables), rows(offset, n), rows(nl, n), 128, dout)
+        got = np.zeros((n, want.shape[1]), F32)
+        for i in range(n):
+            got[i, :size[i]] = dout[offset[i]:end[i]]
+        assert not dout[end[n - 1] if n else 0:].any()  # the lanes beyond n wrote nothing
+        return (got,)
+    return N, (want,), device
+
+
 def case_halton_index(probe, host, pkg):
     per_golden = []
     for golden, scene, rd, pixels in H.halton_index_inputs(pkg):
@@ -553,6 +646,8 @@ CASES = {"tri_test": case_tri_test, "offset_ray_origin": case_offset_ray_origin,
          "bssrdf_probe_segment": case_bssrdf_spatial("bssrdf_probe_segment"), "interpolate_trs": case_interpolate_trs(0), "interpolate_trs_inverse": case_interpolate_trs(1)}
 CASES.update({"lobe_f_pdf": case_lobe_f_pdf, "lobe_sample_f": case_lobe_sample_f, "henyey_greenstein": case_henyey_greenstein, "halton_index": case_halton_index,
               "camera_ray": case_camera_ray, "adapter_bsdf": case_adapter_bsdf, "hg_phase": case_hg_phase, "russian_roulette": case_russian_roulette})
+CASES.update({"film_tile": case_film_tile, "film_radiance": case_film_radiance, "film_filter_weight": case_film_filter_weight, "voxel": case_voxel,
+              "distribution_finish": case_distribution_finish})
 CASES.update({"quadric_test_" + kind: case_quadric_test(kind) for kind in ("sphere", "cylinder", "disk", "cone", "paraboloid", "hyperboloid")})
 
 
