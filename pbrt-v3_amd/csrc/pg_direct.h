@@ -24,7 +24,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
     float4 nextO = make_float4(0, 0, 0, 0), nextD = nextO, shadowO = nextO, shadowD = nextO, misO = nextO, misD = nextO;
     int slot = 0, lightNum = -1;
     unsigned int nLightTests = 0;
-    float4 pdLight = make_float4(0, 0, 0, 1), pdMis = make_float4(0, 0, 0, 0);
+    // (lightSelectPdf and beta of 1: k_resolve's beta * (Ld / lightSelectPdf) is Ld itself here, added to the slot's accumulator)
+    float4 pdLight = pending_light_encode(sp(0), 1), pdMis = pending_mis_encode(sp(0), 0);
     float misWeight = 0;
     if (valid) {
         const float4 d4 = qin.d[i], h4 = hits[i];
@@ -112,8 +113,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
                     if (ed.light.shadow) {
                         shadow_ray_to(is.p, is.pError, is.n, ed.light.ls, slot, shadowO, shadowD);
                         pushShadow = true;
-                        const Spec c = direct_light_folded(ed.light);
-                        pdLight = make_float4(c.r, c.g, c.b, 1);
+                        pdLight = pending_light_encode(direct_light_folded(ed.light), 1);
                     }
                     if (ed.mis.cand) {  // light.Pdf_Li of the sampled direction at once: nothing else is live here
                         V3 misRo;
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
                             misO = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
                             misD = make_float4(ed.mis.wi.x, ed.mis.wi.y, ed.mis.wi.z, __int_as_float(slot));
                             pushMis = true;
-                            pdMis = make_float4(ed.mis.f.r, ed.mis.f.g, ed.mis.f.b, ed.mis.pdf);
-                            misWeight = power_heuristic(1, ed.mis.pdf, 1, lightPdf2);
+                            pdMis = pending_mis_encode(ed.mis.f, ed.mis.pdf);
+                            misWeight = pending_mis_weight(ed.mis.pdf, lightPdf2);
                         }
                     }
                 }
@@ -147,12 +147,13 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_direct(DScene sc, RenderPara
     if (pushShadow) { qshadow.o[outPos[1]] = shadowO; qshadow.d[outPos[1]] = shadowD; }
     if (pushMis) { qmis.o[outPos[2]] = misO; qmis.d[outPos[2]] = misD; }
     store_ray_times(sc, qin, i, outQ, outPred, outPos);
-    if (valid) {  // k_resolve's pending terms, by queue position; its L += beta * (Ld / pdLight.w) is Ld itself here, added to the slot's accumulator
-        st.pdInfo[i] = make_int4(outPos[1], outPos[2], lightNum, ~slot);
+    if (valid) {  // k_resolve's pending terms, by queue position; L is the slot's accumulator: ~slot, what pending_where gives a path that ended (spelled out
+                  // here: through that function, or any other, k_direct<1> takes six more VGPRs -- CHANGELOG.md)
+        st.pdInfo[i] = pending_info_encode(outPos[1], outPos[2], lightNum, ~slot);
         if (pushShadow || pushMis) {
             st.pdLight[i] = pdLight;
             st.pdMis[i] = pdMis;
-            st.pdBeta[i] = make_float4(1, 1, 1, misWeight);
+            st.pdBeta[i] = pending_beta_encode(sp(1.f), misWeight);
         }
     }
     flush_light_tests(lightTriTests, nLightTests);
@@ -165,14 +166,12 @@ void launch_direct(const DScene &sc, const RenderParams &rp, PathState st, RayQu
     else hipLaunchKernelGGL((k_direct<1>), dim3(nblk), dim3(PG_SHADE_BLOCK), 0, s, sc, rp, st, qin, hits, qnext, qshadow, qmis, lightTriTests, ds);
 }
 
-// dst[slot].rgb += src[slot].rgb / divisor, then src[slot].rgb = 0 (the .w fields stay): `L += Ld / nSamples` (integrator.cpp:80),
-// `EstimateDirect(...) / lightPdf` (integrator.cpp:104) and `L += UniformSample...Lights(...)` (directlighting.cpp:84-89, divisor 1).  A division, as the
-// reference's Spectrum::operator/(Float) is.
+// dst[slot].rgb += src[slot].rgb / divisor (direct_fold, pg_resolve.h), then src[slot].rgb = 0 (the .w fields stay)
 __global__ __launch_bounds__(PG_BLOCK) void k_direct_fold(float4 *__restrict__ src, float4 *__restrict__ dst, float divisor, int n) {
     const int slot = blockIdx.x * PG_BLOCK + threadIdx.x;
     if (slot >= n) return;
-    const float4 a = src[slot], d = dst[slot];
-    dst[slot] = make_float4(d.x + a.x / divisor, d.y + a.y / divisor, d.z + a.z / divisor, d.w);
+    const float4 a = src[slot];
+    dst[slot] = direct_fold(dst[slot], a, divisor);
     src[slot] = make_float4(0, 0, 0, a.w);
 }
 void launch_direct_fold(float4 *src, float4 *dst, float divisor, int n, hipStream_t s) {

@@ -16,6 +16,7 @@
 #include "pg_light.h"
 #include "pg_medium.h"
 #include "pg_hit.h"
+#include "pg_resolve.h"
 
 // The light half (integrator.cpp:116-162).  shadow: a shadow ray leaves -- towards ls, to be weighted by what follows; f: f * |wi . ns| (a phase function's p)
 struct DirectLight { bool shadow, isDelta; Spec f, Li; float lightPdf, scatteringPdf; V3 wi; LightSample ls; };
@@ -70,7 +71,7 @@ PG_DEV DirectSetup estimate_direct_setup(const DScene &sc, const M &m, V3 p, V3 
 }
 
 // The light sample's MIS weight as volpath keeps it beside the factors (-1: a delta light) ...
-PG_DEV float direct_light_weight(const DirectLight &d) { return d.isDelta ? -1.f : power_heuristic(1, d.lightPdf, 1, d.scatteringPdf); }
+PG_DEV float direct_light_weight(const DirectLight &d) { return vol_light_weight_of(d.isDelta, d.lightPdf, d.scatteringPdf); }
 // ... and Ld's first term with unoccluded visibility, integrator.cpp:155-160
 PG_DEV Spec direct_light_folded(const DirectLight &d) {
     const Spec f = d.f, Li = d.Li;
@@ -81,11 +82,11 @@ PG_DEV Spec direct_light_folded(const DirectLight &d) {
 // to, the weight (read from here with queue-order state, from pdInfo.w without), and the medium the ray starts in.  Returns the weight.
 PG_DEV float store_vol_light_sample(const VolState &vs, int pdi, const DirectLight &d, int medium) {
     const float w = direct_light_weight(d);
-    vs.pdLi[pdi] = make_float4(d.Li.r, d.Li.g, d.Li.b, d.lightPdf);
+    vs.pdLi[pdi] = vol_light_encode(d.Li, d.lightPdf);
     vs.p1[0][pdi] = make_float4(d.ls.p.x, d.ls.p.y, d.ls.p.z, w);
     vs.p1[1][pdi] = make_float4(d.ls.pError.x, d.ls.pError.y, d.ls.pError.z, 0);
     vs.p1[2][pdi] = make_float4(d.ls.n.x, d.ls.n.y, d.ls.n.z, 0);
-    vs.trAcc[0][pdi] = make_float4(1, 1, 1, __int_as_float(medium));
+    vs.trAcc[0][pdi] = through_acc_start(medium);
     return w;
 }
 

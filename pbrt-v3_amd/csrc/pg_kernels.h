@@ -234,7 +234,8 @@ struct PathState {
     float4 *L;      // (L.rgb, pFilm.x)
     float4 *beta;   // (beta.rgb, pFilm.y)
     int4 *meta;     // (haltonIndexLo, haltonIndexHi, etaScale bits, dimension<<20 | flags | bounces)
-    // pending direct-lighting estimate of the current bounce (EstimateDirect, integrator.cpp:108-215)
+    // pending direct-lighting estimate of the current bounce (EstimateDirect, integrator.cpp:108-215); pg_resolve.h names the fields: its encoders write
+    // these words, its decoders read them, its sums finish the estimate
     float4 *pdLight;  // (f*Li*weight/lightPdf rgb, light-selection pdf)
     float4 *pdMis;    // (f*|wi.n| rgb, scatteringPdf)
     float4 *pdBeta;   // (beta before the bounce rgb, MIS weight)

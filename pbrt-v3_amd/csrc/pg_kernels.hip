@@ -20,7 +20,8 @@
 // This file holds the kernels and their launch_* wrappers only.  The device functions they are built from live in headers, by subject:
 // pg_queue.h (queue append, statistics), pg_triangle.h (Tri, Isect, make_isect), pg_sampler.h, pg_camera.h, pg_bxdf.h (Bsdf, LobeBsdfT,
 // AdapterBsdf), pg_material.h (MatEval), pg_light.h, pg_medium.h, pg_hit.h (the interaction of any hit; it uses the others), pg_estimate.h
-// (EstimateDirect's set-up over any of the scattering models), pg_film.h (FilmTile::AddSample and the sample scrub of the three film kernels) and
+// (EstimateDirect's set-up over any of the scattering models), pg_resolve.h (the record that set-up leaves and EstimateDirect's sums once the rays are
+// back: every k_resolve*, k_direct_fold and QueueState::pend), pg_film.h (FilmTile::AddSample and the sample scrub of the three film kernels) and
 // pg_lightdistrib.h (ComputeDistribution of the two light-table kernels) -- beside pg_device.h, pg_sphere.h, pg_texture.h, pg_motion.h,
 // pg_bssrdf.h, pg_grid.h and pg_lens.h.  A helper of a single kernel (resolve_entry, through_point) stays with its kernel, and so do
 // halton_batch and sample_discrete, below the includes.
@@ -41,6 +42,7 @@
 #include "pg_light.h"
 #include "pg_medium.h"
 #include "pg_hit.h"
+#include "pg_resolve.h"
 #include "pg_estimate.h"
 #include "pg_film.h"
 #include "pg_lightdistrib.h"
@@ -664,12 +666,12 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                                 shadow_ray_to(mediumP, zero, zero, ls, pdi, s_ray[1][0][tid], s_ray[1][1][tid]);  // (transmittance rays find their terms by pdi)
                                 pushShadow = true;
                                 const bool isDelta = PG_LIGHT_IS_DELTA(light.type);
-                                volWeight = isDelta ? -1.f : power_heuristic(1, lightPdf, 1, ph);
-                                pdLight = make_float4(ph, ph, ph, 0);
-                                vs.pdLi[pdi] = make_float4(Li.r, Li.g, Li.b, lightPdf);
+                                volWeight = vol_light_weight_of(isDelta, lightPdf, ph);
+                                pdLight = pending_light_encode(sp(ph), 0);
+                                vs.pdLi[pdi] = vol_light_encode(Li, lightPdf);
                                 vs.p1[0][pdi] = make_float4(ls.p.x, ls.p.y, ls.p.z, volWeight); vs.p1[1][pdi] = make_float4(ls.pError.x, ls.pError.y, ls.pError.z, 0);
                                 vs.p1[2][pdi] = make_float4(ls.n.x, ls.n.y, ls.n.z, 0);
-                                vs.trAcc[0][pdi] = make_float4(1, 1, 1, __int_as_float(med));  // MediumInteraction::GetMedium(): the medium itself
+                                vs.trAcc[0][pdi] = through_acc_start(med);  // MediumInteraction::GetMedium(): the medium itself
                             }
                         }
                         if (light.type == PG_LIGHT_AREA || light.type == PG_LIGHT_INFINITE) {  // integrator.cpp:164-212 with the phase function
@@ -689,7 +691,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                         }
                         pdLight.w = lightSelPdf;
                         st.pdLight[pdi] = pdLight;
-                        st.pdBeta[pdi] = make_float4(beta.r, beta.g, beta.b, 0.f);
+                        st.pdBeta[pdi] = pending_beta_encode(beta, 0.f);
                     }
                 }
                 if (!phaseA) {
@@ -872,15 +874,15 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                                 // delta lights take no MIS weight (integrator.cpp:155-160)
                                 const bool isDelta = PG_LIGHT_IS_DELTA(lh.type);
                                 if constexpr (VOL) {  // Li still is to be multiplied by VisibilityTester::Tr (integrator.cpp:146-150): keep the factors apart
-                                    volWeight = isDelta ? -1.f : power_heuristic(1, lightPdf, 1, scatteringPdf);
-                                    pdLight = make_float4(f.r, f.g, f.b, 0);
-                                    vs.pdLi[pdi] = make_float4(Li.r, Li.g, Li.b, lightPdf);
+                                    volWeight = vol_light_weight_of(isDelta, lightPdf, scatteringPdf);
+                                    pdLight = pending_light_encode(f, 0);
+                                    vs.pdLi[pdi] = vol_light_encode(Li, lightPdf);
                                     vs.p1[0][pdi] = make_float4(ls.p.x, ls.p.y, ls.p.z, volWeight); vs.p1[1][pdi] = make_float4(ls.pError.x, ls.pError.y, ls.pError.z, 0);
                                     vs.p1[2][pdi] = make_float4(ls.n.x, ls.n.y, ls.n.z, 0);
-                                    vs.trAcc[0][pdi] = make_float4(1, 1, 1, __int_as_float(dot(shD, is.n) > 0 ? mOut : mIn));
+                                    vs.trAcc[0][pdi] = through_acc_start(dot(shD, is.n) > 0 ? mOut : mIn);
                                 } else {
                                     Spec c = isDelta ? (f * Li) / lightPdf : ((f * Li) * power_heuristic(1, lightPdf, 1, scatteringPdf)) / lightPdf;
-                                    pdLight = make_float4(c.r, c.g, c.b, 0);
+                                    pdLight = pending_light_encode(c, 0);
                                 }
                             }
                         }
@@ -889,8 +891,8 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
                         // (PENDQ with a pend to write: they wait in the MIS ray's LDS slot instead -- free until the end of the kernel, where most vertices
                         // turn them into one float4 for the next queue entry and the listed ones store them for k_resolve_list)
                         pdLight.w = lightSelPdf;
-                        if (PENDQ && qsOut.pend) { s_ray[2][0][tid] = pdLight; s_ray[2][1][tid] = make_float4(beta.r, beta.g, beta.b, 0.f); }
-                        else { st.pdLight[pdi] = pdLight; st.pdBeta[pdi] = make_float4(beta.r, beta.g, beta.b, 0.f); }
+                        if (PENDQ && qsOut.pend) { s_ray[2][0][tid] = pdLight; s_ray[2][1][tid] = pending_beta_encode(beta, 0.f); }
+                        else { st.pdLight[pdi] = pdLight; st.pdBeta[pdi] = pending_beta_encode(beta, 0.f); }
                         // (beta waits in LDS, where it goes at the end anyway, while the BSDF is sampled: three more registers off the same peak)
                         if constexpr (!TEX) { float *sb = reinterpret_cast<float *>(&s_state[1][tid]); sb[0] = beta.r; sb[1] = beta.g; sb[2] = beta.b; }
                         // BSDF sampling half of MIS (integrator.cpp:164-212): sample now, while the BSDF is live; the
@@ -1022,15 +1024,15 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
         const float lightPdf2 = mis_light_pdf<EXT>(sc, misLightPrim, misLightArea, misInside, misP, misRo, misWi, nLightTests);
         if (lightPdf2 != 0) {
             if (PENDQ && qsOut.pend) {  // a listed vertex: the terms staged in this slot go to k_resolve_list's records before the ray takes it
-                const float4 pb = s_ray[2][1][tid];
+                const PendingBeta pb = pending_beta(s_ray[2][1][tid]);
                 st.pdLight[pdi] = s_ray[2][0][tid];
-                st.pdBeta[pdi] = make_float4(pb.x, pb.y, pb.z, power_heuristic(1, misPdf, 1, lightPdf2));
-            } else st.pdBeta[pdi].w = power_heuristic(1, misPdf, 1, lightPdf2);
+                st.pdBeta[pdi] = pending_beta_encode(pb.beta, pending_mis_weight(misPdf, lightPdf2));
+            } else st.pdBeta[pdi].w = pending_mis_weight(misPdf, lightPdf2);
             s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
             s_ray[2][1][tid] = make_float4(misWi.x, misWi.y, misWi.z, __int_as_float(VOL ? pdi : slot));
             pushMis = true;
-            st.pdMis[pdi] = make_float4(misF.r, misF.g, misF.b, misPdf);
-            if constexpr (VOL) vs.trAcc[1][pdi] = make_float4(1, 1, 1, __int_as_float(misMedium));
+            st.pdMis[pdi] = pending_mis_encode(misF, misPdf);
+            if constexpr (VOL) vs.trAcc[1][pdi] = through_acc_start(misMedium);
         }
     }
     // PENDQ: the vertices that need k_resolve's arithmetic (a MIS ray left, or the path ends here with something to add or count) append their positions to
@@ -1058,19 +1060,16 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK, MODE == 0 ? PG_SHADE0_WAVES : (((MO
             if (PENDQ && qsOut.pend) {
                 if (pushNext) {
                     float4 p4 = make_float4(0, 0, 0, __int_as_float(pushMis || lightNum == -1 ? -2 : -1));
-                    if (pushShadow && !pushMis) {  // k_resolve's operations in k_resolve's order, up to the one bit the any-hit launch still owes
-                        const float4 pl = s_ray[2][0][tid], pb = s_ray[2][1][tid];
-                        Spec Ld = sp(0);
-                        Ld = Ld + sp3(pl.x, pl.y, pl.z);
-                        const Spec add = sp3(pb.x, pb.y, pb.z) * (Ld / pl.w);
+                    if (pushShadow && !pushMis) {  // resolve_entry's sums (direct_pend), up to the one bit the any-hit launch still owes
+                        const Spec add = direct_pend(pending_light(s_ray[2][0][tid]), pending_beta(s_ray[2][1][tid]));
                         p4 = make_float4(add.r, add.g, add.b, __int_as_float(posShadow));
                     }
                     qsOut.pend[posNext] = p4;
                 } else if (pushShadow && !pushMis) { st.pdLight[pdi] = s_ray[2][0][tid]; st.pdBeta[pdi] = s_ray[2][1][tid]; }
-                if (listed) st.pdInfo[pdi] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
-            } else st.pdInfo[pdi] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
+                if (listed) st.pdInfo[pdi] = pending_info_encode(posShadow, posMis, lightNum, pending_where(pushNext, posNext, slot));
+            } else st.pdInfo[pdi] = pending_info_encode(posShadow, posMis, lightNum, pending_where(pushNext, posNext, slot));
         }
-    } else if (valid && !deferred && !phaseB) st.pdInfo[slot] = make_int4(posShadow, posMis, lightNum, VOL ? __float_as_int(volWeight) : 0);
+    } else if (valid && !deferred && !phaseB) st.pdInfo[slot] = pending_info_encode(posShadow, posMis, lightNum, VOL ? pending_where_weight(volWeight) : 0);
     if constexpr (SSS) {
         // the probe rays of the paths that go on through a BSSRDF, region by region like every other queue; such a path's L went to
         // its slot above (where k_resolve adds this vertex's direct lighting), beta and meta follow it there
@@ -1313,43 +1312,42 @@ PG_DEV void resolve_entry(const DScene &sc, const PathState &st, int i, const Ra
                           const float4 *__restrict__ misHits, const QueueState &qsNext, unsigned long long *stats) {
     // stats != nullptr: the launch over a bounce's main queue counts "Zero-radiance paths" (path.cpp:119-126): a vertex whose pdInfo names a light
     // (k_shade chose one: its BSDF has non-specular BxDFs) is one of totalPaths, and one of zeroRadiancePaths when its Ld comes out black
-    int4 info = make_int4(-1, -1, -1, 0);
-    if (i >= 0) info = st.pdInfo[i];  // the pending terms lie in queue order (PathState)
-    const bool counted = stats && i >= 0 && info.z != -1;
+    PendingInfo info = pending_nothing();
+    if (i >= 0) info = pending_info(st.pdInfo[i]);  // the pending terms lie in queue order (PathState)
     bool black = true;
-    if (i >= 0 && !(info.x < 0 && info.y < 0)) {  // (else Ld == 0: L += beta * 0 leaves L unchanged)
-    const float4 pl = st.pdLight[i], pb = st.pdBeta[i];
-    Spec Ld = sp(0);
-    if (info.x >= 0 && !occluded[info.x]) Ld = Ld + sp3(pl.x, pl.y, pl.z);
-    if (info.y >= 0) {
-        const float4 pm = st.pdMis[i];  // (written for the vertices with a MIS ray only)
-        const float4 h = misHits[info.y];
-        const int prim = __float_as_int(h.x);
-        if (prim >= 0) {
-            Tri t = load_tri(sc, prim);
-            if (t.light == info.z) {  // lightIsect.primitive->GetAreaLight() == &light
-                const float4 d4 = qmis.d[info.y];
-                const bool onSphere = EXT && (t.flags & PG_PRIM_SPHERE);
-                const Spec Li = area_light_le<EXT>(sc, sc.lights[t.light], prim, t, h, onSphere ? qmis.o[info.y] : d4, mk(d4.x, d4.y, d4.z));
-                if (!is_black(Li)) Ld = Ld + ((((sp3(pm.x, pm.y, pm.z) * Li) * sp(1.f)) * pb.w) / pm.w);
+    if (i >= 0 && pending_any(info)) {
+        const PendingLight pl = pending_light(st.pdLight[i]);
+        const PendingBeta pb = pending_beta(st.pdBeta[i]);
+        Spec Ld = sp(0);
+        if (info.posShadow >= 0) Ld = ld_add_light(Ld, pl.term, occluded[info.posShadow]);
+        if (info.posMis >= 0) {
+            const PendingMis pm = pending_mis(st.pdMis[i]);
+            const float4 h = misHits[info.posMis];
+            const int prim = __float_as_int(h.x);
+            Spec Li = sp(0);  // the sampled light's radiance along the MIS ray, integrator.cpp:199-208
+            if (prim >= 0) {
+                Tri t = load_tri(sc, prim);
+                if (t.light == info.lightNum) {  // lightIsect.primitive->GetAreaLight() == &light
+                    const float4 d4 = qmis.d[info.posMis];
+                    const bool onSphere = EXT && (t.flags & PG_PRIM_SPHERE);
+                    Li = area_light_le<EXT>(sc, sc.lights[t.light], prim, t, h, onSphere ? qmis.o[info.posMis] : d4, mk(d4.x, d4.y, d4.z));
+                }
+            } else if (EXT && sc.lights[info.lightNum].type == PG_LIGHT_INFINITE) {  // integrator.cpp:207-208: no surface hit: Li = light.Le(ray)
+                const float4 d4 = qmis.d[info.posMis];
+                Li = env_le(sc, sc.lights[info.lightNum], mk(d4.x, d4.y, d4.z));
             }
-        } else if (EXT && sc.lights[info.z].type == PG_LIGHT_INFINITE) {  // integrator.cpp:207-208: no surface hit: Li = light.Le(ray)
-            const float4 d4 = qmis.d[info.y];
-            Spec Li = env_le(sc, sc.lights[info.z], mk(d4.x, d4.y, d4.z));
-            if (!is_black(Li)) Ld = Ld + ((((sp3(pm.x, pm.y, pm.z) * Li) * sp(1.f)) * pb.w) / pm.w);
+            Ld = ld_add_mis(Ld, pm.f, Li, sp(1.f), pb.misWeight, pm.pdf);
         }
-    }
-    // the path's L: with its ray in the next queue's state, or -- the path is over -- in its slot
-    float4 *Lp = info.w >= 0 ? &qsNext.L[info.w] : &st.L[~info.w];
-    const float4 L4 = *Lp;
-    const Spec add = sp3(pb.x, pb.y, pb.z) * (Ld / pl.w);  // beta * UniformSampleOneLight(...)
-    black = is_black(add);
-    const Spec L = sp3(L4.x, L4.y, L4.z) + add;
-    *Lp = make_float4(L.r, L.g, L.b, L4.w);
+        // the path's L: with its ray in the next queue's state, or -- the path is over -- in its slot
+        float4 *Lp = pending_L(st, qsNext, info.where);
+        const Spec add = direct_addend(pb.beta, Ld, pl.lightSelectPdf);  // beta * UniformSampleOneLight(...)
+        black = is_black(add);
+        *Lp = direct_add_to_L(*Lp, add);
     }
     if (stats) {  // (uniform over the launch)
-        stats_count(stats, PG_STAT_PATHS, counted);
-        stats_count(stats, PG_STAT_PATHS_ZERO, counted && black);
+        const int counts = i >= 0 ? resolve_path_counts(info.lightNum, black) : 0;
+        stats_count(stats, PG_STAT_PATHS, (counts & 1) != 0);
+        stats_count(stats, PG_STAT_PATHS_ZERO, (counts & 2) != 0);
     }
 }
 template <bool EXT>
@@ -1369,18 +1367,22 @@ __global__ __launch_bounds__(PG_BLOCK) void k_resolve_list(DScene sc, PathState 
         resolve_entry<EXT>(sc, st, k < n ? pj.list[r * regionCap + k] : -1, qmis, pj.occluded, misHits, qsNext, stats);
     }
 }
+// The grid of both launches: a block per PG_BLOCK entries of the queue's capacity, region by region -- with a bound on the blocks per region, or 0 for none
+static int resolve_blocks(const RayQueue &qin, int maxPerRegion) {
+    const int perRegion = qin.regionCap / PG_BLOCK;
+    return PG_REGIONS * (maxPerRegion > 0 && perRegion > maxPerRegion ? maxPerRegion : perRegion);
+}
 void launch_resolve_list(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis, PendJoin pj, const float4 *misHits, hipStream_t s,
                          int cur, unsigned long long *stats) {
     // (the list is a few per cent of the queue: the blocks stride over their region instead of a grid for the queue's capacity that would mostly find nothing)
-    int nblk = PG_REGIONS * (qin.regionCap / PG_BLOCK);
+    const int nblk = resolve_blocks(qin, 256);
     if (nblk == 0) return;
-    if (nblk > PG_REGIONS * 256) nblk = PG_REGIONS * 256;
     if (sc.ext) hipLaunchKernelGGL(k_resolve_list<true>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, st, qmis, pj, misHits, st.qs[cur ^ 1], stats, qin.regionCap);
     else hipLaunchKernelGGL(k_resolve_list<false>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, st, qmis, pj, misHits, st.qs[cur ^ 1], stats, qin.regionCap);
 }
 void launch_resolve(const DScene &sc, PathState st, RayQueue qin, RayQueue qmis, const int *occluded, const float4 *misHits, hipStream_t s,
                     int cur, unsigned long long *stats) {
-    int nblk = PG_REGIONS * (qin.regionCap / PG_BLOCK);
+    const int nblk = resolve_blocks(qin, 0);
     if (nblk == 0) return;
     if (sc.ext) hipLaunchKernelGGL(k_resolve<true>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, st, qin, qmis, occluded, misHits, st.qs[cur ^ 1], stats);
     else hipLaunchKernelGGL(k_resolve<false>, dim3(nblk), dim3(PG_BLOCK), 0, s, sc, st, qin, qmis, occluded, misHits, st.qs[cur ^ 1], stats);
@@ -1420,9 +1422,9 @@ __global__ __launch_bounds__(PG_BLOCK) void k_through(DScene sc, PathState st, V
         const float4 h4 = hits[ri];
         const int prim = __float_as_int(h4.x);
         const bool surface = prim >= 0;
-        const float4 acc = vs.trAcc[KIND][slot];
-        Spec Tr = sp3(acc.x, acc.y, acc.z);
-        int med = __float_as_int(acc.w);
+        const Through acc = through_acc(vs.trAcc[KIND][slot]);
+        Spec Tr = acc.Tr;
+        int med = acc.medium;
         Tri tri;
         if (surface) tri = load_tri(sc, prim);
         const bool opaque = surface && sc.materials[tri.material].type != PG_MAT_NONE;  // isect.primitive->GetMaterial() != nullptr
@@ -1441,12 +1443,12 @@ __global__ __launch_bounds__(PG_BLOCK) void k_through(DScene sc, PathState st, V
             } else if (med) Tr = Tr * medium_tr(sc.media[med - 1], surface ? hitT[ri] : o4.w, sqrtf(lensq(rayD)));
             if (KIND == 1 && !(surface && !opaque)) {
                 // IntersectTr is over (scene.cpp:64-67): the sampled light's radiance along the ray (integrator.cpp:199-208)
-                const int lightNum = st.pdInfo[slot].z;
+                const int lightNum = pending_info(st.pdInfo[slot]).lightNum;
                 Spec Li = sp(0);
                 if (surface) {
                     if (tri.light == lightNum) Li = area_light_le<true>(sc, sc.lights[tri.light], prim, tri, h4, o4, rayD);
                 } else if (sc.lights[lightNum].type == PG_LIGHT_INFINITE) Li = env_le(sc, sc.lights[lightNum], rayD);
-                vs.misLi[slot] = make_float4(Li.r, Li.g, Li.b, 0);
+                vs.misLi[slot] = vol_mis_li_encode(Li);
             } else if (surface) {
                 // a surface without a material: step over it (light.cpp:79 isect.SpawnRayTo(p1), scene.cpp:68 isect.SpawnRay(ray.d))
                 V3 p, pError, n;
@@ -1467,7 +1469,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_through(DScene sc, PathState st, V
                 push = true;
             }
         }
-        vs.trAcc[KIND][slot] = make_float4(Tr.r, Tr.g, Tr.b, __int_as_float(med));
+        vs.trAcc[KIND][slot] = through_acc_encode(Tr, med);
     }
     int pos;
     block_push<1, false>(&qout, &push, &pos);
@@ -1494,28 +1496,19 @@ __global__ __launch_bounds__(PG_BLOCK) void k_resolve_vol(DScene sc, PathState s
     const int i = queue_item<>(qin);
     if (i < 0) return;
     const int slot = QS ? i : __float_as_int(qin.d[i].w);
-    const int4 info = st.pdInfo[slot];
-    if (info.x < 0 && info.y < 0) return;
-    const float4 pl = st.pdLight[slot], pm = st.pdMis[slot], pb = st.pdBeta[slot];
+    const PendingInfo info = pending_info(st.pdInfo[slot]);
+    if (!pending_any(info)) return;
+    const PendingLight pl = pending_light(st.pdLight[slot]);
+    const PendingMis pm = pending_mis(st.pdMis[slot]);
+    const PendingBeta pb = pending_beta(st.pdBeta[slot]);
     Spec Ld = sp(0);
-    if (info.x >= 0) {
-        const float4 li = vs.pdLi[slot], t0 = vs.trAcc[0][slot];
-        const Spec Li = sp3(li.x, li.y, li.z) * sp3(t0.x, t0.y, t0.z);  // Li *= visibility.Tr(scene, sampler)
-        if (!is_black(Li)) {
-            const Spec f = sp3(pl.x, pl.y, pl.z);
-            const float w = QS ? vs.p1[0][slot].w : __int_as_float(info.w);
-            Ld = Ld + (w < 0 ? (f * Li) / li.w : ((f * Li) * w) / li.w);
-        }
+    if (info.posShadow >= 0) {
+        const VolLight li = vol_light(vs.pdLi[slot]);
+        Ld = ld_add_vol_light(Ld, pl.term, li.Li, through_acc(vs.trAcc[0][slot]).Tr, li.lightPdf, [&]() { return vol_light_weight<QS>(vs, slot, info); });
     }
-    if (info.y >= 0) {
-        const float4 ml = vs.misLi[slot], t1 = vs.trAcc[1][slot];
-        const Spec Li = sp3(ml.x, ml.y, ml.z);
-        if (!is_black(Li)) Ld = Ld + ((((sp3(pm.x, pm.y, pm.z) * Li) * sp3(t1.x, t1.y, t1.z)) * pb.w) / pm.w);
-    }
-    float4 *Lp = QS ? (info.w >= 0 ? &qsNext.L[info.w] : &st.L[~info.w]) : &st.L[slot];
-    float4 L4 = *Lp;
-    Spec L = sp3(L4.x, L4.y, L4.z) + sp3(pb.x, pb.y, pb.z) * (Ld / pl.w);
-    *Lp = make_float4(L.r, L.g, L.b, L4.w);
+    if (info.posMis >= 0) Ld = ld_add_mis(Ld, pm.f, vol_mis_li(vs.misLi[slot]), through_acc(vs.trAcc[1][slot]).Tr, pb.misWeight, pm.pdf);
+    float4 *Lp = QS ? pending_L(st, qsNext, info.where) : &st.L[slot];
+    *Lp = direct_add_to_L(*Lp, direct_addend(pb.beta, Ld, pl.lightSelectPdf));
 }
 void launch_resolve_vol(const DScene &sc, PathState st, VolState vs, RayQueue qin, hipStream_t s, int cur) {
     int nblk = PG_REGIONS * (qin.regionCap / PG_BLOCK);
@@ -1646,7 +1639,7 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
     bool alive = false;
     if (j >= 0) {
         slot = __float_as_int(sss.qjob.d[j].w);
-        if (phase != 2) st.pdInfo[VOL ? slot : j] = make_int4(-1, -1, -1, VOL ? 0 : ~slot);
+        if (phase != 2) st.pdInfo[VOL ? slot : j] = pending_info_encode(-1, -1, -1, VOL ? 0 : ~slot);
         const int2 cnt = sss.count[slot];
         alive = cnt.x > 0;  // bssrdf.cpp:318: no hit on the material: Sample_Sp returns black and the path ends (its L is in its slot)
         if (phase == 2) alive = __float_as_int(exitVertex[slot].w) == 1;
@@ -1711,21 +1704,17 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
                     draw2(uL0, uL1);
                     draw2(uS0, uS1);
                     const DirectSetup ed = estimate_direct_setup<true>(sc, ab, is.p, is.pError, is.n, is.wo, lightNum, uL0, uL1, uS0, uS1);
-                    float4 pdLight = make_float4(0, 0, 0, 0);
+                    Spec lightTerm = sp(0);  // (PendingLight::term: volpath keeps f * |cos| apart from Li)
                     if (ed.light.shadow) {
                         [[maybe_unused]] const V3 shD = shadow_ray_to(is.p, is.pError, is.n, ed.light.ls, slot, s_ray[1][0][tid], s_ray[1][1][tid]);
                         pushShadow = true;
                         if constexpr (VOL) {
-                            pdLight = make_float4(ed.light.f.r, ed.light.f.g, ed.light.f.b, 0);
+                            lightTerm = ed.light.f;
                             volWeight = store_vol_light_sample(vs, slot, ed.light, dot(shD, is.n) > 0 ? mOut : mIn);
-                        } else {
-                            const Spec c = direct_light_folded(ed.light);
-                            pdLight = make_float4(c.r, c.g, c.b, 0);
-                        }
+                        } else lightTerm = direct_light_folded(ed.light);
                     }
-                    pdLight.w = lightSelPdf;
-                    st.pdLight[pdi] = pdLight;
-                    st.pdBeta[pdi] = make_float4(beta.r, beta.g, beta.b, 0.f);
+                    st.pdLight[pdi] = pending_light_encode(lightTerm, lightSelPdf);
+                    st.pdBeta[pdi] = pending_beta_encode(beta, 0.f);
                     if (ed.mis.cand) {
                         V3 misRo;
                         spawn_ray(is, ed.mis.wi, misRo);
@@ -1734,9 +1723,9 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
                             s_ray[2][0][tid] = make_float4(misRo.x, misRo.y, misRo.z, PG_INF);
                             s_ray[2][1][tid] = make_float4(ed.mis.wi.x, ed.mis.wi.y, ed.mis.wi.z, __int_as_float(slot));
                             pushMis = true;
-                            st.pdMis[pdi] = make_float4(ed.mis.f.r, ed.mis.f.g, ed.mis.f.b, ed.mis.pdf);
-                            st.pdBeta[pdi].w = power_heuristic(1, ed.mis.pdf, 1, lightPdf2);
-                            if constexpr (VOL) vs.trAcc[1][slot] = make_float4(1, 1, 1, __int_as_float(dot(ed.mis.wi, is.n) > 0 ? mOut : mIn));
+                            st.pdMis[pdi] = pending_mis_encode(ed.mis.f, ed.mis.pdf);
+                            st.pdBeta[pdi].w = pending_mis_weight(ed.mis.pdf, lightPdf2);
+                            if constexpr (VOL) vs.trAcc[1][slot] = through_acc_start(dot(ed.mis.wi, is.n) > 0 ? mOut : mIn);
                         }
                     }
                 }
@@ -1778,10 +1767,10 @@ __global__ __launch_bounds__(PG_SHADE_BLOCK) void k_sss_exit(DScene sc, RenderPa
     if (alive) {
         if constexpr (VOL) {  // by slot: L is there already (k_resolve_vol adds to it), beta and meta follow
             st.beta[slot] = outB; st.meta[slot] = outM;
-            if (phase != 2) st.pdInfo[slot] = make_int4(posShadow, posMis, lightNum, __float_as_int(volWeight));
+            if (phase != 2) st.pdInfo[slot] = pending_info_encode(posShadow, posMis, lightNum, pending_where_weight(volWeight));
         } else {
             if (pushNext) { qsOut.L[posNext] = outL; qsOut.beta[posNext] = outB; qsOut.meta[posNext] = outM; }  // (L itself already is in the slot)
-            st.pdInfo[j] = make_int4(posShadow, posMis, lightNum, pushNext ? posNext : ~slot);
+            st.pdInfo[j] = pending_info_encode(posShadow, posMis, lightNum, pending_where(pushNext, posNext, slot));
         }
     }
     flush_light_tests(lightTriTests, nLightTests);

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: instantiates every function of pg_grid.h / pg_bssrdf.h in a kernel so that tests/test_device_headers_on_host.py can
 // check that the headers are valid gfx950 device code (hipcc --cuda-device-only -c), ahead of their integration into the volpath kernels.
-// The device library of the shading kernels (pg_queue.h ... pg_hit.h, pg_film.h, pg_lightdistrib.h) is included as well: each header must compile for gfx950 outside pg_kernels.hip.
+// The device library of the shading kernels (pg_queue.h ... pg_hit.h, pg_resolve.h, pg_film.h, pg_lightdistrib.h) is included as well: each header must compile for gfx950 outside pg_kernels.hip.
 #include "../pbrt-v3_amd/csrc/pg_grid.h"
 #include "../pbrt-v3_amd/csrc/pg_bssrdf.h"
 #include "../pbrt-v3_amd/csrc/pg_queue.h"
@@ -12,6 +12,7 @@
 #include "../pbrt-v3_amd/csrc/pg_light.h"
 #include "../pbrt-v3_amd/csrc/pg_medium.h"
 #include "../pbrt-v3_amd/csrc/pg_hit.h"
+#include "../pbrt-v3_amd/csrc/pg_resolve.h"
 #include "../pbrt-v3_amd/csrc/pg_film.h"
 #include "../pbrt-v3_amd/csrc/pg_lightdistrib.h"
 struct Lcg { uint32_t s; PG_DEV float operator()() { s = s * 1664525u + 1013904223u; return (float)(s >> 8) * 0x1p-24f; } };

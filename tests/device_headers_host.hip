@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: the device arithmetic headers of the product (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h, pg_grid.h, pg_bssrdf.h, pg_motion.h and the device library of the kernels: pg_queue.h ... pg_hit.h, pg_film.h, pg_lightdistrib.h) compiled for the HOST
+// TEST INFRASTRUCTURE: the device arithmetic headers of the product (pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h, pg_grid.h, pg_bssrdf.h, pg_motion.h and the device library of the kernels: pg_queue.h ... pg_hit.h, pg_resolve.h, pg_film.h, pg_lightdistrib.h) compiled for the HOST
 // (hipcc --cuda-host-only), so that the very source the HIP kernels execute can be run without a GPU and compared with the oracle
 // -- tests/test_device_headers_on_host.py.  Every PG_DEV function becomes __host__ __device__ (the attribute macro is redefined
 // after the runtime header has been read), and the handful of device-only intrinsics they call get host overloads (clang overloads
@@ -30,10 +30,12 @@ __host__ inline unsigned long long __brevll(unsigned long long v) { return __bui
 #include "../pbrt-v3_amd/csrc/pg_light.h"
 #include "../pbrt-v3_amd/csrc/pg_medium.h"
 #include "../pbrt-v3_amd/csrc/pg_hit.h"
+#include "../pbrt-v3_amd/csrc/pg_resolve.h"
 #include "../pbrt-v3_amd/csrc/pg_film.h"
 #include "../pbrt-v3_amd/csrc/pg_lightdistrib.h"
 #include "scatter_probe.h"
 #include "film_probe.h"
+#include "resolve_probe.h"
 
 static V3 v3of(const float *p) { return mk(p[0], p[1], p[2]); }
 extern "C" {
@@ -158,4 +160,9 @@ void hostdev_film_radiance(const PgRenderDesc *rd, const float *in, float *out) 
 float hostdev_film_filter_weight(const PgRenderDesc *rd, int X, int Y, const float *in) { return probe_film_filter_weight(*rd, X, Y, in); }
 void hostdev_voxel(const int *nVoxels, const float *bmin, const float *bmax, int v, int i, float *out) { probe_voxel(nVoxels, bmin, bmax, v, i, out); }
 void hostdev_distribution_finish(float *table, int nl, int nSamples) { probe_distribution_finish(table, nl, nSamples); }
+// EstimateDirect's pending terms and sums (pg_resolve.h): tests/resolve_probe.h says what goes in and out
+void hostdev_resolve_path(const float *in, const int *iin, float *out, int *iout) { probe_resolve_path(in, iin, out, iout); }
+void hostdev_resolve_vol(const float *in, const int *iin, float *out) { probe_resolve_vol(in, iin, out); }
+void hostdev_direct_fold(const float *in, float *out) { probe_direct_fold(in, out); }
+void hostdev_resolve_roundtrip(const float *in, const int *iin, float *out, int *iout) { probe_resolve_roundtrip(in, iin, out, iout); }
 }

@@ -1,5 +1,5 @@
 """The device arithmetic the HIP kernels execute, run WITHOUT a GPU: tests/device_headers_host.hip compiles the product's device headers
-(pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h ... and the kernels' device library, pg_queue.h ... pg_hit.h, pg_film.h, pg_lightdistrib.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
+(pbrt-v3_amd/csrc/pg_device.h, pg_sphere.h ... and the kernels' device library, pg_queue.h ... pg_hit.h, pg_resolve.h, pg_film.h, pg_lightdistrib.h) for the host (hipcc --cuda-host-only, -ffp-contract=off like the device build) and this
 file compares their functions with the oracle bit for bit -- on inputs far outside what the golden scenes contain (coordinates from
 1e-8 to 1e8, quadric radii from 1e-4 to 1e4), including exactly the ray sets of the GPU tests test_triangle_reintersect_on_device /
 test_quadric_reintersect_on_device.  That the gfx950 build of the same source returns the same bits is tests/test_gpu_device_arithmetic.py: it
@@ -77,6 +77,10 @@ def build_host_headers(directory):
     lib.hostdev_film_filter_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.hostdev_voxel.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]
     lib.hostdev_distribution_finish.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.hostdev_resolve_path.restype = lib.hostdev_resolve_vol.restype = lib.hostdev_direct_fold.restype = lib.hostdev_resolve_roundtrip.restype = None
+    lib.hostdev_resolve_path.argtypes = lib.hostdev_resolve_roundtrip.argtypes = [C.c_void_p] * 4
+    lib.hostdev_resolve_vol.argtypes = [C.c_void_p] * 3
+    lib.hostdev_direct_fold.argtypes = [C.c_void_p] * 2
     return lib
 
 
@@ -903,6 +907,265 @@ def test_voxel_box_and_sample_points_equal_their_restatement(dev, oracle):
             u = [F(L.oracle_radical_inverse(base, int(i))) for base in range(5)]
             want = np.array(vmin + vmax + [lerp(u[k], vmin[k], vmax[k]) for k in range(3)] + u[3:], F)
             assert np.array_equal(bits(out), bits(want)), (nv, v, i, out, want)
+
+
+# ---- EstimateDirect's pending terms and sums once the rays are back (csrc/pg_resolve.h): tests/resolve_probe.h ----
+
+# L of next-queue entries 0, 1 and of slots 0, 1 as (rgb, film position): sixteen different words, one of them a negative zero
+RESOLVE_L = np.array([[.25, .5, .75, 100.5], [3, 2, 1, 200.5], [.125, -0.0, 7, 300.5], [1e-3, 1e3, 1, 400.5]], F)
+RESOLVE_WHERE = (0, 1, ~0, ~1)  # pdInfo.w: the path's L by next-queue position, or by ~slot
+
+
+def black32(s):
+    """Spectrum::IsBlack: every channel equal to zero"""
+    return bool((s == 0).all())
+
+
+def resolve_L_index(where):
+    return where if where >= 0 else 2 + ~where
+
+
+def resolve_path_inputs():
+    """(rows of tests/resolve_probe.h's 31 floats, rows of its 5 ints) for the path integrator's sums: the named rows -- nothing pending, with a light chosen
+    (one that counts), none asked for (-1) and none in the scene (-2); the light sample occluded and not, without a MIS ray; a MIS ray that met the light, one
+    whose Li is black, one alone; a light-selection pdf of 1e-40, at which Ld / pdf is infinite; a zero beta under an Ld that is not black; each of them with L
+    at next-queue position 0 and 1 and at slot 0 and 1 -- and 320 random records."""
+    rng = np.random.default_rng(91)
+    frows, irows = [], []
+
+    def add(term=(.5, .25, .125), sel=.5, beta=(.9, .8, .7), w=.375, f=(.3, .2, .1), pdf=.75, li=(2, 3, 4), info=(0, -1, 0), where=0, occ=0):
+        frows.append(np.concatenate([term, [sel], beta, [w], f, [pdf], li, RESOLVE_L.ravel()]).astype(F))
+        irows.append(tuple(info) + (where, occ))
+    for where in RESOLVE_WHERE:
+        for light in (3, -1, -2): add(info=(-1, -1, light), where=where)
+        add(info=(5, -1, 0), occ=1, where=where)
+        add(info=(5, -1, 0), occ=0, where=where)
+        add(info=(5, 2, 1), occ=0, where=where)
+        add(info=(5, 2, 1), occ=1, where=where)
+        add(info=(5, 2, 1), li=(0, 0, 0), where=where)
+        add(info=(5, 2, 1), li=(0, 0, 0), occ=1, where=where)
+        add(info=(-1, 2, 1), where=where)
+        add(info=(-1, 2, 1), li=(0, 0, 0), where=where)
+        add(info=(5, -1, 0), sel=1e-40, where=where)
+        add(info=(5, 2, 0), beta=(0, 0, 0), where=where)
+        add(info=(5, -1, 0), term=(0, 0, 0), where=where)
+    for trial in range(320):
+        pos_s = int(rng.integers(0, 1000)) if rng.random() < .7 else -1
+        pos_m = int(rng.integers(0, 1000)) if rng.random() < .4 else -1
+        add(term=10.0 ** rng.uniform(-3, 2, 3), sel=rng.random() * .99 + .01, beta=rng.random(3) * 1.5, w=rng.random(), f=10.0 ** rng.uniform(-3, 1, 3),
+            pdf=10.0 ** rng.uniform(-2, 2), li=10.0 ** rng.uniform(-2, 2, 3) if rng.random() < .7 else (0, 0, 0),
+            info=(pos_s, pos_m, int(rng.integers(0, 4)) if trial % 9 else -1), where=RESOLVE_WHERE[trial % 4], occ=int(rng.random() < .4))
+    return np.ascontiguousarray(frows, F), np.ascontiguousarray(irows, np.int32)
+
+
+def resolve_path_restated(row, irow):
+    """tests/resolve_probe.h's 22 floats and 1 int of probe_resolve_path in float32 NumPy: EstimateDirect's two sums with handleMedia = false
+    (integrator.cpp:143-161 with the light's term folded, :196-212), L += beta * Ld / lightPdf (integrator.cpp:104 under path.cpp:122-126) and the
+    counting of path.cpp:119-126; then the addend a record with an unoccluded light sample alone has."""
+    term, sel, beta, w, f, pdf, li = row[0:3], row[3], row[4:7], row[7], row[8:11], row[11], row[12:15]
+    L = row[15:31].copy().reshape(4, 4)
+    pos_s, pos_m, light, where, occ = (int(v) for v in irow)
+    add, black = np.zeros(3, F), True
+    with np.errstate(all="ignore"):
+        if not (pos_s < 0 and pos_m < 0):
+            Ld = np.zeros(3, F)
+            if pos_s >= 0 and not occ: Ld = Ld + term                               # integrator.cpp:143-161: Ld += f * Li * weight / lightPdf
+            if pos_m >= 0 and not black32(li): Ld = Ld + (((f * li) * F(1)) * w) / pdf  # integrator.cpp:196-212: Ld += f * Li * Tr * weight / scatteringPdf
+            add = beta * (Ld / sel)                                                 # integrator.cpp:104, path.cpp:122-126
+            black = black32(add)
+            k = resolve_L_index(where)
+            L[k, :3] = L[k, :3] + add
+        pend = beta * ((np.zeros(3, F) + term) / sel)
+    assert add.dtype == F and pend.dtype == F and L.dtype == F
+    return np.concatenate([L.ravel(), add, pend]).astype(F), (0 if light == -1 else 3 if black else 1)
+
+
+def test_resolve_path_sums_equal_their_restatement(dev):
+    """ld_add_light, ld_add_mis, direct_addend, direct_add_to_L, pending_L and resolve_path_counts of pg_resolve.h, called as resolve_entry calls them, against
+    integrator.cpp:143-161, 196-212, :104 and path.cpp:119-126 in float32 NumPy, every output word bit for bit.  With nothing pending all sixteen L words come
+    back as they went in; otherwise all but the three that were added to."""
+    rows, irows = resolve_path_inputs()
+    seen = {"nothing pending": 0, "occluded": 0, "not occluded": 0, "no MIS ray": 0, "MIS ray with a black Li": 0, "MIS ray alone": 0, "infinite quotient": 0,
+            "black addend under an Ld that is not": 0, "L by position": 0, "L by slot": 0, "counted": 0, "counted as zero radiance": 0, "not counted": 0}
+    for k, (row, irow) in enumerate(zip(rows, irows)):
+        out, iout = np.zeros(22, F), np.zeros(1, np.int32)
+        dev.hostdev_resolve_path(row.ctypes.data, irow.ctypes.data, out.ctypes.data, iout.ctypes.data)
+        want, counts = resolve_path_restated(row, irow)
+        assert np.array_equal(bits(out), bits(want)) and iout[0] == counts, (k, row, irow, out, want, iout, counts)
+        pos_s, pos_m, light, where, occ = (int(v) for v in irow)
+        untouched = bits(out[:16]) == bits(row[15:31])
+        if pos_s < 0 and pos_m < 0:
+            assert untouched.all(), (k, out, row)
+            seen["nothing pending"] += 1
+        else:
+            at = 4 * resolve_L_index(where)
+            assert np.delete(untouched, [at, at + 1, at + 2]).all(), (k, out, row)
+            seen["occluded"] += pos_s >= 0 and occ
+            seen["not occluded"] += pos_s >= 0 and not occ
+            seen["no MIS ray"] += pos_m < 0
+            seen["MIS ray with a black Li"] += pos_m >= 0 and black32(row[12:15])
+            seen["MIS ray alone"] += pos_s < 0
+            seen["infinite quotient"] += bool(np.isinf(out[16:19]).all())
+            seen["black addend under an Ld that is not"] += black32(out[16:19]) and black32(row[4:7]) and not black32(row[0:3]) and pos_s >= 0 and not occ
+            seen["L by position"] += where >= 0
+            seen["L by slot"] += where < 0
+        seen["counted"] += iout[0] == 1
+        seen["counted as zero radiance"] += iout[0] == 3
+        seen["not counted"] += iout[0] == 0
+    assert all(n >= 4 for n in seen.values()), seen
+
+
+def test_pend_value_equals_the_full_sums_of_the_same_record_when_not_occluded(dev):
+    """What k_shade relies on: QueueState::pend (direct_pend) of a record is, bit for bit, the addend resolve_entry's sums give for that record with a shadow
+    ray that was not occluded and no MIS ray -- whichever launch adds it, L receives the same words."""
+    rows, irows = resolve_path_inputs()
+    compared = 0
+    for k, (row, irow) in enumerate(zip(rows, irows)):
+        irow = irow.copy()
+        irow[0], irow[1], irow[4] = 7, -1, 0  # a shadow ray at some position, no MIS ray, not occluded
+        out, iout = np.zeros(22, F), np.zeros(1, np.int32)
+        dev.hostdev_resolve_path(row.ctypes.data, irow.ctypes.data, out.ctypes.data, iout.ctypes.data)
+        assert np.array_equal(bits(out[16:19]), bits(out[19:22])), (k, row, out)
+        at = 4 * resolve_L_index(int(irow[3]))
+        with np.errstate(all="ignore"):
+            assert np.array_equal(bits(out[at:at + 3]), bits(row[15 + at:18 + at] + out[19:22])), (k, row, out)
+        compared += 1
+    assert compared >= 300
+
+
+def resolve_vol_inputs():
+    """(rows of tests/resolve_probe.h's 48 floats, rows of its 6 ints) for volpath's sums, each record with queue-order state (the light weight in p1[0].w, L
+    where pdInfo.w says) and without (the weight's bits in pdInfo.w, L by slot): nothing pending; a light that arrives with a MIS weight, and a delta light
+    (weight -1: none is applied); a black transmittance; a transmittance that only dims; a MIS ray that met the light, through a medium, and one whose Li
+    is black; a light-selection pdf of 1e-40; a zero beta -- and 320 random records."""
+    rng = np.random.default_rng(93)
+    frows, irows = [], []
+
+    def add(f=(.5, .25, .125), sel=.5, beta=(.9, .8, .7), mw=.375, mf=(.3, .2, .1), mpdf=.75, li=(2, 3, 4), lpdf=1.25, tr0=(1, 1, 1), tr1=(1, 1, 1), misli=(5, 6, 7),
+            weight=.625, pos=(0, -1), light=0):
+        for qs in (1, 0):
+            for where in RESOLVE_WHERE:
+                frows.append(np.concatenate([f, [sel], beta, [mw], mf, [mpdf], li, [lpdf], tr0, [0], tr1, [0], misli, [0], [0, 0, 0, weight if qs else 77],
+                                             RESOLVE_L.ravel()]).astype(F))
+                irows.append(tuple(pos) + (light, where if qs else int(np.array([weight], F).view(np.int32)[0]), qs, resolve_L_index(where) % 2))
+    add(pos=(-1, -1))
+    add()
+    add(weight=-1)
+    add(tr0=(0, 0, 0))
+    add(tr0=(0, 0, 0), pos=(3, 4))
+    add(tr0=(.5, .25, 0), pos=(3, 4), tr1=(.75, .5, .125))
+    add(pos=(-1, 4), tr1=(.75, .5, .125))
+    add(pos=(3, 4), misli=(0, 0, 0))
+    add(pos=(3, 4), tr1=(0, 0, 0))
+    add(sel=1e-40)
+    add(beta=(0, 0, 0), pos=(3, 4))
+    for trial in range(40):
+        add(f=10.0 ** rng.uniform(-3, 1, 3), sel=rng.random() * .99 + .01, beta=rng.random(3) * 1.5, mw=rng.random(), mf=10.0 ** rng.uniform(-3, 1, 3),
+            mpdf=10.0 ** rng.uniform(-2, 2), li=10.0 ** rng.uniform(-2, 2, 3), lpdf=10.0 ** rng.uniform(-2, 2), tr0=rng.random(3) if trial % 5 else (0, 0, 0),
+            tr1=rng.random(3), misli=10.0 ** rng.uniform(-2, 2, 3) if trial % 3 else (0, 0, 0), weight=rng.random() if trial % 4 else -1,
+            pos=(int(rng.integers(0, 1000)) if trial % 7 else -1, int(rng.integers(0, 1000)) if trial % 2 else -1), light=int(rng.integers(0, 4)))
+    return np.ascontiguousarray(frows, F), np.ascontiguousarray(irows, np.int32)
+
+
+def resolve_vol_restated(row, irow):
+    """probe_resolve_vol's sixteen L words in float32 NumPy: EstimateDirect's sums with handleMedia = true -- Li *= visibility.Tr (integrator.cpp:146-150),
+    f * Li / lightPdf for a delta light and f * Li * weight / lightPdf otherwise (:155-160), f * Li * Tr * weight / scatteringPdf (:196-212) -- and
+    L += beta * Ld / lightPdf (integrator.cpp:104 under volpath.cpp:124-127)."""
+    f, sel, beta, mw, mf, mpdf, li, lpdf, tr0, tr1, misli = row[0:3], row[3], row[4:7], row[7], row[8:11], row[11], row[12:15], row[15], row[16:19], row[20:23], row[24:27]
+    L = row[32:48].copy().reshape(4, 4)
+    pos_s, pos_m, light, where, qs, slot = (int(v) for v in irow)
+    weight = row[31] if qs else np.array([where], np.int32).view(F)[0]
+    with np.errstate(all="ignore"):
+        if not (pos_s < 0 and pos_m < 0):
+            Ld = np.zeros(3, F)
+            if pos_s >= 0:
+                Li = li * tr0
+                if not black32(Li): Ld = Ld + ((f * Li) / lpdf if weight < 0 else ((f * Li) * weight) / lpdf)
+            if pos_m >= 0 and not black32(misli): Ld = Ld + (((mf * misli) * tr1) * mw) / mpdf
+            k = resolve_L_index(where) if qs else 2 + slot
+            L[k, :3] = L[k, :3] + beta * (Ld / sel)
+    assert L.dtype == F
+    return L.ravel()
+
+
+def test_resolve_vol_sums_equal_their_restatement(dev):
+    """ld_add_vol_light, ld_add_mis, direct_addend, direct_add_to_L and vol_light_weight<QS> of pg_resolve.h, called as k_resolve_vol calls them, against
+    integrator.cpp:143-161, 196-212 and :104 with handleMedia = true in float32 NumPy, every L word bit for bit -- with queue-order state and without."""
+    rows, irows = resolve_vol_inputs()
+    seen = {"nothing pending": 0, "delta light": 0, "weighted light": 0, "black transmittance": 0, "MIS ray through a medium": 0, "MIS ray with a black Li": 0,
+            "infinite quotient": 0, "queue-order state": 0, "by slot": 0}
+    for k, (row, irow) in enumerate(zip(rows, irows)):
+        out = np.zeros(16, F)
+        dev.hostdev_resolve_vol(row.ctypes.data, irow.ctypes.data, out.ctypes.data)
+        want = resolve_vol_restated(row, irow)
+        assert np.array_equal(bits(out), bits(want)), (k, row, irow, out, want)
+        pos_s, pos_m, light, where, qs, slot = (int(v) for v in irow)
+        weight = row[31] if qs else np.array([where], np.int32).view(F)[0]
+        if pos_s < 0 and pos_m < 0:
+            assert np.array_equal(bits(out), bits(row[32:48])), (k, out, row)
+            seen["nothing pending"] += 1
+        else:
+            arrives = pos_s >= 0 and not black32(row[12:15] * row[16:19])
+            seen["delta light"] += arrives and weight < 0
+            seen["weighted light"] += arrives and weight >= 0
+            seen["black transmittance"] += pos_s >= 0 and black32(row[16:19])
+            seen["MIS ray through a medium"] += pos_m >= 0 and not black32(row[24:27]) and bool((row[20:23] < 1).all())
+            seen["MIS ray with a black Li"] += pos_m >= 0 and black32(row[24:27])
+            seen["infinite quotient"] += bool(np.isinf(out).any())
+        seen["queue-order state"] += qs
+        seen["by slot"] += not qs
+    assert all(n >= 8 for n in seen.values()), seen
+
+
+def direct_fold_inputs():
+    """rows of tests/resolve_probe.h's 9 floats: the divisors DirectLightingIntegrator has -- nSamples (1, 3, 4, 16), Float(1) / nLights for 1 .. 7 lights, 1 --
+    over 300 random accumulators, some of them zero, and a divisor of 1e-39 under which the quotient is infinite."""
+    rng = np.random.default_rng(95)
+    divisors = [F(1), F(3), F(4), F(16)] + [F(1) / F(n) for n in range(1, 8)]
+    rows = [np.concatenate([10.0 ** rng.uniform(-3, 3, 3), [rng.random() * 1920], 10.0 ** rng.uniform(-3, 3, 3) if k % 10 else (0, 0, 0), [rng.random() * 1080],
+                            [divisors[k % len(divisors)]]]) for k in range(300)]
+    rows.append(np.array([1, 2, 3, 4, 5, 6, 7, 8, 1e-39]))
+    return np.ascontiguousarray(rows, F)
+
+
+def test_direct_fold_equals_its_restatement(dev):
+    """direct_fold against `L += Ld / nSamples` (integrator.cpp:80), `EstimateDirect(...) / lightPdf` (integrator.cpp:104) and directlighting.cpp:84-89: a
+    division per channel, then the sum; the destination's fourth word stays."""
+    for k, row in enumerate(direct_fold_inputs()):
+        out = np.zeros(4, F)
+        dev.hostdev_direct_fold(row.ctypes.data, out.ctypes.data)
+        with np.errstate(all="ignore"):
+            want = np.concatenate([row[0:3] + row[4:7] / row[8], row[3:4]]).astype(F)
+        assert np.array_equal(bits(out), bits(want)), (k, row, out, want)
+
+
+def resolve_roundtrip_inputs():
+    """(rows of tests/resolve_probe.h's 24 floats, rows of its 8 ints): 300 records of random fields -- queue positions up to 2^30 and -1, every light number
+    from -2, media 0 .. 5, the light weight -1 of a delta light among the random ones."""
+    rng = np.random.default_rng(97)
+    frows = 10.0 ** rng.uniform(-3, 3, (300, 24))
+    frows[::5, 23] = -1
+    irows = [(int(rng.integers(0, 1 << 30)) if k % 3 else -1, int(rng.integers(0, 1 << 30)) if k % 4 else -1, int(rng.integers(-2, 9)), k % 2, (k // 2) % 2, (k // 4) % 2,
+              int(rng.integers(0, 6)), int(k % 7 == 0)) for k in range(300)]
+    return np.ascontiguousarray(frows, F), np.ascontiguousarray(irows, np.int32)
+
+
+def test_pending_record_round_trips_every_field(dev):
+    """Each *_encode of pg_resolve.h followed by its decoder returns the field's bits: the light term and selection pdf, beta and the MIS weight, the scattering f
+    and pdf, Li and the light pdf, a through ray's transmittance and medium, misLi, pdInfo's four words, and the volpath light weight read back from p1[0].w
+    (queue-order state) and from pdInfo.w.  pending_where names the next-queue position of a path that goes on and ~slot of one that ended, and pending_L
+    follows it to that word; the two weights are sampling.h:171-174's PowerHeuristic, the MIS ray's of (scatteringPdf, lightPdf) (integrator.cpp:191-192)
+    and the light sample's of (lightPdf, scatteringPdf), -1 for a delta light (integrator.cpp:155-160)."""
+    frows, irows = resolve_roundtrip_inputs()
+    heuristic = lambda a, b: (a * a) / (a * a + b * b)
+    for k, (row, irow) in enumerate(zip(frows, irows)):
+        out, iout = np.zeros(28, F), np.zeros(8, np.int32)
+        dev.hostdev_resolve_roundtrip(row.ctypes.data, irow.ctypes.data, out.ctypes.data, iout.ctypes.data)
+        pos_s, pos_m, light, push_next, pos_next, slot, medium, is_delta = (int(v) for v in irow)
+        want = np.concatenate([row, [heuristic(row[11], row[15]), F(-1) if is_delta else heuristic(row[15], row[22]), row[23], row[23]]]).astype(F)
+        assert np.array_equal(bits(out), bits(want)), (k, row, out, want)
+        where = pos_next if push_next else ~slot
+        assert iout.tolist() == [pos_s, pos_m, light, where, int(not (pos_s < 0 and pos_m < 0)), medium, medium, where], (k, irow, iout)
 
 
 def halton_index_inputs(pkg):

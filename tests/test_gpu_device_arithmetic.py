@@ -47,7 +47,8 @@ def probe(gpu):
            "lobe_f_pdf": [C.c_int] + [P] * 4, "lobe_sample_f": [C.c_int] + [P] * 6, "henyey_greenstein": [C.c_int] + [P] * 7, "halton_index": [C.c_int] + [P] * 5,
            "camera_ray": [C.c_int] + [P] * 6, "adapter_bsdf": [C.c_int] + [P] * 3, "hg_phase": [C.c_int] + [P] * 2, "russian_roulette": [C.c_int] + [P] * 3,
            "film_tile": [C.c_int, P, C.c_int, P, P, P], "film_radiance": [C.c_int, P, C.c_int, P, P, P], "film_filter_weight": [C.c_int] + [P] * 4,
-           "voxel": [C.c_int] + [P] * 6, "distribution_finish": [C.c_int, P, C.c_int, P, P, C.c_int, P]}
+           "voxel": [C.c_int] + [P] * 6, "distribution_finish": [C.c_int, P, C.c_int, P, P, C.c_int, P],
+           "resolve_path": [C.c_int] + [P] * 4, "resolve_vol": [C.c_int] + [P] * 3, "direct_fold": [C.c_int] + [P] * 2, "resolve_roundtrip": [C.c_int] + [P] * 4}
     for name, argtypes in sig.items():
         fn = getattr(lib, "devprobe_" + name)
         fn.restype, fn.argtypes = C.c_int, argtypes
@@ -602,6 +603,25 @@ def case_distribution_finish(probe, host, pkg):
     return N, (want,), device
 
 
+def case_resolve(name, inputs, n_out, n_iout):
+    """One of tests/resolve_probe.h's functions over H's rows for it: float rows, int rows when the function takes them, int outputs when it has them."""
+    def make(probe, host, pkg):
+        made = inputs()
+        frows, irows = made if isinstance(made, tuple) else (made, None)
+        N = len(frows)
+        out, iout = np.zeros((N, n_out), F32), np.zeros((N, n_iout), np.int32)
+        for i in range(N):
+            args = [ptr(frows[i])] + ([ptr(irows[i])] if irows is not None else []) + [ptr(out[i])] + ([ptr(iout[i])] if n_iout else [])
+            getattr(host, "hostdev_" + name)(*args)
+
+        def device(n):
+            dout, diout = np.zeros((n, n_out), F32), np.zeros((n, n_iout), np.int32)
+            run(probe, name, n, *([rows(frows, n)] + ([rows(irows, n)] if irows is not None else []) + [dout] + ([diout] if n_iout else [])))
+            return (dout, diout) if n_iout else (dout,)
+        return N, ((out, iout) if n_iout else (out,)), device
+    return make
+
+
 def case_halton_index(probe, host, pkg):
     per_golden = []
     for golden, scene, rd, pixels in H.halton_index_inputs(pkg):
@@ -648,6 +668,9 @@ CASES.update({"lobe_f_pdf": case_lobe_f_pdf, "lobe_sample_f": case_lobe_sample_f
               "camera_ray": case_camera_ray, "adapter_bsdf": case_adapter_bsdf, "hg_phase": case_hg_phase, "russian_roulette": case_russian_roulette})
 CASES.update({"film_tile": case_film_tile, "film_radiance": case_film_radiance, "film_filter_weight": case_film_filter_weight, "voxel": case_voxel,
               "distribution_finish": case_distribution_finish})
+CASES.update({"resolve_path": case_resolve("resolve_path", H.resolve_path_inputs, 22, 1), "resolve_vol": case_resolve("resolve_vol", H.resolve_vol_inputs, 16, 0),
+              "direct_fold": case_resolve("direct_fold", H.direct_fold_inputs, 4, 0),
+              "resolve_roundtrip": case_resolve("resolve_roundtrip", H.resolve_roundtrip_inputs, 28, 8)})
 CASES.update({"quadric_test_" + kind: case_quadric_test(kind) for kind in ("sphere", "cylinder", "disk", "cone", "paraboloid", "hyperboloid")})
 
 
