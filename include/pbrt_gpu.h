@@ -811,7 +811,8 @@ typedef struct PgLightSample {
  * chooses: no light-selection distribution is built); u: two floats per sample, the Point2f of Sample_Li.  shadow may be NULL; otherwise eight floats
  * per sample, the ray of p0.SpawnRayTo(p1) (interaction.h:73-78): origin[3], tMax = 1 - ShadowEpsilon, d[3], time -- zeros where visibility is -1 --,
  * with which a caller can march Tr itself or trace the ray again.  Occlusion is Scene::IntersectP's at ref.time, the scene seen as pg_intersect_p_at
- * sees it: a medium boundary occludes, as in Unoccluded; VisibilityTester::Tr is not built, nor are Sample_Le / Pdf_Le.  mem and stream as
+ * sees it: a medium boundary occludes, as in Unoccluded; VisibilityTester::Tr of the same ray is pg_transmittance_at below.  Sample_Le / Pdf_Le are not
+ * built, nor are light-selection distributions or TransportMode::Importance.  mem and stream as
  * pg_intersect_at takes them: with PG_MEM_DEVICE no input and no result visits the host; the call synchronises once.  PgCounters: shadow_rays += the
  * number of samples tested (light >= 0 and visibility >= 0), one shadow launch, the any-hit statistics as pg_intersect_p_at moves them; nothing else. */
 int pg_light_sample_at(PgScene *scene, int32_t n, const PgInteraction *ref, const int32_t *light, const float *u,
@@ -828,6 +829,67 @@ int pg_light_pdf_at(PgScene *scene, int32_t n, const PgInteraction *ref, const i
  * pg_intersect_at's; isect may be NULL, otherwise isect[i] receives exactly the bytes pg_intersect_at writes for ray i, from the same trace. */
 int pg_light_le_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
                    PgInteraction *isect, float *Le, int mem, void *stream);
+
+/* ---- participating media, for an integrator whose Li stays on the host: VisibilityTester::Tr, Scene::IntersectTr and Medium::Sample.
+ *
+ * The draws.  A GridDensityMedium tracks with numbers from the path's sampler (grid.cpp:61-120); the three calls take them as u: n_u floats per ray,
+ * u[i * n_u + k] = the value the k-th sampler.Get1D() of ray i's call would return, consumed in order across all segments of the ray.  u may be NULL
+ * with n_u = 0: a scene without grids draws nothing in the two Tr calls.  A draw beyond the stream is 0.5f and draws_used keeps counting (both tracking
+ * loops terminate under it): a record with draws_used > n_u was computed with made-up numbers and must be discarded -- call again with a longer
+ * stream.  A GlobalSampler's dimensions are closed form, so its caller can hand over K dimensions from the path's current one and advance by
+ * draws_used; PCG-stream samplers inside the call are not built. */
+
+/* What one walk through surfaces without a material leaves: 32 bytes, written by the device as two float4. */
+typedef struct PgTransmittance {
+    float   Tr[3];        /* the product over the segments walked; 0 0 0 when blocked */
+    int32_t status;       /* 0 = the walk ended without an opaque surface (Tr query: reached p1; IntersectTr: escaped),
+                             1 = ended at a surface with a material (Tr query: blocked, Tr = 0; IntersectTr: that hit),
+                            -1 = not walked (medium index outside -1 .. n_media-1): every other field 0 */
+    int32_t medium;       /* ray.medium of the last segment walked (media[] index, -1 = none) */
+    int32_t crossings;    /* surfaces without a material stepped over */
+    int32_t draws_used;   /* sampler.Get1D() calls made; > n_u means the stream ran out and the record must be discarded */
+    int32_t reserved;     /* 0 */
+} PgTransmittance;
+
+/* What Medium::Sample leaves: 64 bytes, written by the device as four float4. */
+typedef struct PgMediumSample {
+    int32_t sampled;      /* 1 = a MediumInteraction at t, 0 = none (the ray reaches tMax), -1 = no medium / bad index: all else 0 */
+    int32_t draws_used;
+    float   beta[3];      /* the Spectrum Medium::Sample returns */
+    float   t;            /* ray parameter of the interaction (ray.tMax as given where sampled == 0) */
+    float   p[3];         /* ray(t); 0 where sampled == 0 */
+    float   wo[3];        /* -ray.d, as the MediumInteraction holds it */
+    float   g;            /* the HenyeyGreenstein phase function's g */
+    int32_t medium;       /* as given */
+    float   reserved[2];  /* 0 */
+} PgMediumSample;
+
+/* Batched VisibilityTester::Tr (light.cpp:63-81).  Ray i is the ray of p0.SpawnRayTo(p1): o, d, tmax = 1 - ShadowEpsilon and time exactly as
+ * pg_light_sample_at writes them into `shadow`; medium[i] is that ray's Ray::medium (a media[] index, -1 = none), which the caller derives from
+ * tri_medium_inside / tri_medium_outside[prim] and the sign of dot(d, n), or from the medium vertex; p1: three floats per ray, the point the walk
+ * re-aims at (PgLightSample.p_light; a bare point, interaction.h:69-72).  Per pass: the closest hit at the ray's time; a hit on a primitive whose
+ * material is not PG_MAT_NONE gives Tr = 0 and that segment draws nothing; otherwise Tr *= ray.medium->Tr(ray, sampler) over [0, hit t or tMax], and
+ * after a hit the walk continues with isect.SpawnRayTo(p1) in isect.GetMedium(d).  The arguments are checked before a device is touched; n == 0
+ * returns PG_OK; mem and stream as pg_intersect_at takes them (PG_MEM_DEVICE: no input and no result visits the host).  The call synchronises once
+ * per pass, for the number of rays still under way.  PgCounters: closest_rays += the segments traced, closest_launches += the passes, the closest-hit
+ * visit statistics as pg_intersect_at moves them; nothing else. */
+int pg_transmittance_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                        const float *p1, const int32_t *medium, const float *u, int32_t n_u,
+                        PgTransmittance *out, int mem, void *stream);
+/* Batched Scene::IntersectTr (scene.cpp:57-70): the rays as pg_intersect_at takes them, medium, u and out as above.  The segment's Tr is applied
+ * before the material test, and the walk continues with isect.SpawnRay(ray.d), tMax = inf.  isect may be NULL; otherwise isect[i] is the PgInteraction
+ * of the final hit, prim = -1 on escape (and for a ray that was not walked: then every other field is 0) -- for a ray that ends at its first hit, exactly
+ * the bytes pg_intersect_at writes for it.  Synchronisation and PgCounters as pg_transmittance_at. */
+int pg_intersect_tr_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                       const int32_t *medium, const float *u, int32_t n_u,
+                       PgTransmittance *out, PgInteraction *isect, int mem, void *stream);
+/* Batched Medium::Sample(ray, sampler, arena, &mi): HomogeneousMedium (homogeneous.cpp:49-74: always two draws) and GridDensityMedium (grid.cpp:61-86:
+ * delta tracking; beta = sigma_s / sigma_t at an interaction, else 1).  The ray carries the tMax Scene::Intersect left (PgInteraction.t); time is
+ * accepted for symmetry and not read (media do not move).  Nothing is traced, no counter of PgCounters moves, the call synchronises once.
+ * Phase-function queries are not built: HenyeyGreenstein::p and Sample_p are a few lines on the host, with g from the record. */
+int pg_medium_sample_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                        const int32_t *medium, const float *u, int32_t n_u,
+                        PgMediumSample *out, int mem, void *stream);
 
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);

@@ -45,6 +45,14 @@ SCATTER_DTYPE = np.dtype([("prim", np.int32), ("n_bxdfs", np.int32), ("n_matchin
 LIGHT_SAMPLE_DTYPE = np.dtype([("light", np.int32), ("visibility", np.int32), ("pdf", np.float32), ("Li", np.float32, 3), ("wi", np.float32, 3),
                                ("p_light", np.float32, 3), ("n_light", np.float32, 3), ("reserved", np.float32)])
 
+# one record of pg_transmittance_at / pg_intersect_tr_at: abi.PgTransmittance field for field (32 bytes)
+TRANSMITTANCE_DTYPE = np.dtype([("Tr", np.float32, 3), ("status", np.int32), ("medium", np.int32), ("crossings", np.int32), ("draws_used", np.int32),
+                                ("reserved", np.int32)])
+
+# one record of pg_medium_sample_at: abi.PgMediumSample field for field (64 bytes)
+MEDIUM_SAMPLE_DTYPE = np.dtype([("sampled", np.int32), ("draws_used", np.int32), ("beta", np.float32, 3), ("t", np.float32), ("p", np.float32, 3),
+                                ("wo", np.float32, 3), ("g", np.float32), ("medium", np.int32), ("reserved", np.float32, 2)])
+
 _host = None
 _gpu = None
 
@@ -418,6 +426,76 @@ class GpuScene:
         """pg_light_le_at on caller-owned device buffers: the rays as intersect_at_device takes them, 3 n floats written at le_ptr and, unless isect_ptr is
         None, n records of INTERACTION_DTYPE at isect_ptr."""
         _check(gpu_lib().pg_light_le_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, isect_ptr, le_ptr, PG_MEM_DEVICE, stream), "pg_light_le_at")
+
+    @staticmethod
+    def _medium_inputs(n, medium, u):
+        medium = np.ascontiguousarray(medium, np.int32)
+        if medium.size != n:
+            raise ValueError("medium holds one index per ray")
+        if u is None:
+            return medium, None, 0
+        u = np.ascontiguousarray(u, np.float32)
+        if u.size % max(n, 1) != 0 or (n == 0 and u.size):
+            raise ValueError("u holds the same number of draws for every ray")
+        n_u = u.size // n if n else 0
+        return medium, (u if n_u else None), n_u
+
+    def transmittance_at(self, o, d, tmax, p1, medium, u=None, time=None):
+        """Batched VisibilityTester::Tr (pg_transmittance_at) on host arrays: the rays of p0.SpawnRayTo(p1) as light_sample_at reports them (origin, direction,
+        tmax = 1 - ShadowEpsilon, time), p1 three floats per ray (the point the walk re-aims at), medium one media[] index per ray (-1 = none: the
+        ray's medium), u an (n, n_u) array of sampler draws per ray or None (a scene without grid media draws nothing).  Returns a structured array of
+        TRANSMITTANCE_DTYPE; a record with draws_used > n_u ran out of draws and must be discarded."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        p1 = np.ascontiguousarray(p1, np.float32)
+        if p1.size != 3 * n:
+            raise ValueError("p1 holds three floats per ray")
+        medium, u, n_u = self._medium_inputs(n, medium, u)
+        out = np.empty(n, TRANSMITTANCE_DTYPE)
+        _check(gpu_lib().pg_transmittance_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                             p1.ctypes.data, medium.ctypes.data, None if u is None else u.ctypes.data, n_u, out.ctypes.data, PG_MEM_HOST, None),
+               "pg_transmittance_at")
+        return out
+
+    def intersect_tr_at(self, o, d, tmax, medium, u=None, time=None, with_interaction=False):
+        """Batched Scene::IntersectTr (pg_intersect_tr_at) on host arrays: the rays as intersect_at takes them, medium and u as transmittance_at takes them.
+        Returns a structured array of TRANSMITTANCE_DTYPE or -- with_interaction -- (records, the final hits as INTERACTION_DTYPE, prim = -1 on escape)."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        medium, u, n_u = self._medium_inputs(n, medium, u)
+        out = np.empty(n, TRANSMITTANCE_DTYPE)
+        isect = np.empty(n, INTERACTION_DTYPE) if with_interaction else None
+        _check(gpu_lib().pg_intersect_tr_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                            medium.ctypes.data, None if u is None else u.ctypes.data, n_u, out.ctypes.data,
+                                            None if isect is None else isect.ctypes.data, PG_MEM_HOST, None), "pg_intersect_tr_at")
+        return (out, isect) if with_interaction else out
+
+    def medium_sample_at(self, o, d, tmax, medium, u, time=None):
+        """Batched Medium::Sample (pg_medium_sample_at) on host arrays: the rays with the tmax Scene::Intersect left (intersect_at's t), medium one media[]
+        index per ray, u an (n, n_u) array of draws (a homogeneous medium takes two).  Returns a structured array of MEDIUM_SAMPLE_DTYPE; traces nothing
+        and moves no counter."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        medium, u, n_u = self._medium_inputs(n, medium, u)
+        out = np.empty(n, MEDIUM_SAMPLE_DTYPE)
+        _check(gpu_lib().pg_medium_sample_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                             medium.ctypes.data, None if u is None else u.ctypes.data, n_u, out.ctypes.data, PG_MEM_HOST, None),
+               "pg_medium_sample_at")
+        return out
+
+    def transmittance_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, p1_ptr, medium_ptr, u_ptr, n_u, out_ptr, stream=None):
+        """pg_transmittance_at on caller-owned device buffers (raw pointers, as intersect_at_device takes them): 3 n floats at p1_ptr, n int32 at medium_ptr,
+        n * n_u floats at u_ptr (None with n_u = 0); n records of TRANSMITTANCE_DTYPE written at out_ptr.  Nothing visits the host."""
+        _check(gpu_lib().pg_transmittance_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, p1_ptr, medium_ptr, u_ptr, int(n_u), out_ptr, PG_MEM_DEVICE, stream),
+               "pg_transmittance_at")
+
+    def intersect_tr_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, medium_ptr, u_ptr, n_u, out_ptr, isect_ptr=None, stream=None):
+        """pg_intersect_tr_at on caller-owned device buffers: the outputs as transmittance_at_device's and, unless isect_ptr is None, n records of
+        INTERACTION_DTYPE at isect_ptr."""
+        _check(gpu_lib().pg_intersect_tr_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, medium_ptr, u_ptr, int(n_u), out_ptr, isect_ptr, PG_MEM_DEVICE, stream),
+               "pg_intersect_tr_at")
+
+    def medium_sample_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, medium_ptr, u_ptr, n_u, out_ptr, stream=None):
+        """pg_medium_sample_at on caller-owned device buffers: n records of MEDIUM_SAMPLE_DTYPE written at out_ptr."""
+        _check(gpu_lib().pg_medium_sample_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, medium_ptr, u_ptr, int(n_u), out_ptr, PG_MEM_DEVICE, stream),
+               "pg_medium_sample_at")
 
     def counters(self):
         c = PgCounters()

@@ -186,6 +186,16 @@ class PgLightSample(C.Structure):
                 ("p_light", C.c_float * 3), ("n_light", C.c_float * 3), ("reserved", C.c_float)]
 
 
+class PgTransmittance(C.Structure):
+    _fields_ = [("Tr", C.c_float * 3), ("status", C.c_int32), ("medium", C.c_int32), ("crossings", C.c_int32), ("draws_used", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PgMediumSample(C.Structure):
+    _fields_ = [("sampled", C.c_int32), ("draws_used", C.c_int32), ("beta", C.c_float * 3), ("t", C.c_float), ("p", C.c_float * 3),
+                ("wo", C.c_float * 3), ("g", C.c_float), ("medium", C.c_int32), ("reserved", C.c_float * 2)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -235,6 +245,12 @@ GPU_SYMBOLS = {
     "pg_light_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_light_pdf_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_light_le_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_transmittance_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_intersect_tr_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_medium_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int, C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -81,6 +81,7 @@ struct PgScene {
     // test-path buffers
     DeviceBuffer tO, tD, tCount, tHit, tT, tOcc;  // the test queue; a closest-hit launch's records and t, an any-hit launch's answers
     DeviceBuffer tIn, tInst, tXf, tOut;  // host rays staged, pg_intersect_at's instances and interpolated matrices of the hits, host results staged
+    DeviceBuffer mqIn, mqO, mqD, mqCount, mqState, mqIsect;  // the medium queries: host inputs staged, the second queue of the walk, its state by ray, a pass's interactions by entry
     PgCounters counters;
     std::vector<hipEvent_t> events;
     bool hasNullMaterial = false;
@@ -1564,6 +1565,147 @@ int pg_light_pdf_at(PgScene *s, int32_t n, const PgInteraction *ref, const int32
     return lightQuery(s, {n, ref, light, wi, nullptr, nullptr, pdf, mem, streamPtr});
 }
 
+// ---- batched VisibilityTester::Tr, Scene::IntersectTr and Medium::Sample ----
+// One call of pg_transmittance_at (p1 != nullptr), pg_intersect_tr_at (isectTr) or pg_medium_sample_at (sample != nullptr)
+struct MediumQuery {
+    int32_t n;
+    const float *o, *d, *tmax, *time, *p1;
+    const int32_t *medium;
+    const float *u; int32_t nU;
+    PgTransmittance *out;
+    bool isectTr; PgInteraction *isect;  // pg_intersect_tr_at (isect may be nullptr)
+    PgMediumSample *sample;              // pg_medium_sample_at
+    int mem;
+    void *stream;
+};
+// The walks are throughRays' loop over this call's own buffers: packRays fills the test queue, k_tr_seed moves the rays with a valid medium into the
+// second queue (mqO / mqD) with their state, then per pass launch_closest -- the scene as pg_intersect_at's launch sees it -- and k_tr_step, which
+// finishes rays into their records and appends the re-spawned ones to the other queue; the queue's size is read once per pass.
+static int mediumQuery(PgScene *s, const MediumQuery &r) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)r.stream;
+    const size_t n = (size_t)r.n, n3 = 3 * n, nu = n * (size_t)r.nU;
+    const bool device = r.mem == PG_MEM_DEVICE;
+    const float *o = r.o, *d = r.d, *tmax = r.tmax, *time = r.time, *p1 = r.p1, *u = r.u;
+    const int32_t *medium = r.medium;
+    if (!device) {  // o, d, tmax, time, p1, medium, u in this order
+        HIP_TRY(reserve(s->mqIn, (3 * n3 + 3 * n + nu) * sizeof(float)));
+        float *in = (float *)s->mqIn.p;
+        HIP_TRY(hipMemcpyAsync(in, r.o, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(in + n3, r.d, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(in + 2 * n3, r.tmax, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (r.time) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + n, r.time, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (r.p1) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + 2 * n, r.p1, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(in + 3 * n3 + 2 * n, r.medium, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        if (nu) HIP_TRY(hipMemcpyAsync(in + 3 * n3 + 3 * n, r.u, nu * sizeof(float), hipMemcpyHostToDevice, stream));
+        o = in; d = in + n3; tmax = in + 2 * n3; time = r.time ? in + 2 * n3 + n : nullptr; p1 = r.p1 ? in + 2 * n3 + 2 * n : nullptr;
+        medium = (const int32_t *)(in + 3 * n3 + 2 * n); u = nu ? in + 3 * n3 + 3 * n : nullptr;
+    }
+    if (r.sample) {
+        if (!device) HIP_TRY(reserve(s->tOut, n * sizeof(PgMediumSample)));
+        PgMediumSample *dOut = device ? r.sample : (PgMediumSample *)s->tOut.p;
+        launch_medium_sample(s->d, s->nMedia, o, d, tmax, medium, u, r.nU, r.n, dOut, stream);
+        HIP_TRY(hipGetLastError());
+        if (!device) HIP_TRY(hipMemcpyAsync(r.sample, dOut, n * sizeof(PgMediumSample), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return PG_OK;
+    }
+    // --- the two queues: the test queue (packed: ray i at entry i) and the walk's own
+    RayQueue q[2];
+    float *times[2];
+    const float *none = nullptr;
+    if (int st = packRays(s, r.n, o, d, tmax, time, none, 0, PG_MEM_DEVICE, stream, q[1], times[1])) return st;
+    const int cap = q[1].regionCap;
+    const size_t N = (size_t)cap * PG_REGIONS;
+    HIP_TRY(reserve(s->mqO, N * sizeof(float4)));
+    HIP_TRY(reserve(s->mqD, N * (sizeof(float4) + sizeof(float))));
+    HIP_TRY(reserve(s->mqCount, QSTRIDE * sizeof(int)));
+    q[0].o = (float4 *)s->mqO.p; q[0].d = (float4 *)s->mqD.p; q[0].counts = (int *)s->mqCount.p; q[0].regionCap = cap;
+    times[0] = reinterpret_cast<float *>(q[0].d + N);
+    // --- the walk's state by ray, a pass's records by entry (the regions are not filled front to back after the first append)
+    HIP_TRY(reserve(s->mqState, n * (2 * sizeof(float4) + sizeof(int2))));
+    TrState state;
+    state.tr = (float4 *)s->mqState.p; state.p1 = state.tr + n; state.cnt = (int2 *)(state.p1 + n);
+    HIP_TRY(reserve(s->tHit, sizeof(float4) * N)); HIP_TRY(reserve(s->tT, sizeof(float) * N));
+    const bool wantIsect = r.isectTr && r.isect;
+    if (wantIsect) HIP_TRY(reserve(s->mqIsect, N * sizeof(PgInteraction)));
+    // --- the scene as pg_intersect_at's launch sees it: the hits' instances, a moving one's matrices at the ray's time
+    DScene dsc = s->d;
+    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
+    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * N)); dsc.hitInst = (int *)s->tInst.p; }
+    if (dsc.hasMotion) {
+        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * N * PG_XF_STRIDE * sizeof(float)));
+        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = (int)N;
+    }
+    const size_t recBytes = n * sizeof(PgTransmittance), isectBytes = wantIsect ? n * sizeof(PgInteraction) : 0;
+    if (!device) HIP_TRY(reserve(s->tOut, recBytes + isectBytes));
+    PgTransmittance *dOut = device ? r.out : (PgTransmittance *)s->tOut.p;
+    PgInteraction *dIsect = !wantIsect ? nullptr : device ? r.isect : (PgInteraction *)((char *)s->tOut.p + recBytes);
+    HIP_TRY(hipMemsetAsync(q[0].counts, 0, QSTRIDE * sizeof(int), stream));
+    launch_tr_seed(s->nMedia, q[1], times[1], medium, p1, r.n, state, q[0], times[0], dOut, dIsect, stream);
+    uint64_t segments = 0, passes = 0;
+    int cur = 0;
+    for (int pass = 0;; ++pass) {
+        if (pass > 100000) return setError(PG_ERR_DEVICE, "%s: transmittance loop did not terminate", r.isectTr ? "pg_intersect_tr_at" : "pg_transmittance_at");
+        int blk[QSTRIDE];
+        HIP_TRY(hipMemcpyAsync(blk, q[cur].counts, sizeof(blk), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // the pass's one wait
+        const uint64_t nk = queueTotal(blk, 0);
+        if (nk == 0) break;
+        launch_closest(dsc, s->trace, q[cur], (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+        segments += nk; ++passes;
+        HIP_TRY(hipMemsetAsync(q[cur ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
+        if (wantIsect) launch_interaction(dsc, q[cur], (const float4 *)s->tHit.p, (const float *)s->tT.p, times[cur], (PgInteraction *)s->mqIsect.p, stream);
+        launch_tr_step(dsc, r.isectTr, q[cur], times[cur], (const float4 *)s->tHit.p, (const float *)s->tT.p, state, u, r.nU, q[cur ^ 1], times[cur ^ 1], dOut,
+                       (const PgInteraction *)s->mqIsect.p, dIsect, stream);
+        cur ^= 1;
+    }
+    HIP_TRY(hipGetLastError());
+    if (!device) {
+        HIP_TRY(hipMemcpyAsync(r.out, dOut, recBytes, hipMemcpyDeviceToHost, stream));
+        if (wantIsect) HIP_TRY(hipMemcpyAsync(r.isect, dIsect, isectBytes, hipMemcpyDeviceToHost, stream));
+    }
+    TraceCounters tc[2];
+    int guard = 0;
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    PgCounters &c = s->counters;
+    c.closest_rays += segments; c.closest_launches += passes;
+    if (passes) {
+        c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
+        c.node_visits = tc[0].node_visits + tc[1].node_visits;
+        c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
+    }
+    return cullGuardStatus(s, guard);
+}
+// The three entry points' shared refusals: name, the scene, n, the rays, the media and the draws
+static int mediumQueryArgs(const char *name, PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *u,
+                           int32_t nU, const void *out, const void *extra) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !medium || !out || !extra))) return setError(PG_ERR_INVALID, "%s: null argument", name);
+    if (nU < 0 || (n > 0 && nU > 0 && !u)) return setError(PG_ERR_INVALID, "%s: n_u = %d %s", name, nU, nU < 0 ? "is negative" : "without a stream of draws: null argument");
+    return PG_OK;
+}
+int pg_transmittance_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *p1, const int32_t *medium,
+                        const float *u, int32_t nU, PgTransmittance *out, int mem, void *streamPtr) {
+    if (int e = mediumQueryArgs("pg_transmittance_at", s, n, o, d, tmax, medium, u, nU, out, p1)) return e;
+    if (n == 0) return PG_OK;
+    const MediumQuery r = {n, o, d, tmax, time, p1, medium, u, nU, out, false, nullptr, nullptr, mem, streamPtr};
+    return withExactFallback(s, [&]() { return mediumQuery(s, r); });
+}
+int pg_intersect_tr_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const int32_t *medium, const float *u,
+                       int32_t nU, PgTransmittance *out, PgInteraction *isect, int mem, void *streamPtr) {
+    if (int e = mediumQueryArgs("pg_intersect_tr_at", s, n, o, d, tmax, medium, u, nU, out, out)) return e;
+    if (n == 0) return PG_OK;
+    const MediumQuery r = {n, o, d, tmax, time, nullptr, medium, u, nU, out, true, isect, nullptr, mem, streamPtr};
+    return withExactFallback(s, [&]() { return mediumQuery(s, r); });
+}
+int pg_medium_sample_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const int32_t *medium, const float *u,
+                        int32_t nU, PgMediumSample *out, int mem, void *streamPtr) {
+    if (int e = mediumQueryArgs("pg_medium_sample_at", s, n, o, d, tmax, medium, u, nU, out, out)) return e;
+    if (n == 0) return PG_OK;
+    return mediumQuery(s, {n, o, d, tmax, time, nullptr, medium, u, nU, nullptr, false, nullptr, out, mem, streamPtr});
+}
 
 int pg_counters(PgScene *s, PgCounters *out) {
     if (!s || !out) return setError(PG_ERR_INVALID, "pg_counters: null argument");

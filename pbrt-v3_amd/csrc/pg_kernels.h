@@ -506,5 +506,22 @@ void launch_light_visibility(RayQueue q, const int *occluded, PgLightSample *out
 void launch_light_pdf(const DScene &sc, const PgInteraction *ref, const int32_t *light, const float *wi, int n, float *pdf, hipStream_t s);
 // Le[3i .. 3i+2] = the radiance ray i of q meets after the same launch_closest: isect.Le(-ray.d) at a hit, the infinite lights' Le(ray) on a miss
 void launch_emitted(const DScene &sc, RayQueue q, const float4 *hits, float *Le, hipStream_t s);
+// ---- the medium queries (pg_mediumquery.h)
+// A transmittance walk's state between its passes, by tag (the original ray number, in d.w of every queue entry as k_pack_rays leaves it):
+// tr = (the product so far, ray.medium as index + 1 in w's bits), cnt = (surfaces stepped over, draws made), p1 = the point VisibilityTester::Tr re-aims at
+struct TrState { float4 *tr; int2 *cnt; float4 *p1; };
+// The start of VisibilityTester::Tr (p1 != nullptr: three floats per ray) / Scene::IntersectTr over the packed queue qin (ray i at entry i): the state of the
+// rays whose medium[i] lies in -1 .. nMedia-1, which are appended to qout (counters zeroed by the caller; timesIn / timesOut: the floats behind the queues' d);
+// every other ray gets its record (status -1) in out and, unless isect is null, an interaction of zeros with prim -1
+void launch_tr_seed(int nMedia, RayQueue qin, const float *timesIn, const int32_t *medium, const float *p1, int n, TrState st, RayQueue qout, float *timesOut,
+                    PgTransmittance *out, PgInteraction *isect, hipStream_t s);
+// One pass of the walk after launch_closest(sc, ..., qin, hits, hitT, ...): an entry's segment is attenuated (grid media draw from u[tag * nU ...]), a ray that
+// ends is finished into out[tag] (isectTr: and, unless null, isectOut[tag] = isectIn[entry], launch_interaction's record of this pass), one that stepped
+// over a surface without a material is appended to qout (counters zeroed by the caller)
+void launch_tr_step(const DScene &sc, bool isectTr, RayQueue qin, const float *timesIn, const float4 *hits, const float *hitT, TrState st, const float *u, int nU,
+                    RayQueue qout, float *timesOut, PgTransmittance *out, const PgInteraction *isectIn, PgInteraction *isectOut, hipStream_t s);
+// out[i] = Medium::Sample of medium[i] on ray i (o, d: three floats each; tmax as Scene::Intersect left it) with the draws u[i * nU ...]
+void launch_medium_sample(const DScene &sc, int nMedia, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *u, int nU, int n,
+                          PgMediumSample *out, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

@@ -13,6 +13,8 @@
 //   k_scatter    BSDF::f / Pdf / Sample_f at a ray's closest hit, for pg_scatter_f_at / pg_scatter_sample_at (pg_scatter.h, included at the end)
 //   k_light_sample / k_light_visibility / k_light_pdf / k_emitted  Light::Sample_Li with its visibility, Pdf_Li and the radiance a ray meets, for
 //                pg_light_sample_at / pg_light_pdf_at / pg_light_le_at (pg_lightquery.h, included at the end)
+//   k_tr_seed / k_tr_step / k_medium_sample  VisibilityTester::Tr, Scene::IntersectTr and Medium::Sample per ray, for pg_transmittance_at /
+//                pg_intersect_tr_at / pg_medium_sample_at (pg_mediumquery.h, included at the end)
 //
 // No MFMA: there is no dense contraction on this path; traversal is a
 // latency/bandwidth-bound gather over the node and triangle arrays.
@@ -2004,3 +2006,4 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
 #include "pg_interaction.h"  // the kernels of the ray queries with per-ray time (pg_intersect_at / pg_intersect_p_at)
 #include "pg_scatter.h"  // the kernel of the scattering queries (pg_scatter_f_at / pg_scatter_sample_at)
 #include "pg_lightquery.h"  // the kernels of the light queries (pg_light_sample_at / pg_light_pdf_at / pg_light_le_at)
+#include "pg_mediumquery.h"  // the kernels of the medium queries (pg_transmittance_at / pg_intersect_tr_at / pg_medium_sample_at)

@@ -1,7 +1,8 @@
 // pg_medium.h -- participating media as device functions: HomogeneousMedium's transmittance and distance sample, the
 // Henyey-Greenstein phase function, and a primitive's medium interface.  (GridDensityMedium: pg_grid.h.)
 //
-// Used by the VOL instantiations of k_shade, k_through, k_resolve_vol and k_sss_exit (pg_kernels.hip).  phase_hg / hg_sample_p are
+// Used by the VOL instantiations of k_shade, k_through, k_resolve_vol and k_sss_exit (pg_kernels.hip) and by k_tr_step / k_medium_sample
+// (pg_mediumquery.h).  phase_hg / hg_sample_p are
 // pinned on the host (tests/test_device_headers_on_host.py) and on the device (tests/test_gpu_device_arithmetic.py).
 #ifndef PG_MEDIUM_H
 #define PG_MEDIUM_H
@@ -61,6 +62,21 @@ PG_DEV void homogeneous_sample_distance(const PgMedium &mm, float uChannel, floa
     channel = (int)(uChannel * 3);
     if (channel > 2) channel = 2;
     dist = -pg_logf((1 - uDist)) / mm.sigma_t[channel];
+}
+// ... and the rest of it, homogeneous.cpp:55-73, for a ray of length dLen = |d| whose tMax is tMaxRay: the interaction's ray parameter t (tMaxRay where
+// the ray leaves the medium), whether the medium was sampled, and the weight Sample returns -- k_shade's medium vertex (pg_kernels.hip) spells the same
+// out in place, in this operation order; k_medium_sample (pg_mediumquery.h) calls this.  Pinned by tests/test_medium_headers_on_host.py.
+PG_DEV Spec homogeneous_sample_weight(const PgMedium &mm, float dist, float dLen, float tMaxRay, float &t, bool &inMedium) {
+    t = pmin(dist / dLen, tMaxRay);
+    inMedium = t < tMaxRay;
+    const Spec sigT = sp3(mm.sigma_t[0], mm.sigma_t[1], mm.sigma_t[2]), sigS = sp3(mm.sigma_s[0], mm.sigma_s[1], mm.sigma_s[2]);
+    const Spec Tr = sp_exp((sp3(-sigT.r, -sigT.g, -sigT.b) * pmin(t, PG_MAX_FLOAT)) * dLen);
+    const Spec density = inMedium ? sigT * Tr : Tr;
+    float pdf = 0;
+    pdf += density.r; pdf += density.g; pdf += density.b;
+    pdf *= 1 / (float)3;
+    if (pdf == 0) pdf = 1;
+    return inMedium ? (Tr * sigS) / pdf : Tr / pdf;
 }
 
 #endif  // PG_MEDIUM_H
