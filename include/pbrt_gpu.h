@@ -763,8 +763,8 @@ int pg_intersect_p_at(PgScene *scene, int32_t n, const float *o, const float *d,
 
 /* The BSDF at one ray's closest hit, evaluated or sampled: 64 bytes, written by the device as four float4.  It is the BSDF PathIntegrator::Li holds
  * after isect.ComputeScatteringFunctions(ray, arena, true): TransportMode::Radiance, allowMultipleLobes = true, and a ray without differentials, so every
- * texture footprint is zero (ComputeDifferentials' early-out).  TransportMode::Importance is not built.  A BSSRDF is not reported; the BSDF of a
- * subsurface material is.  The BxDFType bits are the reference's (reflection.h:120-128): REFLECTION 1, TRANSMISSION 2, DIFFUSE 4, GLOSSY 8, SPECULAR 16. */
+ * texture footprint is zero (ComputeDifferentials' early-out).  TransportMode::Importance is not built.  The BSDF of a subsurface material is
+ * reported here; its BSSRDF is pg_subsurface_sample_at's below.  The BxDFType bits are the reference's (reflection.h:120-128): REFLECTION 1, TRANSMISSION 2, DIFFUSE 4, GLOSSY 8, SPECULAR 16. */
 typedef struct PgScatter {
     int32_t prim;          /* -1 = miss: every other field is 0.  Otherwise as pg_intersect_at reports it */
     int32_t n_bxdfs;       /* BSDF::NumComponents(BSDF_ALL); 0 for a primitive without material (medium boundary) or an all-black material */
@@ -890,6 +890,58 @@ int pg_intersect_tr_at(PgScene *scene, int32_t n, const float *o, const float *d
 int pg_medium_sample_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
                         const int32_t *medium, const float *u, int32_t n_u,
                         PgMediumSample *out, int mem, void *stream);
+
+/* ---- subsurface scattering, for an integrator whose Li stays on the host: the BSSRDF branch of PathIntegrator::Li / VolPathIntegrator::Li
+ * (path.cpp:152-174, volpath.cpp:151-176) -- isect.bssrdf, BSSRDF::Sample_S down to the exit point pi, and the BSDF Sample_S installs there. */
+
+/* What bssrdf->Sample_S(scene, u1, u2, arena, &pi, &pdf) leaves for one ray's closest hit po (bssrdf.cpp:238-251; SeparableBSSRDF::Sample_Sp
+ * :253-328): 64 bytes, written by the device as four float4. */
+typedef struct PgSubsurfaceSample {
+    int32_t status;        /* -1 = the ray missed; 0 = a hit whose SurfaceInteraction has no bssrdf; 1 = a bssrdf, but Sample_S returned black or
+                              pdf == 0 (no probe segment, bssrdf.cpp:275-281; a zero probe direction or no hit on the material, :306-318; Sr black;
+                              Pdf_Sp 0): S and pdf are 0, no pi; 2 = sampled: S, pdf and pi are valid */
+    int32_t prim;          /* po's primitive, as pg_intersect_at reports it; -1 on a miss */
+    int32_t bssrdf;        /* bssrdfs[] index of po's material, -1 where status <= 0 */
+    int32_t n_found;       /* hits of the probe chain on po's material (bssrdf.cpp:311-316); 0 where no chain was walked */
+    float   S[3];          /* Sample_S's return value = Sp(pi) = Sr(|po - pi|) (bssrdf.cpp:322-323, bssrdf.h:112) */
+    float   pdf;           /* Pdf_Sp(pi) / nFound (bssrdf.cpp:322-327, :330-350) */
+    float   eta;           /* the BSSRDF's eta: what the exit BSDF needs; 0 where status <= 0 */
+    int32_t medium_inside, medium_outside; /* pi's MediumInterface as media[] indices, -1 = none: the primitive's own transition, else the medium of
+                              the probe ray that found it (primitive.cpp:121-125; Sample_Sp's first probe ray carries none); -1 unless status == 2 */
+    int32_t chain_rays;    /* probe rays the reference traces for this sample: the Scene::Intersect calls of the loop at bssrdf.cpp:303-317 */
+    float   reserved[4];   /* 0 */
+} PgSubsurfaceSample;
+
+/* Batched BSSRDF::Sample_S at the rays' closest hits.  The rays, time, mem and stream exactly as pg_intersect_at takes them.
+ * - The BSDF and isect.bssrdf at po.  The BSDF at po is the one pg_scatter_*_at evaluates: TransportMode::Radiance, allowMultipleLobes = true, no ray
+ *   differentials.  isect.bssrdf exists exactly where the renderer's shading kernel finds one (k_shade<., ., SSS>: material_bssrdf[material] >= 0, and
+ *   for a textured BSSRDF a BSDF with at least one BxDF -- subsurface.cpp:79-80 / kdsubsurface.cpp:80-81 return before they set it otherwise); the
+ *   coefficients of a textured material are evaluated at po (subsurface.cpp:87-90, kdsubsurface.cpp:88-93).
+ * - The transmission test and the draw order.  The call does not test `flags & BSDF_TRANSMISSION` of the direction sampled at po (path.cpp:152): that
+ *   is the caller's line.  u: three floats per ray, u1, u2.x, u2.y -- Sample_S's sampler.Get1D() and sampler.Get2D().  The reference build evaluates
+ *   these arguments right to left: the 2D sample is drawn from the sampler FIRST, then the 1D one (the renderer draws them so).
+ * - The exit point.  pi (required) is the chosen hit as Sample_Sp leaves it, a record as pg_intersect_at writes them with wo = shading_n
+ *   (bssrdf.cpp:243-248), time = the ray's time and t = 0 (pi lies on no ray of the caller's); prim = -1 and zeros unless status == 2.  po may be
+ *   NULL; otherwise po[i] receives exactly the bytes pg_intersect_at writes for ray i, from the same trace.
+ * - PgCounters: closest_rays += n + the sum of chain_rays, closest_launches += 1 + the steps of the longest chain; the closest-hit visit statistics
+ *   as pg_intersect_at moves them, for those launches.  The device walks every chain a second time to stop at the chosen hit; that walk repeats
+ *   queries the reference makes once and is not counted (the renderer's rule).
+ * The arguments are checked before a device is touched; n == 0 returns PG_OK; a scene without BSSRDF materials is served (every hit: status 0).  The
+ * call synchronises once per step of the chains.  BSSRDF::S itself, TransportMode::Importance and Sample_Le / Pdf_Le are not built. */
+int pg_subsurface_sample_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                            const float *u, PgInteraction *po, PgInteraction *pi, PgSubsurfaceSample *out, int mem, void *stream);
+/* Batched BSDF::f and BSDF::Pdf (reflection.cpp:680-693, :781-796) of the BSDF Sample_S installs at pi (bssrdf.cpp:243-248): one
+ * SeparableBSSRDFAdapter (bssrdf.h:209-225) over pi's shading frame, f = Sw(wi) (bssrdf.h:97-100) * eta^2 under TransportMode::Radiance, with BxDF's
+ * cosine-hemisphere Pdf / Sample_f (reflection.cpp:383-394).  pi: the records pg_subsurface_sample_at writes, of which prim (>= 0 = valid), n, wo,
+ * shading_n and shading_dpdu are read; eta: one float per record (PgSubsurfaceSample.eta); wi: three floats per record, world space, used as given;
+ * flags: one BxDFType mask for the call, 0 .. 31.  The PgScatter: n_bxdfs = 1, n_matching = 1 when flags holds REFLECTION | DIFFUSE (else 0), eta = 1
+ * (BSDF's default: Sample_S passes none), shading_n = pi's, types = 0 (the adapter is no PgBxDFType), prim = pi.prim; an invalid record gives
+ * prim = -1 and zeros.  Nothing is traced, no counter of PgCounters moves, the call synchronises once; mem and stream as pg_light_pdf_at. */
+int pg_subsurface_f_at(PgScene *scene, int32_t n, const PgInteraction *pi, const float *eta, const float *wi, int32_t flags,
+                       PgScatter *out, int mem, void *stream);
+/* Batched BSDF::Sample_f (reflection.cpp:714-779) of the same BSDF: as pg_subsurface_f_at, with u: two floats per record, the Point2f. */
+int pg_subsurface_sample_f_at(PgScene *scene, int32_t n, const PgInteraction *pi, const float *eta, const float *u, int32_t flags,
+                              PgScatter *out, int mem, void *stream);
 
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);

@@ -53,6 +53,11 @@ TRANSMITTANCE_DTYPE = np.dtype([("Tr", np.float32, 3), ("status", np.int32), ("m
 MEDIUM_SAMPLE_DTYPE = np.dtype([("sampled", np.int32), ("draws_used", np.int32), ("beta", np.float32, 3), ("t", np.float32), ("p", np.float32, 3),
                                 ("wo", np.float32, 3), ("g", np.float32), ("medium", np.int32), ("reserved", np.float32, 2)])
 
+# one record of pg_subsurface_sample_at: abi.PgSubsurfaceSample field for field (64 bytes)
+SUBSURFACE_SAMPLE_DTYPE = np.dtype([("status", np.int32), ("prim", np.int32), ("bssrdf", np.int32), ("n_found", np.int32), ("S", np.float32, 3),
+                                    ("pdf", np.float32), ("eta", np.float32), ("medium_inside", np.int32), ("medium_outside", np.int32),
+                                    ("chain_rays", np.int32), ("reserved", np.float32, 4)])
+
 _host = None
 _gpu = None
 
@@ -496,6 +501,57 @@ class GpuScene:
         """pg_medium_sample_at on caller-owned device buffers: n records of MEDIUM_SAMPLE_DTYPE written at out_ptr."""
         _check(gpu_lib().pg_medium_sample_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, medium_ptr, u_ptr, int(n_u), out_ptr, PG_MEM_DEVICE, stream),
                "pg_medium_sample_at")
+
+    def subsurface_sample_at(self, o, d, tmax, u, time=None, with_po=False):
+        """Batched BSSRDF::Sample_S at the rays' closest hits (pg_subsurface_sample_at) on host arrays: the rays as intersect_at takes them, u three floats
+        per ray (u1, u2.x, u2.y).  Returns (records of SUBSURFACE_SAMPLE_DTYPE, the exit points pi as INTERACTION_DTYPE: prim = -1 unless status == 2) or --
+        with_po -- (records, pi, what intersect_at returns for the same rays) from the one trace."""
+        o, d, tmax, time, n = self._rays(o, d, tmax, time)
+        u = np.ascontiguousarray(u, np.float32)
+        if u.size != 3 * n:
+            raise ValueError("u holds three floats per ray")
+        out, pi = np.empty(n, SUBSURFACE_SAMPLE_DTYPE), np.empty(n, INTERACTION_DTYPE)
+        po = np.empty(n, INTERACTION_DTYPE) if with_po else None
+        _check(gpu_lib().pg_subsurface_sample_at(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
+                                                 u.ctypes.data, None if po is None else po.ctypes.data, pi.ctypes.data, out.ctypes.data, PG_MEM_HOST, None),
+               "pg_subsurface_sample_at")
+        return (out, pi, po) if with_po else (out, pi)
+
+    def _adapter(self, name, pi, eta, extra, per, flags):
+        pi = np.ascontiguousarray(pi, INTERACTION_DTYPE)
+        eta = np.ascontiguousarray(eta, np.float32)
+        extra = np.ascontiguousarray(extra, np.float32)
+        n = pi.size
+        if eta.size != n or extra.size != per * n:
+            raise ValueError("eta holds one float and " + ("wi three floats" if per == 3 else "u two floats") + " per exit point")
+        out = np.empty(n, SCATTER_DTYPE)
+        _check(getattr(gpu_lib(), name)(self._h, n, pi.ctypes.data, eta.ctypes.data, extra.ctypes.data, int(flags), out.ctypes.data, PG_MEM_HOST, None), name)
+        return out
+
+    def subsurface_f_at(self, pi, eta, wi, flags=31):
+        """Batched BSDF::f and BSDF::Pdf of the BSDF Sample_S installs at the exit points (pg_subsurface_f_at) on host arrays: pi the records
+        subsurface_sample_at returns (prim >= 0 marks a valid one), eta one float per record (the sample's eta), wi three floats per record (world space,
+        used as given), flags one BxDFType mask.  Returns SCATTER_DTYPE records; traces nothing and moves no counter."""
+        return self._adapter("pg_subsurface_f_at", pi, eta, wi, 3, flags)
+
+    def subsurface_sample_f_at(self, pi, eta, u, flags=31):
+        """Batched BSDF::Sample_f of the same BSDF (pg_subsurface_sample_f_at): as subsurface_f_at, with u two floats per record."""
+        return self._adapter("pg_subsurface_sample_f_at", pi, eta, u, 2, flags)
+
+    def subsurface_sample_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, po_ptr, pi_ptr, out_ptr, stream=None):
+        """pg_subsurface_sample_at on caller-owned device buffers (raw pointers, as intersect_at_device takes them): 3 n floats at u_ptr; n records of
+        SUBSURFACE_SAMPLE_DTYPE written at out_ptr, n of INTERACTION_DTYPE at pi_ptr and, unless po_ptr is None, at po_ptr.  Nothing visits the host."""
+        _check(gpu_lib().pg_subsurface_sample_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, po_ptr, pi_ptr, out_ptr, PG_MEM_DEVICE, stream),
+               "pg_subsurface_sample_at")
+
+    def subsurface_f_at_device(self, n, pi_ptr, eta_ptr, wi_ptr, flags, out_ptr, stream=None):
+        """pg_subsurface_f_at on caller-owned device buffers: n records of INTERACTION_DTYPE at pi_ptr, n floats at eta_ptr, 3 n at wi_ptr; n records of
+        SCATTER_DTYPE written at out_ptr."""
+        _check(gpu_lib().pg_subsurface_f_at(self._h, n, pi_ptr, eta_ptr, wi_ptr, int(flags), out_ptr, PG_MEM_DEVICE, stream), "pg_subsurface_f_at")
+
+    def subsurface_sample_f_at_device(self, n, pi_ptr, eta_ptr, u_ptr, flags, out_ptr, stream=None):
+        """pg_subsurface_sample_f_at on caller-owned device buffers: 2 n floats at u_ptr, the rest as subsurface_f_at_device's."""
+        _check(gpu_lib().pg_subsurface_sample_f_at(self._h, n, pi_ptr, eta_ptr, u_ptr, int(flags), out_ptr, PG_MEM_DEVICE, stream), "pg_subsurface_sample_f_at")
 
     def counters(self):
         c = PgCounters()

@@ -196,6 +196,11 @@ class PgMediumSample(C.Structure):
                 ("wo", C.c_float * 3), ("g", C.c_float), ("medium", C.c_int32), ("reserved", C.c_float * 2)]
 
 
+class PgSubsurfaceSample(C.Structure):
+    _fields_ = [("status", C.c_int32), ("prim", C.c_int32), ("bssrdf", C.c_int32), ("n_found", C.c_int32), ("S", C.c_float * 3), ("pdf", C.c_float),
+                ("eta", C.c_float), ("medium_inside", C.c_int32), ("medium_outside", C.c_int32), ("chain_rays", C.c_int32), ("reserved", C.c_float * 4)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -251,6 +256,10 @@ GPU_SYMBOLS = {
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_medium_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_subsurface_sample_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_subsurface_f_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_subsurface_sample_f_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

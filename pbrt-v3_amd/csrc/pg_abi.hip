@@ -82,6 +82,7 @@ struct PgScene {
     DeviceBuffer tO, tD, tCount, tHit, tT, tOcc;  // the test queue; a closest-hit launch's records and t, an any-hit launch's answers
     DeviceBuffer tIn, tInst, tXf, tOut;  // host rays staged, pg_intersect_at's instances and interpolated matrices of the hits, host results staged
     DeviceBuffer mqIn, mqO, mqD, mqCount, mqState, mqIsect;  // the medium queries: host inputs staged, the second queue of the walk, its state by ray, a pass's interactions by entry
+    DeviceBuffer ssO[3], ssD[3], ssCount, ssState, ssXf;  // the subsurface queries: the job queue and the two probe queues, the SssState by ray with chain_rays, the chosen hits' matrices
     PgCounters counters;
     std::vector<hipEvent_t> events;
     bool hasNullMaterial = false;
@@ -1705,6 +1706,154 @@ int pg_medium_sample_at(PgScene *s, int32_t n, const float *o, const float *d, c
     if (int e = mediumQueryArgs("pg_medium_sample_at", s, n, o, d, tmax, medium, u, nU, out, out)) return e;
     if (n == 0) return PG_OK;
     return mediumQuery(s, {n, o, d, tmax, time, nullptr, medium, u, nU, nullptr, false, nullptr, out, mem, streamPtr});
+}
+
+// ---- batched BSSRDF::Sample_S at the rays' closest hits, and the BSDF it installs at the exit point ----
+struct SubsurfaceQuery {
+    int32_t n;
+    const float *o, *d, *tmax, *time, *u;
+    PgInteraction *po, *pi;  // po may be nullptr
+    PgSubsurfaceSample *out;
+    int mem;
+    void *stream;
+};
+// packRays, one closest-hit launch as pg_intersect_at's (k_interaction into po where asked for), k_sss_seed, then sssProbeChains' loop over this call's
+// own queues -- the job queue and two probe queues of the test queue's geometry -- with the SssState indexed by ray number in grow-only scratch, and
+// k_sss_emit.  The first walk's launches count (and k_sss_tally notes each probe ray for its sample's chain_rays); the second walk's go to the third set
+// of trace counters, as the renderer's.  One wait per step, for the number of chains still under way.
+static int subsurfaceQuery(PgScene *s, const SubsurfaceQuery &r) {
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)r.stream;
+    const size_t n = (size_t)r.n;
+    const bool device = r.mem == PG_MEM_DEVICE, vol = s->nMedia > 0;
+    RayQueue q;
+    float *times = nullptr;
+    const float *u = r.u;
+    if (int st = packRays(s, r.n, r.o, r.d, r.tmax, r.time, u, 3, r.mem, stream, q, times)) return st;
+    const int cap = q.regionCap;
+    const size_t N = (size_t)cap * PG_REGIONS;
+    // --- the scene as pg_intersect_at's launch sees it, its records by queue entry: the probe queues are not filled front to back
+    DScene dsc = s->d;
+    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
+    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * N)); dsc.hitInst = (int *)s->tInst.p; }
+    if (dsc.hasMotion) {
+        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * N * PG_XF_STRIDE * sizeof(float)));
+        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = (int)N;
+    }
+    HIP_TRY(reserve(s->tHit, sizeof(float4) * N)); HIP_TRY(reserve(s->tT, sizeof(float) * N));
+    // --- the job queue and the two probe queues (their rays' times behind d, PG_QUEUE_TIMES), the state by ray
+    RayQueue sq[3];
+    HIP_TRY(reserve(s->ssCount, 3 * QSTRIDE * sizeof(int)));
+    for (int k = 0; k < 3; ++k) {
+        HIP_TRY(reserve(s->ssO[k], N * sizeof(float4)));
+        HIP_TRY(reserve(s->ssD[k], N * (sizeof(float4) + sizeof(float))));
+        sq[k].o = (float4 *)s->ssO[k].p; sq[k].d = (float4 *)s->ssD[k].p; sq[k].counts = (int *)s->ssCount.p + k * QSTRIDE; sq[k].regionCap = cap;
+    }
+    HIP_TRY(reserve(s->ssState, n * (10 * sizeof(float4) + 2 * sizeof(int2) + 2 * sizeof(int))));
+    if (dsc.hasMotion) HIP_TRY(reserve(s->ssXf, (dsc.hasNest ? 2 : 1) * n * PG_XF_STRIDE * sizeof(float)));
+    SssState st = {};
+    float4 *f4 = (float4 *)s->ssState.p;
+    st.po = f4; st.frame[0] = f4 + n; st.frame[1] = f4 + 2 * n; st.frame[2] = f4 + 3 * n; st.coef[0] = f4 + 4 * n; st.coef[1] = f4 + 5 * n;
+    st.target = f4 + 6 * n; st.hit = f4 + 7 * n; st.hitO = f4 + 8 * n; st.hitD = f4 + 9 * n;
+    st.count = (int2 *)(f4 + 10 * n); st.medium = st.count + n; st.hitInst = (int *)(st.medium + n);
+    int *chain = st.hitInst + n;
+    st.hitXf = dsc.hasMotion ? (float *)s->ssXf.p : nullptr; st.hitXfNest = r.n;
+    st.qjob = sq[0];
+    // --- the results: PG_MEM_DEVICE: the kernels write the caller's arrays; otherwise into tOut (records, pi, po), copied to the caller below
+    const size_t recBytes = n * sizeof(PgSubsurfaceSample), isectBytes = n * sizeof(PgInteraction);
+    if (!device) HIP_TRY(reserve(s->tOut, recBytes + (r.po ? 2 : 1) * isectBytes));
+    PgSubsurfaceSample *dOut = device ? r.out : (PgSubsurfaceSample *)s->tOut.p;
+    PgInteraction *dPi = device ? r.pi : (PgInteraction *)((char *)s->tOut.p + recBytes);
+    PgInteraction *dPo = !r.po ? nullptr : device ? r.po : (PgInteraction *)((char *)s->tOut.p + recBytes + isectBytes);
+    TraceCounters *cn = (TraceCounters *)s->traceCn.p;
+    launch_closest(dsc, s->trace, q, (float4 *)s->tHit.p, (float *)s->tT.p, cn, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+    if (dPo) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dPo, stream);
+    HIP_TRY(hipMemsetAsync(st.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
+    launch_sss_seed(dsc, vol, q, (const float4 *)s->tHit.p, times, u, r.n, st, chain, dOut, dPi, stream);
+    auto total = [&](const int *counts, uint64_t &t) -> int {
+        int blk[QSTRIDE];
+        HIP_TRY(hipMemcpyAsync(blk, counts, sizeof(blk), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        t = queueTotal(blk, 0);
+        return PG_OK;
+    };
+    uint64_t nJobs = 0, chainRays = 0, steps = 0;
+    if (int e = total(st.qjob.counts, nJobs)) return e;
+    for (int pass = 1; pass <= 2 && nJobs > 0; ++pass) {
+        RayQueue curQ = st.qjob;
+        uint64_t nRays = nJobs;
+        for (int step = 0; nRays > 0; ++step) {
+            if (step > 1000000) return setError(PG_ERR_DEVICE, "pg_subsurface_sample_at: a BSSRDF probe chain did not terminate");
+            RayQueue outQ = sq[1 + (step & 1)];
+            HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), stream));
+            launch_closest(dsc, s->trace, curQ, (float4 *)s->tHit.p, nullptr, pass == 1 ? cn : cn + 2, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+            if (pass == 1) { chainRays += nRays; ++steps; launch_sss_tally(curQ, chain, stream); }
+            launch_sss_probe(dsc, st, pass, curQ, (const float4 *)s->tHit.p, outQ, stream, vol, vol && step == 0);
+            if (int e = total(outQ.counts, nRays)) return e;
+            curQ = outQ;
+        }
+    }
+    if (nJobs > 0) launch_sss_emit(dsc, vol, st, chain, times, dOut, dPi, stream);
+    HIP_TRY(hipGetLastError());
+    if (!device) {
+        HIP_TRY(hipMemcpyAsync(r.out, dOut, recBytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(r.pi, dPi, isectBytes, hipMemcpyDeviceToHost, stream));
+        if (r.po) HIP_TRY(hipMemcpyAsync(r.po, dPo, isectBytes, hipMemcpyDeviceToHost, stream));
+    }
+    TraceCounters tc[2];
+    int guard = 0;
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    PgCounters &c = s->counters;
+    c.closest_rays += n + chainRays; c.closest_launches += 1 + steps;
+    c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
+    c.node_visits = tc[0].node_visits + tc[1].node_visits;
+    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
+    return cullGuardStatus(s, guard);
+}
+int pg_subsurface_sample_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *u, PgInteraction *po,
+                            PgInteraction *pi, PgSubsurfaceSample *out, int mem, void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !u || !pi || !out))) return setError(PG_ERR_INVALID, "pg_subsurface_sample_at: null argument");
+    if (n == 0) return PG_OK;
+    const SubsurfaceQuery r = {n, o, d, tmax, time, u, po, pi, out, mem, streamPtr};
+    return withExactFallback(s, [&]() { return subsurfaceQuery(s, r); });
+}
+// The two exit-BSDF calls: stage, k_adapter, copy back, one wait.  Nothing is traced and no counter moves.
+static int adapterQuery(const char *name, PgScene *s, int32_t n, const PgInteraction *pi, const float *eta, const float *in, bool sample, int32_t flags,
+                        PgScatter *out, int mem, void *streamPtr) {
+    if (!s || n < 0 || (n > 0 && (!pi || !eta || !in || !out))) return setError(PG_ERR_INVALID, "%s: null argument", name);
+    if (flags < 0 || flags > 31) return setError(PG_ERR_INVALID, "%s: flags %d is not a BxDFType mask (0 .. 31)", name, flags);
+    if (n == 0) return PG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    const size_t nn = (size_t)n, inPer = sample ? 2 : 3;
+    const bool device = mem == PG_MEM_DEVICE;
+    PgScatter *dOut = out;
+    if (!device) {  // the records, eta and the per-record input, in this order (16-byte aligned records first)
+        HIP_TRY(reserve(s->tIn, nn * (sizeof(PgInteraction) + (inPer + 1) * sizeof(float))));
+        HIP_TRY(reserve(s->tOut, nn * sizeof(PgScatter)));
+        char *base = (char *)s->tIn.p;
+        HIP_TRY(hipMemcpyAsync(base, pi, nn * sizeof(PgInteraction), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(base + nn * sizeof(PgInteraction), eta, nn * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(base + nn * (sizeof(PgInteraction) + sizeof(float)), in, nn * inPer * sizeof(float), hipMemcpyHostToDevice, stream));
+        pi = (const PgInteraction *)base;
+        eta = (const float *)(base + nn * sizeof(PgInteraction));
+        in = eta + nn;
+        dOut = (PgScatter *)s->tOut.p;
+    }
+    launch_adapter(pi, eta, in, sample, flags, n, dOut, stream);
+    HIP_TRY(hipGetLastError());
+    if (!device) HIP_TRY(hipMemcpyAsync(out, dOut, nn * sizeof(PgScatter), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PG_OK;
+}
+int pg_subsurface_f_at(PgScene *s, int32_t n, const PgInteraction *pi, const float *eta, const float *wi, int32_t flags, PgScatter *out, int mem, void *streamPtr) {
+    return adapterQuery("pg_subsurface_f_at", s, n, pi, eta, wi, false, flags, out, mem, streamPtr);
+}
+int pg_subsurface_sample_f_at(PgScene *s, int32_t n, const PgInteraction *pi, const float *eta, const float *u, int32_t flags, PgScatter *out, int mem,
+                              void *streamPtr) {
+    return adapterQuery("pg_subsurface_sample_f_at", s, n, pi, eta, u, true, flags, out, mem, streamPtr);
 }
 
 int pg_counters(PgScene *s, PgCounters *out) {

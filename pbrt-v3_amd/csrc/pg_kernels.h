@@ -523,5 +523,17 @@ void launch_tr_step(const DScene &sc, bool isectTr, RayQueue qin, const float *t
 // out[i] = Medium::Sample of medium[i] on ray i (o, d: three floats each; tmax as Scene::Intersect left it) with the draws u[i * nU ...]
 void launch_medium_sample(const DScene &sc, int nMedia, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *u, int nU, int n,
                           PgMediumSample *out, hipStream_t s);
+// ---- the subsurface queries (pg_subsurfacequery.h)
+// The start of BSSRDF::Sample_S over the packed queue q (ray i at entry i) after launch_closest(sc, ..., q, hits, ...): every ray's record (status -1 / 0 / 1)
+// in out, a pi of zeros with prim -1, chain[i] = 0; a ray with a probe segment (u: three floats per ray -- u1, u2.x, u2.y) gets its SssState at slot i and its
+// first probe ray in sss.qjob (counters zeroed by the caller; tag i, time timesIn[i]).  vol: the scene has media (SssState::medium is kept)
+void launch_sss_seed(const DScene &sc, bool vol, RayQueue q, const float4 *hits, const float *timesIn, const float *u, int n, SssState sss, int *chain,
+                     PgSubsurfaceSample *out, PgInteraction *pi, hipStream_t s);
+// chain[tag] += 1 for every entry of q: the probe rays of the first walk per sample (PgSubsurfaceSample::chain_rays)
+void launch_sss_tally(RayQueue q, int *chain, hipStream_t s);
+// The end of Sample_S for the jobs of sss.qjob after both walks: S, pdf, n_found, chain_rays, pi's media and -- status 2 -- pi (time = times[ray])
+void launch_sss_emit(const DScene &sc, bool vol, SssState sss, const int *chain, const float *times, PgSubsurfaceSample *out, PgInteraction *pi, hipStream_t s);
+// out[i] = BSDF::f and Pdf (in = wi, three floats) or Sample_f (sample: in = u, two floats) of the SeparableBSSRDFAdapter at pi[i] with eta[i]
+void launch_adapter(const PgInteraction *pi, const float *eta, const float *in, bool sample, int flags, int n, PgScatter *out, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

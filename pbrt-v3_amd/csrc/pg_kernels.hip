@@ -15,6 +15,8 @@
 //                pg_light_sample_at / pg_light_pdf_at / pg_light_le_at (pg_lightquery.h, included at the end)
 //   k_tr_seed / k_tr_step / k_medium_sample  VisibilityTester::Tr, Scene::IntersectTr and Medium::Sample per ray, for pg_transmittance_at /
 //                pg_intersect_tr_at / pg_medium_sample_at (pg_mediumquery.h, included at the end)
+//   k_sss_seed / k_sss_tally / k_sss_emit / k_adapter  BSSRDF::Sample_S per ray around k_sss_probe's chains and the exit point's adapter BSDF, for
+//                pg_subsurface_sample_at / pg_subsurface_f_at / pg_subsurface_sample_f_at (pg_subsurfacequery.h, included at the end)
 //
 // No MFMA: there is no dense contraction on this path; traversal is a
 // latency/bandwidth-bound gather over the node and triangle arrays.
@@ -1534,6 +1536,8 @@ void launch_fill_int(int *p, int value, int n, hipStream_t s) {
 // pass 1 counts the hits on the material, pass 2 stops at the chosen one.  Each step is one k_trace<0, .> launch over the
 // chains still under way followed by k_sss_probe.
 // ===========================================================================
+// Invariant others rely on: a chain has ONE probe ray under way -- an entry of qin appends at most one entry to qout, with its own slot as tag -- so a slot
+// appears at most once in a queue.  k_sss_tally (pg_subsurfacequery.h) counts a sample's probe rays with a plain chain[tag] += 1 on that ground.
 // NEST: DScene::hasNest -- the chain's hits can lie under two transforms (a moving shape inside an object definition)
 template <int PASS, bool VOL, bool NEST = false>
 __global__ __launch_bounds__(PG_BLOCK) void k_sss_probe(DScene sc, SssState sss, RayQueue qin, const float4 *__restrict__ hits, RayQueue qout, int first) {
@@ -2007,3 +2011,4 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
 #include "pg_scatter.h"  // the kernel of the scattering queries (pg_scatter_f_at / pg_scatter_sample_at)
 #include "pg_lightquery.h"  // the kernels of the light queries (pg_light_sample_at / pg_light_pdf_at / pg_light_le_at)
 #include "pg_mediumquery.h"  // the kernels of the medium queries (pg_transmittance_at / pg_intersect_tr_at / pg_medium_sample_at)
+#include "pg_subsurfacequery.h"  // the kernels of the subsurface queries (pg_subsurface_sample_at / pg_subsurface_f_at / pg_subsurface_sample_f_at)
