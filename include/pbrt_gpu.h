@@ -943,6 +943,51 @@ int pg_subsurface_f_at(PgScene *scene, int32_t n, const PgInteraction *pi, const
 int pg_subsurface_sample_f_at(PgScene *scene, int32_t n, const PgInteraction *pi, const float *eta, const float *u, int32_t flags,
                               PgScatter *out, int mem, void *stream);
 
+/* ---- Camera queries, for an integrator whose Li stays on the host: the first vertex of every path.  The cameras live on the device (a moving camera's
+ * interpolation and the realistic camera's lens system included); these calls answer Camera::GenerateRayDifferential for a batch of CameraSamples and carry
+ * the ray's differentials into ComputeScatteringFunctions at the camera ray's hit. */
+
+/* What camera.GenerateRayDifferential(cameraSample, &ray) leaves for one CameraSample, in world space: 96 bytes, written by the device as six float4.
+ * The differentials are the ones SamplerIntegrator::Render hands to Li: AFTER ray.ScaleDifferentials(1 / sqrt(spp)) (integrator.cpp:282-283, geometry.h:908-913)
+ * with spp = PgRenderDesc.spp -- what the frames' own kernels compute.  Unscaled differentials are not reported. */
+typedef struct PgCameraRay {
+    float o[3];                /* ray.o */
+    float t_max;               /* ray.tMax (infinity, less what Transform::operator()(Ray) takes off for the origin's error bound) */
+    float d[3];                /* ray.d */
+    float time;                /* ray.time = Lerp(u_time, shutter_open, shutter_close) */
+    float weight;              /* GenerateRayDifferential's return value: 1 for the perspective, orthographic and environment cameras, the lens weight for
+                                  the realistic camera; 0 = the sample is vignetted (the main ray, or both shifts of an axis): EVERY other field is then 0 */
+    int32_t medium;            /* ray.medium = PgRenderDesc.camera_medium (media[] index, -1 = none) */
+    int32_t has_differentials; /* ray.hasDifferentials: 1 unless weight == 0 */
+    float reserved;            /* written as 0 */
+    float differentials[12];   /* rxOrigin, rxDirection, ryOrigin, ryDirection, three floats each: what pg_scatter_*_diff_at take per ray */
+} PgCameraRay;
+
+/* Batched Camera::GenerateRayDifferential (cameras/perspective.cpp:117-144, orthographic.cpp:95-117, camera.cpp:52-97 for the environment and realistic
+ * cameras) of the camera `desc` describes -- still or moving (AnimatedTransform::Interpolate at every ray's time), camera_type 0 .. 3 --, scaled as above.
+ * p_film: two floats per sample, CameraSample::pFilm (raster space; points outside the image are served); p_lens: two floats per sample, CameraSample::pLens
+ * (NULL: 0 for every sample); u_time: one float per sample, CameraSample::time BEFORE the shutter's Lerp (NULL: 0).  GetCameraSample itself is the caller's:
+ * it holds the sampler.  desc is checked as pg_render checks it, on the host and before the device is touched (PG_ERR_INVALID with pg_render's text); of its
+ * fields the camera's, spp, the shutter and camera_medium are used.  mem and stream as pg_intersect_at: host arrays are staged once each way, PG_MEM_DEVICE
+ * pointers are used as given (out 16-byte aligned), and the call synchronises once.  n == 0 returns PG_OK.
+ * PgCounters: lens_rays_total / lens_rays_vignetted move as a frame's camera samples move them (the realistic camera's GenerateRay calls); nothing else moves --
+ * camera_rays neither: no ray was traced.  Not built: Camera::We / Pdf_We / Sample_Wi. */
+int pg_camera_rays_at(PgScene *scene, const PgRenderDesc *desc, int32_t n, const float *p_film, const float *p_lens, const float *u_time,
+                      PgCameraRay *out, int mem, void *stream);
+
+/* pg_scatter_f_at / pg_scatter_sample_at for rays WITH differentials: the BSDF SamplerIntegrator's Li holds after isect.ComputeScatteringFunctions(ray, ...)
+ * for a camera ray -- SurfaceInteraction::ComputeDifferentials (interaction.cpp:101-147) gives every texture its footprint (MIP level, EWA, a checkerboard's
+ * closed-form filter) and Material::Bump its du / dv.  Every argument as in the plain calls; diff: twelve floats per ray in PgCameraRay.differentials' order,
+ * world space, used as given (the rays need not be camera rays); with PG_MEM_DEVICE 16-byte aligned.  A ray WITHOUT differentials hands over twelve zeros
+ * (what pg_camera_rays_at writes beside has_differentials = 0): such a ray's record is the plain call's, byte for byte.  So is every record of a call
+ * with diff == NULL, and of a scene without textured materials (nothing there reads a footprint).  Later vertices of a path pass NULL: PathIntegrator
+ * spawns its rays without differentials.  Differentials after specular bounces (whitted's, directlighting's: they need dndu / dndv, which PgInteraction
+ * does not carry) are not built.  PgCounters as the plain calls. */
+int pg_scatter_f_diff_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                         const float *wi, const float *diff, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
+int pg_scatter_sample_diff_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                              const float *u, const float *diff, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
+
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);
 int pg_scene_set_option(PgScene *scene, int32_t option, int32_t value);

@@ -58,6 +58,10 @@ SUBSURFACE_SAMPLE_DTYPE = np.dtype([("status", np.int32), ("prim", np.int32), ("
                                     ("pdf", np.float32), ("eta", np.float32), ("medium_inside", np.int32), ("medium_outside", np.int32),
                                     ("chain_rays", np.int32), ("reserved", np.float32, 4)])
 
+# one record of pg_camera_rays_at: abi.PgCameraRay field for field (96 bytes); `differentials` is what scatter_f_at / scatter_sample_at take as diff
+CAMERA_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("time", np.float32), ("weight", np.float32), ("medium", np.int32),
+                             ("has_differentials", np.int32), ("reserved", np.float32), ("differentials", np.float32, 12)])
+
 _host = None
 _gpu = None
 
@@ -345,26 +349,73 @@ class GpuScene:
         """pg_intersect_p_at on caller-owned device buffers: n bytes written at occluded_ptr."""
         _check(gpu_lib().pg_intersect_p_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, occluded_ptr, PG_MEM_DEVICE, stream), "pg_intersect_p_at")
 
-    def _scatter(self, name, o, d, tmax, extra, per, time, flags, with_interaction):
+    def _scatter(self, name, o, d, tmax, extra, per, time, flags, with_interaction, diff=None):
         o, d, tmax, time, n = self._rays(o, d, tmax, time)
         extra = np.ascontiguousarray(extra, np.float32)
         if extra.size != per * n:
             raise ValueError(("wi holds three floats" if per == 3 else "u holds two floats") + " per ray")
         out = np.empty(n, SCATTER_DTYPE)
         isect = np.empty(n, INTERACTION_DTYPE) if with_interaction else None
+        args = [extra.ctypes.data]
+        if diff is not None:  # the _diff_ entry points: the differentials follow wi / u
+            diff = np.ascontiguousarray(diff, np.float32)
+            if diff.size != 12 * n:
+                raise ValueError("diff holds twelve floats per ray (PgCameraRay.differentials)")
+            name = name.replace("_at", "_diff_at")
+            args.append(diff.ctypes.data)
         _check(getattr(gpu_lib(), name)(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
-                                        extra.ctypes.data, int(flags), None if isect is None else isect.ctypes.data, out.ctypes.data, PG_MEM_HOST, None), name)
+                                        *args, int(flags), None if isect is None else isect.ctypes.data, out.ctypes.data, PG_MEM_HOST, None), name)
         return (out, isect) if with_interaction else out
 
-    def scatter_f_at(self, o, d, tmax, wi, time=None, flags=31, with_interaction=False):
+    def scatter_f_at(self, o, d, tmax, wi, time=None, flags=31, with_interaction=False, diff=None):
         """Batched BSDF::f and BSDF::Pdf at the rays' closest hits (pg_scatter_f_at) on host arrays: the rays as intersect_at takes them, wi three floats per
         ray (world space, used as given), flags one BxDFType mask (0 .. 31) for all rays.  Returns the records as a structured array of SCATTER_DTYPE, or
-        -- with_interaction -- (records, what intersect_at returns for the same rays) from the one trace."""
-        return self._scatter("pg_scatter_f_at", o, d, tmax, wi, 3, time, flags, with_interaction)
+        -- with_interaction -- (records, what intersect_at returns for the same rays) from the one trace.  diff: the rays' differentials, twelve floats
+        per ray as camera_rays reports them (pg_scatter_f_diff_at: textures are filtered over the footprint ComputeDifferentials finds; twelve zeros =
+        a ray without); None: rays without differentials, the plain call."""
+        return self._scatter("pg_scatter_f_at", o, d, tmax, wi, 3, time, flags, with_interaction, diff)
 
-    def scatter_sample_at(self, o, d, tmax, u, time=None, flags=31, with_interaction=False):
-        """Batched BSDF::Sample_f at the rays' closest hits (pg_scatter_sample_at): as scatter_f_at, with u two floats per ray (Sample_f's Point2f)."""
-        return self._scatter("pg_scatter_sample_at", o, d, tmax, u, 2, time, flags, with_interaction)
+    def scatter_sample_at(self, o, d, tmax, u, time=None, flags=31, with_interaction=False, diff=None):
+        """Batched BSDF::Sample_f at the rays' closest hits (pg_scatter_sample_at, or -- diff -- pg_scatter_sample_diff_at): as scatter_f_at, with u two
+        floats per ray (Sample_f's Point2f)."""
+        return self._scatter("pg_scatter_sample_at", o, d, tmax, u, 2, time, flags, with_interaction, diff)
+
+    def scatter_f_diff_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, diff_ptr, flags, isect_ptr, out_ptr, stream=None):
+        """pg_scatter_f_diff_at on caller-owned device buffers: as scatter_f_at_device, with 12 n floats at diff_ptr (16-byte aligned; None: no differentials)."""
+        _check(gpu_lib().pg_scatter_f_diff_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, diff_ptr, int(flags), isect_ptr, out_ptr, PG_MEM_DEVICE, stream),
+               "pg_scatter_f_diff_at")
+
+    def scatter_sample_diff_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, diff_ptr, flags, isect_ptr, out_ptr, stream=None):
+        """pg_scatter_sample_diff_at on caller-owned device buffers: as scatter_sample_at_device, with 12 n floats at diff_ptr."""
+        _check(gpu_lib().pg_scatter_sample_diff_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, diff_ptr, int(flags), isect_ptr, out_ptr, PG_MEM_DEVICE, stream),
+               "pg_scatter_sample_diff_at")
+
+    def camera_rays(self, rd, p_film, p_lens=None, u_time=None):
+        """Batched Camera::GenerateRayDifferential (pg_camera_rays_at) on host arrays, for the camera rd describes: p_film two floats per sample
+        (CameraSample::pFilm), p_lens two (pLens; None: 0), u_time one (CameraSample::time before the shutter's Lerp; None: 0).  Returns a structured array
+        of CAMERA_RAY_DTYPE: the world-space ray, its time and medium, the sample's weight (0: vignetted, a record of zeros) and the differentials Li
+        receives, scaled by 1 / sqrt(rd.spp)."""
+        p_film = np.ascontiguousarray(p_film, np.float32)
+        n = p_film.size // 2
+        if p_film.size != 2 * n:
+            raise ValueError("p_film holds two floats per sample")
+        if p_lens is not None:
+            p_lens = np.ascontiguousarray(p_lens, np.float32)
+            if p_lens.size != 2 * n:
+                raise ValueError("p_lens holds two floats per sample")
+        if u_time is not None:
+            u_time = np.ascontiguousarray(u_time, np.float32)
+            if u_time.size != n:
+                raise ValueError("u_time holds one float per sample")
+        out = np.empty(n, CAMERA_RAY_DTYPE)
+        _check(gpu_lib().pg_camera_rays_at(self._h, C.byref(rd), n, p_film.ctypes.data, None if p_lens is None else p_lens.ctypes.data,
+                                           None if u_time is None else u_time.ctypes.data, out.ctypes.data, PG_MEM_HOST, None), "pg_camera_rays_at")
+        return out
+
+    def camera_rays_device(self, rd, n, p_film_ptr, p_lens_ptr, u_time_ptr, out_ptr, stream=None):
+        """pg_camera_rays_at on caller-owned device buffers (raw pointers): 2 n floats at p_film_ptr and p_lens_ptr (None: 0), n at u_time_ptr (None: 0); n
+        records of CAMERA_RAY_DTYPE written at out_ptr (16-byte aligned).  Nothing visits the host."""
+        _check(gpu_lib().pg_camera_rays_at(self._h, C.byref(rd), n, p_film_ptr, p_lens_ptr, u_time_ptr, out_ptr, PG_MEM_DEVICE, stream), "pg_camera_rays_at")
 
     def scatter_f_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, flags, isect_ptr, out_ptr, stream=None):
         """pg_scatter_f_at on caller-owned device buffers (raw pointers, as intersect_at_device takes them): 3 n floats at wi_ptr, n records of

@@ -201,6 +201,11 @@ class PgSubsurfaceSample(C.Structure):
                 ("eta", C.c_float), ("medium_inside", C.c_int32), ("medium_outside", C.c_int32), ("chain_rays", C.c_int32), ("reserved", C.c_float * 4)]
 
 
+class PgCameraRay(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("t_max", C.c_float), ("d", C.c_float * 3), ("time", C.c_float), ("weight", C.c_float), ("medium", C.c_int32),
+                ("has_differentials", C.c_int32), ("reserved", C.c_float), ("differentials", C.c_float * 12)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -260,6 +265,11 @@ GPU_SYMBOLS = {
                                           C.c_void_p, C.c_int, C.c_void_p]),
     "pg_subsurface_f_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_subsurface_sample_f_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_camera_rays_at": (C.c_int, [C.c_void_p, C.POINTER(PgRenderDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_scatter_f_diff_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_scatter_sample_diff_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -3,6 +3,7 @@
 // into batches of camera samples that advance one bounce per launch), and the
 // batched Scene::Intersect/IntersectP entry points.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -83,6 +84,8 @@ struct PgScene {
     DeviceBuffer tIn, tInst, tXf, tOut;  // host rays staged, pg_intersect_at's instances and interpolated matrices of the hits, host results staged
     DeviceBuffer mqIn, mqO, mqD, mqCount, mqState, mqIsect;  // the medium queries: host inputs staged, the second queue of the walk, its state by ray, a pass's interactions by entry
     DeviceBuffer ssO[3], ssD[3], ssCount, ssState, ssXf;  // the subsurface queries: the job queue and the two probe queues, the SssState by ray with chain_rays, the chosen hits' matrices
+    DeviceBuffer cqIn, cqOut, cqDiff, cqFrame;  // the camera queries: host samples and records staged, host differentials staged, the call's LensFrame (PG_LENS_FRAME_BYTES)
+    LensFrame cqHead = {};  // ... and what the call uploads into it (kept here: the copy is asynchronous)
     PgCounters counters;
     std::vector<hipEvent_t> events;
     bool hasNullMaterial = false;
@@ -1332,6 +1335,7 @@ struct RayQuery {
     bool sample = false;
     int32_t flags = 0;
     float *le = nullptr;  // pg_light_le_at (at, not anyhit): three floats per ray
+    const float *diff = nullptr;  // pg_scatter_*_diff_at: the rays' differentials, twelve floats per ray (nullptr: rays without)
 };
 // The statistics of one query launch, from the device's totals (tc[0] closest hit, tc[1] any hit) as read after it
 static void countQuery(PgCounters &c, bool anyhit, int n, const TraceCounters *tc, hipEvent_t a, hipEvent_t b) {
@@ -1386,6 +1390,22 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     float *dLe = device ? r.le : (float *)((char *)s->tOut.p + scatterBytes + isectBytes);
     int32_t *dPrim = device ? r.prim : (int32_t *)s->tOut.p;
     float *dT = device ? r.t : (float *)s->tOut.p + n, *dBary = device ? r.bary : (float *)s->tOut.p + 2 * n;
+    // --- a scattering query's differentials (pg_cameraquery.h): read by scenes with textured materials alone -- the rest take the plain kernel --, by ray, through a
+    // LensFrame of this call's in front of `stL`, the way a realistic camera's frame keeps them by slot
+    const float4 *stL = nullptr;
+    if (r.scatter && r.diff && (dsc.hasTextured || dsc.hasNest)) {
+        const float *dDiff = r.diff;
+        if (!device) {
+            HIP_TRY(reserve(s->cqDiff, 12 * sizeof(float) * n));
+            HIP_TRY(hipMemcpyAsync(s->cqDiff.p, r.diff, 12 * sizeof(float) * n, hipMemcpyHostToDevice, stream));
+            dDiff = (const float *)s->cqDiff.p;
+        }
+        HIP_TRY(reserve(s->cqFrame, PG_LENS_FRAME_BYTES));
+        s->cqHead = LensFrame{};
+        s->cqHead.differentials = reinterpret_cast<float4 *>(const_cast<float *>(dDiff));
+        HIP_TRY(hipMemcpyAsync(s->cqFrame.p, &s->cqHead, sizeof(LensFrame), hipMemcpyHostToDevice, stream));
+        stL = reinterpret_cast<const float4 *>((const char *)s->cqFrame.p + PG_LENS_FRAME_BYTES);  // (an address only: nothing is read at or behind it)
+    }
     hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
     HIP_TRY(hipEventRecord(a, stream));
     if (r.anyhit) launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
@@ -1393,7 +1413,8 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     HIP_TRY(hipEventRecord(b, stream));
     if (r.anyhit) launch_occluded_bytes((const int *)s->tOcc.p, device ? r.occluded : (uint8_t *)s->tOut.p, r.n, stream);
     else if (r.at) {
-        if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, dScatter, stream);
+        if (r.scatter && stL) launch_scatter_diff(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, stL, dScatter, stream);
+        else if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, dScatter, stream);
         if (r.out) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dIsect, stream);
         if (r.le) launch_emitted(dsc, q, (const float4 *)s->tHit.p, dLe, stream);
     }
@@ -1447,12 +1468,13 @@ int pg_intersect_p_at(PgScene *s, int32_t n, const float *o, const float *d, con
 }
 // The two scattering queries: pg_intersect_at's call with the BSDF's records beside (or instead of) the interactions
 static int scatterQuery(const char *name, PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *in, bool sample,
-                        int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+                        int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr, const float *diff = nullptr) {
     if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !in || !out))) return setError(PG_ERR_INVALID, "%s: null argument", name);
     if (flags < 0 || flags > 31) return setError(PG_ERR_INVALID, "%s: flags %d is not a BxDFType mask (0 .. 31)", name, flags);
+    if (diff && mem == PG_MEM_DEVICE && ((uintptr_t)diff & 15)) return setError(PG_ERR_INVALID, "%s: diff in device memory must be 16-byte aligned (it is read as float4)", name);
     if (n == 0) return PG_OK;
     RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
-    r.scatter = out; r.scatterIn = in; r.sample = sample; r.flags = flags;
+    r.scatter = out; r.scatterIn = in; r.sample = sample; r.flags = flags; r.diff = diff;
     return withExactFallback(s, [&]() { return rayQuery(s, r); });
 }
 int pg_scatter_f_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *wi, int32_t flags,
@@ -1463,6 +1485,15 @@ int pg_scatter_sample_at(PgScene *s, int32_t n, const float *o, const float *d, 
                          PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
     return scatterQuery("pg_scatter_sample_at", s, n, o, d, tmax, time, u, true, flags, isect, out, mem, streamPtr);
 }
+// The same two for rays with differentials (diff == nullptr: the plain calls)
+int pg_scatter_f_diff_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *wi, const float *diff, int32_t flags,
+                         PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    return scatterQuery("pg_scatter_f_diff_at", s, n, o, d, tmax, time, wi, false, flags, isect, out, mem, streamPtr, diff);
+}
+int pg_scatter_sample_diff_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *u, const float *diff, int32_t flags,
+                              PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    return scatterQuery("pg_scatter_sample_diff_at", s, n, o, d, tmax, time, u, true, flags, isect, out, mem, streamPtr, diff);
+}
 int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *isect, float *Le, int mem,
                    void *streamPtr) {
     if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !Le))) return setError(PG_ERR_INVALID, "pg_light_le_at: null argument");
@@ -1470,6 +1501,55 @@ int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const 
     RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
     r.le = Le;
     return withExactFallback(s, [&]() { return rayQuery(s, r); });
+}
+
+// ---- batched Camera::GenerateRayDifferential (pg_cameraquery.h) ----
+// Check, stage, one launch, copy back, one wait.  The description is checked as a frame's is (pg_check_render_desc) before the device is touched -- first by
+// itself, over facts that grant whatever it asks of a scene (the camera's kind and lens tables index the device's code and need no scene), then against this scene's.
+// The realistic camera's lens block and zeroed statistics go into the call's LensFrame, whose counts are added to the scene's counters as a frame's are
+// (camera_rays excepted: no ray is traced)
+int pg_camera_rays_at(PgScene *s, const PgRenderDesc *rd, int32_t n, const float *pFilm, const float *pLens, const float *uTime, PgCameraRay *out, int mem,
+                      void *streamPtr) {
+    if (!s || !rd || n < 0 || (n > 0 && (!pFilm || !out))) return setError(PG_ERR_INVALID, "pg_camera_rays_at: null argument");
+    if (n == 0) return PG_OK;
+    PgRenderDesc current;
+    rd = pgCurrentRenderDesc(rd, current);
+    std::string err;
+    RenderSceneFacts granted = {INT_MAX, true, true, true, INT_MAX};
+    if (int st = pg_check_render_desc(rd, granted, err)) return setError(st, "%s", err.c_str());
+    const RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
+    if (int st = pg_check_render_desc(rd, facts, err)) return setError(st, "%s", err.c_str());
+    const bool device = mem == PG_MEM_DEVICE;
+    if (device && ((uintptr_t)out & 15)) return setError(PG_ERR_INVALID, "pg_camera_rays_at: out in device memory must be 16-byte aligned (it is written as float4)");
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    const size_t N = (size_t)n;
+    if (!device) {  // pFilm, then pLens and uTime where given
+        HIP_TRY(reserve(s->cqIn, (2 + (pLens ? 2 : 0) + (uTime ? 1 : 0)) * N * sizeof(float)));
+        HIP_TRY(reserve(s->cqOut, N * sizeof(PgCameraRay)));
+        float *in = (float *)s->cqIn.p;
+        HIP_TRY(hipMemcpyAsync(in, pFilm, 2 * N * sizeof(float), hipMemcpyHostToDevice, stream));
+        pFilm = in; in += 2 * N;
+        if (pLens) { HIP_TRY(hipMemcpyAsync(in, pLens, 2 * N * sizeof(float), hipMemcpyHostToDevice, stream)); pLens = in; in += 2 * N; }
+        if (uTime) { HIP_TRY(hipMemcpyAsync(in, uTime, N * sizeof(float), hipMemcpyHostToDevice, stream)); uTime = in; }
+    }
+    PgCameraRay *dOut = device ? out : (PgCameraRay *)s->cqOut.p;
+    LensFrame *lf = nullptr;
+    if (rd->camera_type == 3) {
+        HIP_TRY(reserve(s->cqFrame, PG_LENS_FRAME_BYTES));
+        s->cqHead = LensFrame{};
+        memcpy(&s->cqHead.lens, &rd->n_lens_interfaces, sizeof(PgLensSystem));
+        HIP_TRY(hipMemcpyAsync(s->cqFrame.p, &s->cqHead, sizeof(LensFrame), hipMemcpyHostToDevice, stream));
+        lf = (LensFrame *)s->cqFrame.p;
+    }
+    launch_camera_rays(*rd, lf, pFilm, pLens, uTime, n, dOut, stream);
+    HIP_TRY(hipGetLastError());
+    if (!device) HIP_TRY(hipMemcpyAsync(out, dOut, N * sizeof(PgCameraRay), hipMemcpyDeviceToHost, stream));
+    unsigned long long ls[3] = {0, 0, 0};
+    if (lf) HIP_TRY(hipMemcpyAsync(ls, (const char *)lf + offsetof(LensFrame, stats), sizeof(ls), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
+    s->counters.lens_rays_total += ls[0]; s->counters.lens_rays_vignetted += ls[1];
+    return PG_OK;
 }
 
 // ---- batched Light::Sample_Li + VisibilityTester::Unoccluded, and Light::Pdf_Li, at reference points ----

@@ -535,5 +535,12 @@ void launch_sss_tally(RayQueue q, int *chain, hipStream_t s);
 void launch_sss_emit(const DScene &sc, bool vol, SssState sss, const int *chain, const float *times, PgSubsurfaceSample *out, PgInteraction *pi, hipStream_t s);
 // out[i] = BSDF::f and Pdf (in = wi, three floats) or Sample_f (sample: in = u, two floats) of the SeparableBSSRDFAdapter at pi[i] with eta[i]
 void launch_adapter(const PgInteraction *pi, const float *eta, const float *in, bool sample, int flags, int n, PgScatter *out, hipStream_t s);
+// ---- the camera queries (pg_cameraquery.h)
+// out[i] = Camera::GenerateRayDifferential of the camera of rd for sample i (pFilm: two floats; pLens: two, or nullptr = 0; uTime: one, or nullptr = 0), the
+// differentials scaled by 1 / sqrt(rd.spp).  lf: the call's LensFrame in device memory -- read (its lens block) and written (its statistics) for camera_type 3 alone
+void launch_camera_rays(const PgRenderDesc &rd, LensFrame *lf, const float *pFilm, const float *pLens, const float *uTime, int n, PgCameraRay *out, hipStream_t s);
+// launch_scatter for rays with differentials, in a scene with textured materials or nesting (the caller's test: no other scene reads a footprint): stL is such
+// that lens_frame(stL)->differentials holds three float4 per ray, by ray -- rxOrigin, rxDirection, ryOrigin, ryDirection; twelve zeros = a ray without
+void launch_scatter_diff(const DScene &sc, RayQueue q, const float4 *hits, const float *in, bool sample, int flags, const float4 *stL, PgScatter *out, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif
