@@ -81,10 +81,11 @@ struct PgScene {
     DeviceBuffer qsPend[2], pendList;  // QueueState::pend of the two main queues; PendJoin::list
     // test-path buffers
     DeviceBuffer tO, tD, tCount, tHit, tT, tOcc;  // the test queue; a closest-hit launch's records and t, an any-hit launch's answers
-    DeviceBuffer tIn, tInst, tXf, tOut;  // host rays staged, pg_intersect_at's instances and interpolated matrices of the hits, host results staged
-    DeviceBuffer mqIn, mqO, mqD, mqCount, mqState, mqIsect;  // the medium queries: host inputs staged, the second queue of the walk, its state by ray, a pass's interactions by entry
+    DeviceBuffer stageIn, stageOut;  // the queries' host arrays staged, one arena per direction (Staging)
+    DeviceBuffer tInst, tXf;  // pg_intersect_at's instances and interpolated matrices of the hits (queryScene)
+    DeviceBuffer mqO, mqD, mqCount, mqState, mqIsect;  // the medium queries: the second queue of the walk, its state by ray, a pass's interactions by entry
     DeviceBuffer ssO[3], ssD[3], ssCount, ssState, ssXf;  // the subsurface queries: the job queue and the two probe queues, the SssState by ray with chain_rays, the chosen hits' matrices
-    DeviceBuffer cqIn, cqOut, cqDiff, cqFrame;  // the camera queries: host samples and records staged, host differentials staged, the call's LensFrame (PG_LENS_FRAME_BYTES)
+    DeviceBuffer cqFrame;  // the camera queries and a scattering query's differentials: the call's LensFrame (PG_LENS_FRAME_BYTES)
     LensFrame cqHead = {};  // ... and what the call uploads into it (kept here: the copy is asynchronous)
     PgCounters counters;
     std::vector<hipEvent_t> events;
@@ -465,12 +466,12 @@ static int readCounts(FrameCtx &c) {
     HIP_TRY(hipStreamSynchronize(c.stream));
     return PG_OK;
 }
-// one queue's counters on the device -> its size
-static int regionSum(FrameCtx &c, const int *dev, uint64_t &total) {
-    int jb[QSTRIDE];
-    HIP_TRY(hipMemcpyAsync(jb, dev, QSTRIDE * sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    total = queueTotal(jb, 0);
+// one queue's counters on the device -> its size (one wait)
+static int queueSize(hipStream_t stream, const int *deviceCounts, uint64_t &total) {
+    int blk[QSTRIDE];
+    HIP_TRY(hipMemcpyAsync(blk, deviceCounts, sizeof(blk), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    total = queueTotal(blk, 0);
     return PG_OK;
 }
 // PgCounters::shading_modes: which k_shade<MODE> this frame's shading launches are (pg_shade_mode, the launch functions' own choice)
@@ -508,26 +509,33 @@ static int startBatch(FrameCtx &c, const std::function<void()> &generate) {
     HIP_TRY(hipMemsetAsync(c.counts, 0, 4 * QSTRIDE * sizeof(int), c.stream));
     return c.timer.run(4, c.stream, generate);
 }
-// The probe chains of SeparableBSSRDF::Sample_Sp for the nJobs paths k_shade handed over (c.sq.qjob), walked twice through the
-// traversal kernel: pass 1 counts the hits on the material, pass 2 stops at the chosen one.  One counter read-back per step.  `d`
-// says where the probe rays' instances go, `hits` where their hits go; vol: the volpath variant of k_sss_probe.
-static int sssProbeChains(FrameCtx &c, const DScene &d, float4 *hits, uint64_t nJobs, bool vol) {
+// The probe chains of SeparableBSSRDF::Sample_Sp for the nJobs entries of the job queue sq.qjob, walked twice through the traversal kernel over the
+// two probe queues: pass 1 counts the hits on the material, pass 2 stops at the chosen one.  One counter read-back per step.  `d` says where the
+// probe rays' instances go, `hits` where their hits go; vol: the volpath variant of k_sss_probe.  The first walk's launches count into cn and the
+// caller accounts for each of its steps in firstWalkStep(queue, rays), between the step's two launches; the second walk repeats queries the reference
+// makes once: its traversal work goes to cn + 2 and its rays are not counted.  `entry`: the entry point that runs, for the error text
+template <class F> static int sssProbeChains(const char *entry, PgScene *s, const DScene &d, const SssState &sq, const RayQueue probe[2], float4 *hits, TraceCounters *cn,
+                                             uint64_t nJobs, bool vol, hipStream_t stream, F &&firstWalkStep) {
     for (int pass = 1; pass <= 2; ++pass) {
-        RayQueue curQ = c.sq.qjob;
+        RayQueue curQ = sq.qjob;
         uint64_t nRays = nJobs;
         for (int step = 0; nRays > 0; ++step) {
-            if (step > 1000000) return setError(PG_ERR_DEVICE, "pg_render: a BSSRDF probe chain did not terminate");
-            RayQueue outQ = c.sssP[step & 1];
-            HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), c.stream));
-            // the second walk repeats queries the reference makes once: its rays and traversal work are not counted
-            launch_closest(d, c.s->trace, curQ, hits, nullptr, pass == 1 ? c.cnClosest : c.cnClosest + 2, c.cursors, c.cullGuard, c.stream);
-            if (pass == 1) { c.closestRays += nRays; ++c.closestLaunches; }
-            launch_sss_probe(d, c.sq, pass, curQ, hits, outQ, c.stream, vol, vol && step == 0);
-            if (int e = regionSum(c, outQ.counts, nRays)) return e;
+            if (step > 1000000) return setError(PG_ERR_DEVICE, "%s: a BSSRDF probe chain did not terminate", entry);
+            RayQueue outQ = probe[step & 1];
+            HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), stream));
+            launch_closest(d, s->trace, curQ, hits, nullptr, pass == 1 ? cn : cn + 2, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+            if (pass == 1) firstWalkStep(curQ, nRays);
+            launch_sss_probe(d, sq, pass, curQ, hits, outQ, stream, vol, vol && step == 0);
+            if (int e = queueSize(stream, outQ.counts, nRays)) return e;
             curQ = outQ;
         }
     }
     return PG_OK;
+}
+// ... for the paths k_shade handed over (c.sq.qjob)
+static int sssProbeChains(FrameCtx &c, const DScene &d, float4 *hits, uint64_t nJobs, bool vol) {
+    return sssProbeChains("pg_render", c.s, d, c.sq, c.sssP, hits, c.cnClosest, nJobs, vol, c.stream,
+                          [&c](const RayQueue &, uint64_t nRays) { c.closestRays += nRays; ++c.closestLaunches; });
 }
 
 // volpath's through rays: kind 0 = light samples (q[2] <-> vq[0]), kind 1 = BSDF / phase samples (q[3] <-> vq[1]), re-traced
@@ -627,7 +635,7 @@ static int bouncesVolpath(FrameCtx &c, const std::function<void()> &generate, co
             // vertices, their transmittance rays and resolve; the exit vertices' next rays join q[nxt], which is
             // traced as a whole at the start of the next iteration
             uint64_t nJobs = 0;
-            if (int e = regionSum(c, c.sq.qjob.counts, nJobs)) return e;
+            if (int e = queueSize(c.stream, c.sq.qjob.counts, nJobs)) return e;
             if (nJobs > 0) {
                 if (int e = sssProbeChains(c, dv, c.hits, nJobs, true)) return e;
                 HIP_TRY(hipMemsetAsync(c.counts + 2 * QSTRIDE, 0, 2 * QSTRIDE * sizeof(int), stream));
@@ -709,7 +717,7 @@ static int bouncesPath(FrameCtx &c, const std::function<void()> &generate, const
             // vertices: their shadow / MIS rays, the tail of the next bounce's queue that their next rays form, and the resolve of
             // their direct lighting.
             uint64_t nJobs = 0;
-            if (int e = regionSum(c, c.sq.qjob.counts, nJobs)) return e;
+            if (int e = queueSize(c.stream, c.sq.qjob.counts, nJobs)) return e;
             if (nJobs > 0) {
                 const size_t n1 = (size_t)q[0].regionCap * PG_REGIONS;
                 DScene dprobe = c.d;  // the probe rays' hits go where the MIS rays' went (k_resolve is done with those)
@@ -727,8 +735,8 @@ static int bouncesPath(FrameCtx &c, const std::function<void()> &generate, const
                 launch_resolve(c.d, c.ps, c.sq.qjob, q[3], (const int *)s->occluded.p, c.hitsMis, stream, cur);
                 ++c.resolveLaunches;
                 uint64_t nSh = 0, nMis = 0;
-                if (int e = regionSum(c, c.counts + 2 * QSTRIDE, nSh)) return e;
-                if (int e = regionSum(c, c.counts + 3 * QSTRIDE, nMis)) return e;
+                if (int e = queueSize(c.stream, c.counts + 2 * QSTRIDE, nSh)) return e;
+                if (int e = queueSize(c.stream, c.counts + 3 * QSTRIDE, nMis)) return e;
                 c.shadowRays += nSh; c.closestRays += nMis; c.misRays += nMis;  // (the next rays are counted with the next bounce's queue)
             }
         }
@@ -1284,38 +1292,134 @@ int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *des
     return PG_OK;
 }
 
-// ---- batched Scene::Intersect / IntersectP -------------------------------------------
+// ---- the batched queries --------------------------------------------------------------
 // pg_intersect / pg_intersect_p (rays at time 0; primitive, t and barycentrics), pg_intersect_at / pg_intersect_p_at (Ray::time; the
 // SurfaceInteraction, pg_interaction.h), pg_scatter_f_at / pg_scatter_sample_at (the BSDF at the closest hit, pg_scatter.h) and pg_light_le_at (the
-// radiance the ray meets, pg_lightquery.h) are one device path, rayQuery: pack, trace, emit, account, one wait.  The two light queries that take
-// reference points instead of rays, pg_light_sample_at / pg_light_pdf_at, are lightQuery below.
-// The test-path buffers only grow: DeviceBuffer::alloc frees first, and hipFree waits for the device
+// radiance the ray meets, pg_lightquery.h) are one device path, rayQuery: pack, trace, emit, account, one wait.  The other families have a driver each:
+// lightQuery (reference points instead of rays), mediumQuery, subsurfaceQuery with adapterQuery, and pg_camera_rays_at.  What the drivers share is
+// stated once, in front of them:
+//   checkArgs    the entry points' refusals
+//   Staging      a call's host arrays <-> the scene's two staging arenas
+//   queryScene   the scene as pg_intersect_at's launch sees it
+//   queueOver    a RayQueue over grow-only buffers (testQueue: the test queue; packRays: ... with the call's rays in it)
+//   finishQuery  the call's one wait, its counters, the cull guard
+// and, with the renderer, queueSize and sssProbeChains above.
+// The queries' buffers only grow: DeviceBuffer::alloc frees first, and hipFree waits for the device
 static hipError_t reserve(DeviceBuffer &b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes); }
-// The rays into the test queue ON the device (k_pack_rays), their times behind `d` in PG_QUEUE_TIMES's layout -- for every scene: a still scene's
-// k_trace does not read them, the records report them.  Host rays are staged in tIn; the caller's arrays must outlive the stream's work, which the
-// entry points wait for before they return.  `extra`: a scattering query's per-ray input (extraPer floats per ray: wi or u), staged behind the rays
-static int packRays(PgScene *s, int n, const float *o, const float *d, const float *tmax, const float *time, const float *&extra, int extraPer, int mem,
-                    hipStream_t stream, RayQueue &q, float *&times) {
-    const size_t N = (size_t)regionCapFor(n) * PG_REGIONS;
-    HIP_TRY(reserve(s->tO, N * sizeof(float4)));
-    HIP_TRY(reserve(s->tD, N * (sizeof(float4) + sizeof(float))));
-    HIP_TRY(reserve(s->tCount, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));
-    if (mem != PG_MEM_DEVICE) {
-        const size_t n3 = 3 * (size_t)n;
-        HIP_TRY(reserve(s->tIn, (2 * n3 + (2 + (size_t)extraPer) * (size_t)n) * sizeof(float)));
-        float *in = (float *)s->tIn.p;
-        HIP_TRY(hipMemcpyAsync(in, o, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(in + n3, d, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(in + 2 * n3, tmax, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (time) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + n, time, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (extra) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + 2 * (size_t)n, extra, (size_t)extraPer * (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
-        o = in; d = in + n3; tmax = in + 2 * n3; time = time ? in + 2 * n3 + n : nullptr;
-        if (extra) extra = in + 2 * n3 + 2 * (size_t)n;
+
+// The refusals, in this order: no scene, n < 0 or -- of a call with work to do -- a required array missing; `flags` that are no BxDFType mask (the
+// scattering calls pass theirs).  n == 0 is the caller's to return PG_OK for, before anything is dereferenced or the device is touched
+static int checkArgs(const char *name, const PgScene *s, int32_t n, std::initializer_list<const void *> required, int32_t flags = 0) {
+    bool refused = !s || n < 0;
+    if (n > 0) for (const void *p : required) refused = refused || !p;
+    if (refused) return setError(PG_ERR_INVALID, "%s: null argument", name);
+    if (flags < 0 || flags > 31) return setError(PG_ERR_INVALID, "%s: flags %d is not a BxDFType mask (0 .. 31)", name, flags);
+    return PG_OK;
+}
+
+extern "C++" {  // (templates)
+// A call's arrays in the caller's memory and what the kernels use in their place.  The driver declares its inputs and outputs -- in() / out(): its
+// pointer variable and the array's element count; an array that is not given (nullptr) takes no part -- and upload() re-aims the declared variables.
+// PG_MEM_DEVICE: nothing is declared or copied, the kernels read and write the caller's arrays.  Otherwise each array gets a slot on a 16-byte boundary
+// (PgInteraction, PgCameraRay and the differentials are read or written as float4) of PgScene::stageIn or stageOut, upload() enqueues the inputs'
+// copies and download() the results'; the host arrays must outlive the stream's work, which the entry points wait for before they return.
+// Both arenas are grown for the whole call before its first copy is enqueued: growing frees the old block, which no work of this call may be using.
+struct Staging {
+    PgScene *s; hipStream_t stream; bool device;
+    struct Slot { void *var, *host; size_t bytes, offset; };  // (var: the driver's pointer variable)
+    std::vector<Slot> ins, outs;
+    size_t inBytes = 0, outBytes = 0;
+    Staging(PgScene *s, int mem, hipStream_t stream) : s(s), stream(stream), device(mem == PG_MEM_DEVICE) {}
+    static void add(std::vector<Slot> &slots, size_t &total, void *var, void *host, size_t bytes) {
+        slots.push_back({var, host, bytes, total});
+        total += (bytes + 15) & ~(size_t)15;
     }
-    q.o = (float4 *)s->tO.p; q.d = (float4 *)s->tD.p; q.counts = (int *)s->tCount.p; q.regionCap = regionCapFor(n);
+    template <class T> void in(const T *&p, size_t count) {
+        if (device || !p) return;
+        if (count) add(ins, inBytes, &p, const_cast<T *>(p), count * sizeof(T));
+        else p = nullptr;  // (draws of a call with n_u = 0: nothing to read)
+    }
+    template <class T> void out(T *&p, size_t count) { if (!device && p) add(outs, outBytes, &p, p, count * sizeof(T)); }
+    // o, d (three floats per ray), tmax and -- where given -- time
+    void rays(const float *&o, const float *&d, const float *&tmax, const float *&time, size_t n) { in(o, 3 * n); in(d, 3 * n); in(tmax, n); in(time, n); }
+    int upload() {
+        HIP_TRY(reserve(s->stageIn, inBytes));
+        HIP_TRY(reserve(s->stageOut, outBytes));
+        for (const Slot &t : ins) {
+            void *dev = (char *)s->stageIn.p + t.offset;
+            HIP_TRY(hipMemcpyAsync(dev, t.host, t.bytes, hipMemcpyHostToDevice, stream));
+            memcpy(t.var, &dev, sizeof(dev));
+        }
+        for (const Slot &t : outs) {
+            void *dev = (char *)s->stageOut.p + t.offset;
+            memcpy(t.var, &dev, sizeof(dev));
+        }
+        return PG_OK;
+    }
+    int download() {
+        for (const Slot &t : outs) HIP_TRY(hipMemcpyAsync(t.host, (char *)s->stageOut.p + t.offset, t.bytes, hipMemcpyDeviceToHost, stream));
+        return PG_OK;
+    }
+};
+}  // extern "C++"
+
+// The scene as pg_intersect_at's launch sees it -- as a frame's: the hits' instances, a moving one's matrices at the ray's time -- over the queries' own
+// records for `entries` hits.  dsc: a copy of s->d
+static int queryScene(PgScene *s, size_t entries, DScene &dsc) {
+    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
+    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * entries)); dsc.hitInst = (int *)s->tInst.p; }
+    if (dsc.hasMotion) {
+        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * entries * PG_XF_STRIDE * sizeof(float)));  // (hasNest: a second half for the inner transform)
+        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = (int)entries;
+    }
+    return PG_OK;
+}
+// A queue of PG_REGIONS regions of `cap` entries over the buffers o and d with the counter block `counts`, its rays' times behind `d` in
+// PG_QUEUE_TIMES's layout -- for every scene: a still scene's k_trace does not read them, the records report them
+static int queueOver(DeviceBuffer &o, DeviceBuffer &d, int *counts, int cap, RayQueue &q, float *&times) {
+    const size_t N = (size_t)cap * PG_REGIONS;
+    HIP_TRY(reserve(o, N * sizeof(float4)));
+    HIP_TRY(reserve(d, N * (sizeof(float4) + sizeof(float))));
+    q.o = (float4 *)o.p; q.d = (float4 *)d.p; q.counts = counts; q.regionCap = cap;
     times = reinterpret_cast<float *>(q.d + N);
+    return PG_OK;
+}
+static int testQueue(PgScene *s, int cap, RayQueue &q, float *&times) {
+    HIP_TRY(reserve(s->tCount, QSTRIDE * sizeof(int)));
+    return queueOver(s->tO, s->tD, (int *)s->tCount.p, cap, q, times);
+}
+// The rays (in device memory: staged by the driver) into the test queue ON the device (k_pack_rays): ray i at entry i
+static int packRays(PgScene *s, int n, const float *o, const float *d, const float *tmax, const float *time, hipStream_t stream, RayQueue &q, float *&times) {
+    if (int e = testQueue(s, regionCapFor(n), q, times)) return e;
     launch_pack_rays(o, d, tmax, time, n, q, times, stream);
     return PG_OK;
+}
+// The end of a call that traced.  Behind the call's work it reads the device's trace totals (tc[0] closest hit, tc[1] any hit), a closest-hit call's
+// cull guard -- only such a launch can raise it, and it decides whether the results stand -- and, rayCounts != nullptr, that queue's counters: its size
+// is then the number of rays (pg_light_sample_at: the sample kernel chose the rays to test).  The call's one wait (the walks' per-pass waits aside);
+// then the call's rays and launches join the scene's counters, with the totals of a call that launched and the time between the events a and b of a
+// driver that recorded them around its one launch
+static int finishQuery(PgScene *s, hipStream_t stream, bool anyhit, uint64_t rays, uint64_t launches, hipEvent_t a = nullptr, hipEvent_t b = nullptr,
+                       const int *rayCounts = nullptr) {
+    TraceCounters tc[2];
+    int guard = 0, blk[QSTRIDE];
+    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
+    if (!anyhit) HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (rayCounts) HIP_TRY(hipMemcpyAsync(blk, rayCounts, sizeof(blk), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (rayCounts) rays = queueTotal(blk, 0);
+    PgCounters &c = s->counters;
+    (anyhit ? c.shadow_rays : c.closest_rays) += rays;
+    (anyhit ? c.shadow_launches : c.closest_launches) += launches;
+    if (launches) {
+        (anyhit ? c.shadow_node_visits : c.closest_node_visits) = tc[anyhit].node_visits;
+        (anyhit ? c.shadow_tri_tests : c.closest_tri_tests) = tc[anyhit].tri_tests;
+        c.node_visits = tc[0].node_visits + tc[1].node_visits;
+        c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
+    }
+    float ms = 0;
+    if (a && hipEventElapsedTime(&ms, a, b) == hipSuccess) (anyhit ? c.shadow_ms : c.closest_ms) += ms;
+    return cullGuardStatus(s, guard);
 }
 
 // One call of the seven entry points: the rays, and the caller's arrays (in `mem`) of the kind of result it asks for
@@ -1337,72 +1441,44 @@ struct RayQuery {
     float *le = nullptr;  // pg_light_le_at (at, not anyhit): three floats per ray
     const float *diff = nullptr;  // pg_scatter_*_diff_at: the rays' differentials, twelve floats per ray (nullptr: rays without)
 };
-// The statistics of one query launch, from the device's totals (tc[0] closest hit, tc[1] any hit) as read after it
-static void countQuery(PgCounters &c, bool anyhit, int n, const TraceCounters *tc, hipEvent_t a, hipEvent_t b) {
-    (anyhit ? c.shadow_rays : c.closest_rays) += (uint64_t)n;
-    (anyhit ? c.shadow_node_visits : c.closest_node_visits) = tc[anyhit].node_visits;
-    (anyhit ? c.shadow_tri_tests : c.closest_tri_tests) = tc[anyhit].tri_tests;
-    c.node_visits = tc[0].node_visits + tc[1].node_visits;
-    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    (anyhit ? c.shadow_launches : c.closest_launches) += 1;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) (anyhit ? c.shadow_ms : c.closest_ms) += ms;
-}
-static int rayQuery(PgScene *s, const RayQuery &r) {
+static int rayQuery(PgScene *s, RayQuery r) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)r.stream;
     const size_t n = (size_t)r.n;
-    const bool device = r.mem == PG_MEM_DEVICE;
+    // (a scattering query's differentials, pg_cameraquery.h, are read by scenes with textured materials or nesting alone: the rest take the plain kernel)
+    if (!s->d.hasTextured && !s->d.hasNest) r.diff = nullptr;
+    Staging stage(s, r.mem, stream);
+    stage.rays(r.o, r.d, r.tmax, r.time, n);
+    stage.in(r.scatterIn, (r.sample ? 2 : 3) * n);
+    stage.in(r.diff, 12 * n);
+    stage.out(r.scatter, n); stage.out(r.out, n); stage.out(r.le, 3 * n);
+    stage.out(r.prim, n); stage.out(r.t, n); stage.out(r.bary, 3 * n);
+    stage.out(r.occluded, n);
+    if (int e = stage.upload()) return e;
     RayQueue q;
     float *times = nullptr;
-    const float *scatterIn = r.scatterIn;
-    if (int st = packRays(s, r.n, r.o, r.d, r.tmax, r.time, scatterIn, !r.scatter ? 0 : r.sample ? 2 : 3, r.mem, stream, q, times)) return st;
+    if (int e = packRays(s, r.n, r.o, r.d, r.tmax, r.time, stream, q, times)) return e;
     // --- the scene and the tunables the launch sees, per entry point:
     //   pg_intersect       no instance or matrix records (primitive, t and barycentrics are all it reports); rays at time 0
     //   pg_intersect_p     rays at time 0 (an any-hit launch touches neither record)
-    //   pg_intersect_at    as a frame's launch -- the hits' instances, a moving one's matrices at the ray's time -- over this call's own buffers
+    //   pg_intersect_at    queryScene, the records by ray
     //   pg_scatter_*_at, pg_light_le_at  as pg_intersect_at
     //   pg_intersect_p_at  no records; the rays' times as the scene has them
     // any hit: in the reference's visiting order, so that the counters are the reference's (tests compare them)
     DScene dsc = s->d;
     TraceConfig cfg = s->trace;
     if (!r.at) dsc.rayTimes = 0;
-    if (r.at || !r.anyhit) { dsc.hitInst = nullptr; dsc.animXf = nullptr; }
     if (r.anyhit) cfg.anyhitFree = 0;
-    if (r.at && !r.anyhit) {
-        dsc.nestXfOff = 0;
-        if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * n)); dsc.hitInst = (int *)s->tInst.p; }
-        if (dsc.hasMotion) {
-            HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * n * PG_XF_STRIDE * sizeof(float)));  // (hasNest: a second half for the inner transform)
-            dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = r.n;
-        }
-    }
+    if (r.at && !r.anyhit) { if (int e = queryScene(s, n, dsc)) return e; }
+    else { dsc.hitInst = nullptr; dsc.animXf = nullptr; }
     if (r.anyhit) HIP_TRY(reserve(s->tOcc, sizeof(int) * n));
     else { HIP_TRY(reserve(s->tHit, sizeof(float4) * n)); HIP_TRY(reserve(s->tT, sizeof(float) * n)); }
-    // --- the results: PG_MEM_DEVICE: the kernels write the caller's arrays; otherwise into tOut, copied to the caller below
-    // (a scattering query: the PgScatter records first, the interactions it was asked for behind them; pg_light_le_at: interactions, then Le)
-    const size_t scatterBytes = r.scatter ? sizeof(PgScatter) * n : 0, isectBytes = r.at && !r.anyhit && r.out ? sizeof(PgInteraction) * n : 0;
-    const size_t leBytes = r.le ? 3 * sizeof(float) * n : 0;
-    const size_t outBytes = r.anyhit ? n : r.at ? scatterBytes + isectBytes + leBytes : 5 * sizeof(float) * n;  // (pg_intersect: prim, t, three barycentrics)
-    if (!device) HIP_TRY(reserve(s->tOut, outBytes));
-    PgScatter *dScatter = device ? r.scatter : (PgScatter *)s->tOut.p;
-    PgInteraction *dIsect = device ? r.out : (PgInteraction *)((char *)s->tOut.p + scatterBytes);
-    float *dLe = device ? r.le : (float *)((char *)s->tOut.p + scatterBytes + isectBytes);
-    int32_t *dPrim = device ? r.prim : (int32_t *)s->tOut.p;
-    float *dT = device ? r.t : (float *)s->tOut.p + n, *dBary = device ? r.bary : (float *)s->tOut.p + 2 * n;
-    // --- a scattering query's differentials (pg_cameraquery.h): read by scenes with textured materials alone -- the rest take the plain kernel --, by ray, through a
-    // LensFrame of this call's in front of `stL`, the way a realistic camera's frame keeps them by slot
+    // --- the differentials reach k_scatter_diff by ray, through a LensFrame of this call's in front of `stL`, the way a realistic camera's frame keeps them by slot
     const float4 *stL = nullptr;
-    if (r.scatter && r.diff && (dsc.hasTextured || dsc.hasNest)) {
-        const float *dDiff = r.diff;
-        if (!device) {
-            HIP_TRY(reserve(s->cqDiff, 12 * sizeof(float) * n));
-            HIP_TRY(hipMemcpyAsync(s->cqDiff.p, r.diff, 12 * sizeof(float) * n, hipMemcpyHostToDevice, stream));
-            dDiff = (const float *)s->cqDiff.p;
-        }
+    if (r.diff) {
         HIP_TRY(reserve(s->cqFrame, PG_LENS_FRAME_BYTES));
         s->cqHead = LensFrame{};
-        s->cqHead.differentials = reinterpret_cast<float4 *>(const_cast<float *>(dDiff));
+        s->cqHead.differentials = reinterpret_cast<float4 *>(const_cast<float *>(r.diff));
         HIP_TRY(hipMemcpyAsync(s->cqFrame.p, &s->cqHead, sizeof(LensFrame), hipMemcpyHostToDevice, stream));
         stL = reinterpret_cast<const float4 *>((const char *)s->cqFrame.p + PG_LENS_FRAME_BYTES);  // (an address only: nothing is read at or behind it)
     }
@@ -1411,66 +1487,48 @@ static int rayQuery(PgScene *s, const RayQuery &r) {
     if (r.anyhit) launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
     else launch_closest(dsc, cfg, q, (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
     HIP_TRY(hipEventRecord(b, stream));
-    if (r.anyhit) launch_occluded_bytes((const int *)s->tOcc.p, device ? r.occluded : (uint8_t *)s->tOut.p, r.n, stream);
+    if (r.anyhit) launch_occluded_bytes((const int *)s->tOcc.p, r.occluded, r.n, stream);
     else if (r.at) {
-        if (r.scatter && stL) launch_scatter_diff(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, stL, dScatter, stream);
-        else if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, scatterIn, r.sample, r.flags, dScatter, stream);
-        if (r.out) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dIsect, stream);
-        if (r.le) launch_emitted(dsc, q, (const float4 *)s->tHit.p, dLe, stream);
+        if (r.scatter && stL) launch_scatter_diff(dsc, q, (const float4 *)s->tHit.p, r.scatterIn, r.sample, r.flags, stL, r.scatter, stream);
+        else if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, r.scatterIn, r.sample, r.flags, r.scatter, stream);
+        if (r.out) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, r.out, stream);
+        if (r.le) launch_emitted(dsc, q, (const float4 *)s->tHit.p, r.le, stream);
     }
-    else launch_hit_arrays((const float4 *)s->tHit.p, (const float *)s->tT.p, dPrim, dT, dBary, r.n, stream);
+    else launch_hit_arrays((const float4 *)s->tHit.p, (const float *)s->tT.p, r.prim, r.t, r.bary, r.n, stream);
     HIP_TRY(hipGetLastError());
-    if (!device) {
-        if (r.anyhit) HIP_TRY(hipMemcpyAsync(r.occluded, s->tOut.p, outBytes, hipMemcpyDeviceToHost, stream));
-        else if (r.at) {
-            if (r.scatter) HIP_TRY(hipMemcpyAsync(r.scatter, dScatter, scatterBytes, hipMemcpyDeviceToHost, stream));
-            if (r.out) HIP_TRY(hipMemcpyAsync(r.out, dIsect, isectBytes, hipMemcpyDeviceToHost, stream));
-            if (r.le) HIP_TRY(hipMemcpyAsync(r.le, dLe, leBytes, hipMemcpyDeviceToHost, stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(r.prim, dPrim, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(r.t, dT, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(r.bary, dBary, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, stream));
-        }
-    }
-    TraceCounters tc[2];
-    int guard = 0;  // (only a closest-hit launch can raise it)
-    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
-    if (!r.anyhit) HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait: the cull guard decides whether the results stand
-    countQuery(s->counters, r.anyhit, r.n, tc, a, b);
-    return cullGuardStatus(s, guard);
+    if (int e = stage.download()) return e;
+    return finishQuery(s, stream, r.anyhit, n, 1, a, b);
 }
 
 int pg_intersect(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, int32_t *prim, float *t, float *bary, int mem,
                  void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !prim || !t || !bary))) return setError(PG_ERR_INVALID, "pg_intersect: null argument");
+    if (int e = checkArgs("pg_intersect", s, n, {o, d, tmax, prim, t, bary})) return e;
     if (n == 0) return PG_OK;
     const RayQuery r = {n, o, d, tmax, nullptr, false, false, prim, t, bary, nullptr, nullptr, mem, streamPtr};
     return withExactFallback(s, [&]() { return rayQuery(s, r); });
 }
 int pg_intersect_p(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, uint8_t *occluded, int mem, void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p: null argument");
+    if (int e = checkArgs("pg_intersect_p", s, n, {o, d, tmax, occluded})) return e;
     if (n == 0) return PG_OK;
     return rayQuery(s, {n, o, d, tmax, nullptr, true, false, nullptr, nullptr, nullptr, nullptr, occluded, mem, streamPtr});
 }
 int pg_intersect_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *out, int mem,
                     void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !out))) return setError(PG_ERR_INVALID, "pg_intersect_at: null argument");
+    if (int e = checkArgs("pg_intersect_at", s, n, {o, d, tmax, out})) return e;
     if (n == 0) return PG_OK;
     const RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, out, nullptr, mem, streamPtr};
     return withExactFallback(s, [&]() { return rayQuery(s, r); });
 }
 int pg_intersect_p_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, uint8_t *occluded, int mem,
                       void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !occluded))) return setError(PG_ERR_INVALID, "pg_intersect_p_at: null argument");
+    if (int e = checkArgs("pg_intersect_p_at", s, n, {o, d, tmax, occluded})) return e;
     if (n == 0) return PG_OK;
     return rayQuery(s, {n, o, d, tmax, time, true, true, nullptr, nullptr, nullptr, nullptr, occluded, mem, streamPtr});
 }
 // The two scattering queries: pg_intersect_at's call with the BSDF's records beside (or instead of) the interactions
 static int scatterQuery(const char *name, PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *in, bool sample,
                         int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr, const float *diff = nullptr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !in || !out))) return setError(PG_ERR_INVALID, "%s: null argument", name);
-    if (flags < 0 || flags > 31) return setError(PG_ERR_INVALID, "%s: flags %d is not a BxDFType mask (0 .. 31)", name, flags);
+    if (int e = checkArgs(name, s, n, {o, d, tmax, in, out}, flags)) return e;
     if (diff && mem == PG_MEM_DEVICE && ((uintptr_t)diff & 15)) return setError(PG_ERR_INVALID, "%s: diff in device memory must be 16-byte aligned (it is read as float4)", name);
     if (n == 0) return PG_OK;
     RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
@@ -1496,7 +1554,7 @@ int pg_scatter_sample_diff_at(PgScene *s, int32_t n, const float *o, const float
 }
 int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *isect, float *Le, int mem,
                    void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !Le))) return setError(PG_ERR_INVALID, "pg_light_le_at: null argument");
+    if (int e = checkArgs("pg_light_le_at", s, n, {o, d, tmax, Le})) return e;
     if (n == 0) return PG_OK;
     RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
     r.le = Le;
@@ -1510,7 +1568,7 @@ int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const 
 // (camera_rays excepted: no ray is traced)
 int pg_camera_rays_at(PgScene *s, const PgRenderDesc *rd, int32_t n, const float *pFilm, const float *pLens, const float *uTime, PgCameraRay *out, int mem,
                       void *streamPtr) {
-    if (!s || !rd || n < 0 || (n > 0 && (!pFilm || !out))) return setError(PG_ERR_INVALID, "pg_camera_rays_at: null argument");
+    if (int e = checkArgs("pg_camera_rays_at", rd ? s : nullptr, n, {pFilm, out})) return e;  // (the description is required as the scene is, whatever n)
     if (n == 0) return PG_OK;
     PgRenderDesc current;
     rd = pgCurrentRenderDesc(rd, current);
@@ -1519,21 +1577,14 @@ int pg_camera_rays_at(PgScene *s, const PgRenderDesc *rd, int32_t n, const float
     if (int st = pg_check_render_desc(rd, granted, err)) return setError(st, "%s", err.c_str());
     const RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
     if (int st = pg_check_render_desc(rd, facts, err)) return setError(st, "%s", err.c_str());
-    const bool device = mem == PG_MEM_DEVICE;
-    if (device && ((uintptr_t)out & 15)) return setError(PG_ERR_INVALID, "pg_camera_rays_at: out in device memory must be 16-byte aligned (it is written as float4)");
+    if (mem == PG_MEM_DEVICE && ((uintptr_t)out & 15)) return setError(PG_ERR_INVALID, "pg_camera_rays_at: out in device memory must be 16-byte aligned (it is written as float4)");
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)streamPtr;
     const size_t N = (size_t)n;
-    if (!device) {  // pFilm, then pLens and uTime where given
-        HIP_TRY(reserve(s->cqIn, (2 + (pLens ? 2 : 0) + (uTime ? 1 : 0)) * N * sizeof(float)));
-        HIP_TRY(reserve(s->cqOut, N * sizeof(PgCameraRay)));
-        float *in = (float *)s->cqIn.p;
-        HIP_TRY(hipMemcpyAsync(in, pFilm, 2 * N * sizeof(float), hipMemcpyHostToDevice, stream));
-        pFilm = in; in += 2 * N;
-        if (pLens) { HIP_TRY(hipMemcpyAsync(in, pLens, 2 * N * sizeof(float), hipMemcpyHostToDevice, stream)); pLens = in; in += 2 * N; }
-        if (uTime) { HIP_TRY(hipMemcpyAsync(in, uTime, N * sizeof(float), hipMemcpyHostToDevice, stream)); uTime = in; }
-    }
-    PgCameraRay *dOut = device ? out : (PgCameraRay *)s->cqOut.p;
+    Staging stage(s, mem, stream);
+    stage.in(pFilm, 2 * N); stage.in(pLens, 2 * N); stage.in(uTime, N);
+    stage.out(out, N);
+    if (int e = stage.upload()) return e;
     LensFrame *lf = nullptr;
     if (rd->camera_type == 3) {
         HIP_TRY(reserve(s->cqFrame, PG_LENS_FRAME_BYTES));
@@ -1542,9 +1593,9 @@ int pg_camera_rays_at(PgScene *s, const PgRenderDesc *rd, int32_t n, const float
         HIP_TRY(hipMemcpyAsync(s->cqFrame.p, &s->cqHead, sizeof(LensFrame), hipMemcpyHostToDevice, stream));
         lf = (LensFrame *)s->cqFrame.p;
     }
-    launch_camera_rays(*rd, lf, pFilm, pLens, uTime, n, dOut, stream);
+    launch_camera_rays(*rd, lf, pFilm, pLens, uTime, n, out, stream);
     HIP_TRY(hipGetLastError());
-    if (!device) HIP_TRY(hipMemcpyAsync(out, dOut, N * sizeof(PgCameraRay), hipMemcpyDeviceToHost, stream));
+    if (int e = stage.download()) return e;
     unsigned long long ls[3] = {0, 0, 0};
     if (lf) HIP_TRY(hipMemcpyAsync(ls, (const char *)lf + offsetof(LensFrame, stats), sizeof(ls), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
@@ -1559,89 +1610,58 @@ struct LightQuery {
     const PgInteraction *ref;
     const int32_t *light;
     const float *in;
-    PgLightSample *out; float *shadow;  // pg_light_sample_at (shadow may be nullptr)
+    PgLightSample *out; float *shadow;  // pg_light_sample_at (shadow may be nullptr: else eight floats per sample)
     float *pdf;                         // pg_light_pdf_at
     int mem;
     void *stream;
 };
 // Stage, sample, trace, visibility, copy back, one wait.  The sample kernel appends the rays of the samples EstimateDirect would test to the test
-// queue; the any-hit launch sees the scene as pg_intersect_p_at's does (the rays' times as the scene has them, the reference's visiting order)
-static int lightQuery(PgScene *s, const LightQuery &r) {
+// queue; the any-hit launch sees the scene as pg_intersect_p_at's does (the rays' times as the scene has them, the reference's visiting order).
+// pg_light_pdf_at traces nothing and moves no counter
+static int lightQuery(PgScene *s, LightQuery r) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)r.stream;
     const size_t n = (size_t)r.n;
-    const bool device = r.mem == PG_MEM_DEVICE, sample = r.out != nullptr;
-    const size_t inPer = sample ? 2 : 3;
-    const PgInteraction *ref = r.ref;
-    const int32_t *light = r.light;
-    const float *in = r.in;
-    if (!device) {  // the reference points, the per-sample input and the light indices, in this order (16-byte aligned records first)
-        HIP_TRY(reserve(s->tIn, n * (sizeof(PgInteraction) + (inPer + 1) * sizeof(float))));
-        char *base = (char *)s->tIn.p;
-        HIP_TRY(hipMemcpyAsync(base, r.ref, n * sizeof(PgInteraction), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(base + n * sizeof(PgInteraction), r.in, n * inPer * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(base + n * (sizeof(PgInteraction) + inPer * sizeof(float)), r.light, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        ref = (const PgInteraction *)base;
-        in = (const float *)(base + n * sizeof(PgInteraction));
-        light = (const int32_t *)(base + n * (sizeof(PgInteraction) + inPer * sizeof(float)));
-    }
+    const bool sample = r.out != nullptr;
+    Staging stage(s, r.mem, stream);
+    stage.in(r.ref, n); stage.in(r.in, (sample ? 2 : 3) * n); stage.in(r.light, n);
+    stage.out(r.out, n); stage.out(r.shadow, 8 * n); stage.out(r.pdf, n);
+    if (int e = stage.upload()) return e;
     DScene dsc = s->d;
     dsc.hitInst = nullptr; dsc.animXf = nullptr;
     if (!sample) {
-        if (!device) HIP_TRY(reserve(s->tOut, n * sizeof(float)));
-        float *dPdf = device ? r.pdf : (float *)s->tOut.p;
-        launch_light_pdf(dsc, ref, light, in, r.n, dPdf, stream);
+        launch_light_pdf(dsc, r.ref, r.light, r.in, r.n, r.pdf, stream);
         HIP_TRY(hipGetLastError());
-        if (!device) HIP_TRY(hipMemcpyAsync(r.pdf, dPdf, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (int e = stage.download()) return e;
         HIP_TRY(hipStreamSynchronize(stream));
         return PG_OK;
     }
     // the test queue, empty: k_light_sample appends to it
-    const int cap = regionCapFor(r.n);
-    const size_t N = (size_t)cap * PG_REGIONS;
-    HIP_TRY(reserve(s->tO, N * sizeof(float4)));
-    HIP_TRY(reserve(s->tD, N * (sizeof(float4) + sizeof(float))));
-    HIP_TRY(reserve(s->tCount, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int)));
-    HIP_TRY(reserve(s->tOcc, sizeof(int) * N));  // (answers by queue entry: the regions are not filled front to back here)
     RayQueue q;
-    q.o = (float4 *)s->tO.p; q.d = (float4 *)s->tD.p; q.counts = (int *)s->tCount.p; q.regionCap = cap;
-    float *times = reinterpret_cast<float *>(q.d + N);
-    HIP_TRY(hipMemsetAsync(q.counts, 0, PG_REGIONS * PG_COUNT_STRIDE * sizeof(int), stream));
-    const size_t recBytes = n * sizeof(PgLightSample), shadowBytes = r.shadow ? n * 8 * sizeof(float) : 0;
-    if (!device) HIP_TRY(reserve(s->tOut, recBytes + shadowBytes));
-    PgLightSample *dOut = device ? r.out : (PgLightSample *)s->tOut.p;
-    float *dShadow = !r.shadow ? nullptr : device ? r.shadow : (float *)((char *)s->tOut.p + recBytes);
-    launch_light_sample(dsc, ref, light, in, r.n, q, times, dOut, dShadow, stream);
+    float *times = nullptr;
+    if (int e = testQueue(s, regionCapFor(r.n), q, times)) return e;
+    HIP_TRY(reserve(s->tOcc, sizeof(int) * (size_t)q.regionCap * PG_REGIONS));  // (answers by queue entry: the regions are not filled front to back here)
+    HIP_TRY(hipMemsetAsync(q.counts, 0, QSTRIDE * sizeof(int), stream));
+    launch_light_sample(dsc, r.ref, r.light, r.in, r.n, q, times, r.out, r.shadow, stream);
     TraceConfig cfg = s->trace;
     cfg.anyhitFree = 0;
     hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
     HIP_TRY(hipEventRecord(a, stream));
     launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
     HIP_TRY(hipEventRecord(b, stream));
-    launch_light_visibility(q, (const int *)s->tOcc.p, dOut, stream);
+    launch_light_visibility(q, (const int *)s->tOcc.p, r.out, stream);
     HIP_TRY(hipGetLastError());
-    if (!device) {
-        HIP_TRY(hipMemcpyAsync(r.out, dOut, recBytes, hipMemcpyDeviceToHost, stream));
-        if (r.shadow) HIP_TRY(hipMemcpyAsync(r.shadow, dShadow, shadowBytes, hipMemcpyDeviceToHost, stream));
-    }
-    TraceCounters tc[2];
-    int counts[PG_REGIONS * PG_COUNT_STRIDE];
-    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(counts, q.counts, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
-    int tested = 0;
-    for (int k = 0; k < PG_REGIONS; ++k) tested += counts[k * PG_COUNT_STRIDE];
-    countQuery(s->counters, true, tested, tc, a, b);
-    return PG_OK;
+    if (int e = stage.download()) return e;
+    return finishQuery(s, stream, true, 0, 1, a, b, q.counts);
 }
 int pg_light_sample_at(PgScene *s, int32_t n, const PgInteraction *ref, const int32_t *light, const float *u, PgLightSample *out, float *shadow, int mem,
                        void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!ref || !light || !u || !out))) return setError(PG_ERR_INVALID, "pg_light_sample_at: null argument");
+    if (int e = checkArgs("pg_light_sample_at", s, n, {ref, light, u, out})) return e;
     if (n == 0) return PG_OK;
     return lightQuery(s, {n, ref, light, u, out, shadow, nullptr, mem, streamPtr});
 }
 int pg_light_pdf_at(PgScene *s, int32_t n, const PgInteraction *ref, const int32_t *light, const float *wi, float *pdf, int mem, void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!ref || !light || !wi || !pdf))) return setError(PG_ERR_INVALID, "pg_light_pdf_at: null argument");
+    if (int e = checkArgs("pg_light_pdf_at", s, n, {ref, light, wi, pdf})) return e;
     if (n == 0) return PG_OK;
     return lightQuery(s, {n, ref, light, wi, nullptr, nullptr, pdf, mem, streamPtr});
 }
@@ -1660,110 +1680,66 @@ struct MediumQuery {
     void *stream;
 };
 // The walks are throughRays' loop over this call's own buffers: packRays fills the test queue, k_tr_seed moves the rays with a valid medium into the
-// second queue (mqO / mqD) with their state, then per pass launch_closest -- the scene as pg_intersect_at's launch sees it -- and k_tr_step, which
+// second queue (mqO / mqD) with their state, then per pass launch_closest -- queryScene, the records by queue entry -- and k_tr_step, which
 // finishes rays into their records and appends the re-spawned ones to the other queue; the queue's size is read once per pass.
-static int mediumQuery(PgScene *s, const MediumQuery &r) {
+// pg_medium_sample_at traces nothing and moves no counter
+static int mediumQuery(PgScene *s, MediumQuery r) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)r.stream;
-    const size_t n = (size_t)r.n, n3 = 3 * n, nu = n * (size_t)r.nU;
-    const bool device = r.mem == PG_MEM_DEVICE;
-    const float *o = r.o, *d = r.d, *tmax = r.tmax, *time = r.time, *p1 = r.p1, *u = r.u;
-    const int32_t *medium = r.medium;
-    if (!device) {  // o, d, tmax, time, p1, medium, u in this order
-        HIP_TRY(reserve(s->mqIn, (3 * n3 + 3 * n + nu) * sizeof(float)));
-        float *in = (float *)s->mqIn.p;
-        HIP_TRY(hipMemcpyAsync(in, r.o, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(in + n3, r.d, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(in + 2 * n3, r.tmax, n * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (r.time) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + n, r.time, n * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (r.p1) HIP_TRY(hipMemcpyAsync(in + 2 * n3 + 2 * n, r.p1, n3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(in + 3 * n3 + 2 * n, r.medium, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        if (nu) HIP_TRY(hipMemcpyAsync(in + 3 * n3 + 3 * n, r.u, nu * sizeof(float), hipMemcpyHostToDevice, stream));
-        o = in; d = in + n3; tmax = in + 2 * n3; time = r.time ? in + 2 * n3 + n : nullptr; p1 = r.p1 ? in + 2 * n3 + 2 * n : nullptr;
-        medium = (const int32_t *)(in + 3 * n3 + 2 * n); u = nu ? in + 3 * n3 + 3 * n : nullptr;
-    }
+    const size_t n = (size_t)r.n;
+    Staging stage(s, r.mem, stream);
+    stage.rays(r.o, r.d, r.tmax, r.time, n);
+    stage.in(r.p1, 3 * n); stage.in(r.medium, n); stage.in(r.u, n * (size_t)r.nU);
+    stage.out(r.sample, n); stage.out(r.out, n); stage.out(r.isect, n);
+    if (int e = stage.upload()) return e;
     if (r.sample) {
-        if (!device) HIP_TRY(reserve(s->tOut, n * sizeof(PgMediumSample)));
-        PgMediumSample *dOut = device ? r.sample : (PgMediumSample *)s->tOut.p;
-        launch_medium_sample(s->d, s->nMedia, o, d, tmax, medium, u, r.nU, r.n, dOut, stream);
+        launch_medium_sample(s->d, s->nMedia, r.o, r.d, r.tmax, r.medium, r.u, r.nU, r.n, r.sample, stream);
         HIP_TRY(hipGetLastError());
-        if (!device) HIP_TRY(hipMemcpyAsync(r.sample, dOut, n * sizeof(PgMediumSample), hipMemcpyDeviceToHost, stream));
+        if (int e = stage.download()) return e;
         HIP_TRY(hipStreamSynchronize(stream));
         return PG_OK;
     }
     // --- the two queues: the test queue (packed: ray i at entry i) and the walk's own
     RayQueue q[2];
     float *times[2];
-    const float *none = nullptr;
-    if (int st = packRays(s, r.n, o, d, tmax, time, none, 0, PG_MEM_DEVICE, stream, q[1], times[1])) return st;
+    if (int e = packRays(s, r.n, r.o, r.d, r.tmax, r.time, stream, q[1], times[1])) return e;
     const int cap = q[1].regionCap;
     const size_t N = (size_t)cap * PG_REGIONS;
-    HIP_TRY(reserve(s->mqO, N * sizeof(float4)));
-    HIP_TRY(reserve(s->mqD, N * (sizeof(float4) + sizeof(float))));
     HIP_TRY(reserve(s->mqCount, QSTRIDE * sizeof(int)));
-    q[0].o = (float4 *)s->mqO.p; q[0].d = (float4 *)s->mqD.p; q[0].counts = (int *)s->mqCount.p; q[0].regionCap = cap;
-    times[0] = reinterpret_cast<float *>(q[0].d + N);
+    if (int e = queueOver(s->mqO, s->mqD, (int *)s->mqCount.p, cap, q[0], times[0])) return e;
     // --- the walk's state by ray, a pass's records by entry (the regions are not filled front to back after the first append)
     HIP_TRY(reserve(s->mqState, n * (2 * sizeof(float4) + sizeof(int2))));
     TrState state;
     state.tr = (float4 *)s->mqState.p; state.p1 = state.tr + n; state.cnt = (int2 *)(state.p1 + n);
     HIP_TRY(reserve(s->tHit, sizeof(float4) * N)); HIP_TRY(reserve(s->tT, sizeof(float) * N));
-    const bool wantIsect = r.isectTr && r.isect;
-    if (wantIsect) HIP_TRY(reserve(s->mqIsect, N * sizeof(PgInteraction)));
-    // --- the scene as pg_intersect_at's launch sees it: the hits' instances, a moving one's matrices at the ray's time
+    if (r.isect) HIP_TRY(reserve(s->mqIsect, N * sizeof(PgInteraction)));
     DScene dsc = s->d;
-    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
-    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * N)); dsc.hitInst = (int *)s->tInst.p; }
-    if (dsc.hasMotion) {
-        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * N * PG_XF_STRIDE * sizeof(float)));
-        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = (int)N;
-    }
-    const size_t recBytes = n * sizeof(PgTransmittance), isectBytes = wantIsect ? n * sizeof(PgInteraction) : 0;
-    if (!device) HIP_TRY(reserve(s->tOut, recBytes + isectBytes));
-    PgTransmittance *dOut = device ? r.out : (PgTransmittance *)s->tOut.p;
-    PgInteraction *dIsect = !wantIsect ? nullptr : device ? r.isect : (PgInteraction *)((char *)s->tOut.p + recBytes);
+    if (int e = queryScene(s, N, dsc)) return e;
     HIP_TRY(hipMemsetAsync(q[0].counts, 0, QSTRIDE * sizeof(int), stream));
-    launch_tr_seed(s->nMedia, q[1], times[1], medium, p1, r.n, state, q[0], times[0], dOut, dIsect, stream);
+    launch_tr_seed(s->nMedia, q[1], times[1], r.medium, r.p1, r.n, state, q[0], times[0], r.out, r.isect, stream);
     uint64_t segments = 0, passes = 0;
     int cur = 0;
     for (int pass = 0;; ++pass) {
         if (pass > 100000) return setError(PG_ERR_DEVICE, "%s: transmittance loop did not terminate", r.isectTr ? "pg_intersect_tr_at" : "pg_transmittance_at");
-        int blk[QSTRIDE];
-        HIP_TRY(hipMemcpyAsync(blk, q[cur].counts, sizeof(blk), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));  // the pass's one wait
-        const uint64_t nk = queueTotal(blk, 0);
+        uint64_t nk = 0;
+        if (int e = queueSize(stream, q[cur].counts, nk)) return e;  // the pass's one wait
         if (nk == 0) break;
         launch_closest(dsc, s->trace, q[cur], (float4 *)s->tHit.p, (float *)s->tT.p, (TraceCounters *)s->traceCn.p, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
         segments += nk; ++passes;
         HIP_TRY(hipMemsetAsync(q[cur ^ 1].counts, 0, QSTRIDE * sizeof(int), stream));
-        if (wantIsect) launch_interaction(dsc, q[cur], (const float4 *)s->tHit.p, (const float *)s->tT.p, times[cur], (PgInteraction *)s->mqIsect.p, stream);
-        launch_tr_step(dsc, r.isectTr, q[cur], times[cur], (const float4 *)s->tHit.p, (const float *)s->tT.p, state, u, r.nU, q[cur ^ 1], times[cur ^ 1], dOut,
-                       (const PgInteraction *)s->mqIsect.p, dIsect, stream);
+        if (r.isect) launch_interaction(dsc, q[cur], (const float4 *)s->tHit.p, (const float *)s->tT.p, times[cur], (PgInteraction *)s->mqIsect.p, stream);
+        launch_tr_step(dsc, r.isectTr, q[cur], times[cur], (const float4 *)s->tHit.p, (const float *)s->tT.p, state, r.u, r.nU, q[cur ^ 1], times[cur ^ 1], r.out,
+                       (const PgInteraction *)s->mqIsect.p, r.isect, stream);
         cur ^= 1;
     }
     HIP_TRY(hipGetLastError());
-    if (!device) {
-        HIP_TRY(hipMemcpyAsync(r.out, dOut, recBytes, hipMemcpyDeviceToHost, stream));
-        if (wantIsect) HIP_TRY(hipMemcpyAsync(r.isect, dIsect, isectBytes, hipMemcpyDeviceToHost, stream));
-    }
-    TraceCounters tc[2];
-    int guard = 0;
-    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    PgCounters &c = s->counters;
-    c.closest_rays += segments; c.closest_launches += passes;
-    if (passes) {
-        c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
-        c.node_visits = tc[0].node_visits + tc[1].node_visits;
-        c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    }
-    return cullGuardStatus(s, guard);
+    if (int e = stage.download()) return e;
+    return finishQuery(s, stream, false, segments, passes);
 }
 // The three entry points' shared refusals: name, the scene, n, the rays, the media and the draws
 static int mediumQueryArgs(const char *name, PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const int32_t *medium, const float *u,
                            int32_t nU, const void *out, const void *extra) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !medium || !out || !extra))) return setError(PG_ERR_INVALID, "%s: null argument", name);
+    if (int e = checkArgs(name, s, n, {o, d, tmax, medium, out, extra})) return e;
     if (nU < 0 || (n > 0 && nU > 0 && !u)) return setError(PG_ERR_INVALID, "%s: n_u = %d %s", name, nU, nU < 0 ? "is negative" : "without a stream of draws: null argument");
     return PG_OK;
 }
@@ -1791,44 +1767,41 @@ int pg_medium_sample_at(PgScene *s, int32_t n, const float *o, const float *d, c
 // ---- batched BSSRDF::Sample_S at the rays' closest hits, and the BSDF it installs at the exit point ----
 struct SubsurfaceQuery {
     int32_t n;
-    const float *o, *d, *tmax, *time, *u;
+    const float *o, *d, *tmax, *time, *u;  // u: three floats per ray
     PgInteraction *po, *pi;  // po may be nullptr
     PgSubsurfaceSample *out;
     int mem;
     void *stream;
 };
-// packRays, one closest-hit launch as pg_intersect_at's (k_interaction into po where asked for), k_sss_seed, then sssProbeChains' loop over this call's
+// packRays, one closest-hit launch as pg_intersect_at's (k_interaction into po where asked for), k_sss_seed, then sssProbeChains over this call's
 // own queues -- the job queue and two probe queues of the test queue's geometry -- with the SssState indexed by ray number in grow-only scratch, and
-// k_sss_emit.  The first walk's launches count (and k_sss_tally notes each probe ray for its sample's chain_rays); the second walk's go to the third set
-// of trace counters, as the renderer's.  One wait per step, for the number of chains still under way.
-static int subsurfaceQuery(PgScene *s, const SubsurfaceQuery &r) {
+// k_sss_emit.  The first walk's launches count (and k_sss_tally notes each probe ray for its sample's chain_rays).  One wait per step, for the number
+// of chains still under way.
+static int subsurfaceQuery(PgScene *s, SubsurfaceQuery r) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)r.stream;
     const size_t n = (size_t)r.n;
-    const bool device = r.mem == PG_MEM_DEVICE, vol = s->nMedia > 0;
+    const bool vol = s->nMedia > 0;
+    Staging stage(s, r.mem, stream);
+    stage.rays(r.o, r.d, r.tmax, r.time, n);
+    stage.in(r.u, 3 * n);
+    stage.out(r.out, n); stage.out(r.pi, n); stage.out(r.po, n);
+    if (int e = stage.upload()) return e;
     RayQueue q;
     float *times = nullptr;
-    const float *u = r.u;
-    if (int st = packRays(s, r.n, r.o, r.d, r.tmax, r.time, u, 3, r.mem, stream, q, times)) return st;
+    if (int e = packRays(s, r.n, r.o, r.d, r.tmax, r.time, stream, q, times)) return e;
     const int cap = q.regionCap;
     const size_t N = (size_t)cap * PG_REGIONS;
-    // --- the scene as pg_intersect_at's launch sees it, its records by queue entry: the probe queues are not filled front to back
+    // (the records by queue entry: the probe queues are not filled front to back)
     DScene dsc = s->d;
-    dsc.hitInst = nullptr; dsc.animXf = nullptr; dsc.nestXfOff = 0;
-    if (dsc.nInstances > 0) { HIP_TRY(reserve(s->tInst, sizeof(int) * N)); dsc.hitInst = (int *)s->tInst.p; }
-    if (dsc.hasMotion) {
-        HIP_TRY(reserve(s->tXf, (dsc.hasNest ? 2 : 1) * N * PG_XF_STRIDE * sizeof(float)));
-        dsc.animXf = (float *)s->tXf.p; dsc.nestXfOff = (int)N;
-    }
+    if (int e = queryScene(s, N, dsc)) return e;
     HIP_TRY(reserve(s->tHit, sizeof(float4) * N)); HIP_TRY(reserve(s->tT, sizeof(float) * N));
-    // --- the job queue and the two probe queues (their rays' times behind d, PG_QUEUE_TIMES), the state by ray
+    // --- the job queue and the two probe queues, the state by ray
     RayQueue sq[3];
+    float *probeTimes = nullptr;  // (k_sss_probe finds them behind d itself)
     HIP_TRY(reserve(s->ssCount, 3 * QSTRIDE * sizeof(int)));
-    for (int k = 0; k < 3; ++k) {
-        HIP_TRY(reserve(s->ssO[k], N * sizeof(float4)));
-        HIP_TRY(reserve(s->ssD[k], N * (sizeof(float4) + sizeof(float))));
-        sq[k].o = (float4 *)s->ssO[k].p; sq[k].d = (float4 *)s->ssD[k].p; sq[k].counts = (int *)s->ssCount.p + k * QSTRIDE; sq[k].regionCap = cap;
-    }
+    for (int k = 0; k < 3; ++k)
+        if (int e = queueOver(s->ssO[k], s->ssD[k], (int *)s->ssCount.p + k * QSTRIDE, cap, sq[k], probeTimes)) return e;
     HIP_TRY(reserve(s->ssState, n * (10 * sizeof(float4) + 2 * sizeof(int2) + 2 * sizeof(int))));
     if (dsc.hasMotion) HIP_TRY(reserve(s->ssXf, (dsc.hasNest ? 2 : 1) * n * PG_XF_STRIDE * sizeof(float)));
     SssState st = {};
@@ -1839,62 +1812,24 @@ static int subsurfaceQuery(PgScene *s, const SubsurfaceQuery &r) {
     int *chain = st.hitInst + n;
     st.hitXf = dsc.hasMotion ? (float *)s->ssXf.p : nullptr; st.hitXfNest = r.n;
     st.qjob = sq[0];
-    // --- the results: PG_MEM_DEVICE: the kernels write the caller's arrays; otherwise into tOut (records, pi, po), copied to the caller below
-    const size_t recBytes = n * sizeof(PgSubsurfaceSample), isectBytes = n * sizeof(PgInteraction);
-    if (!device) HIP_TRY(reserve(s->tOut, recBytes + (r.po ? 2 : 1) * isectBytes));
-    PgSubsurfaceSample *dOut = device ? r.out : (PgSubsurfaceSample *)s->tOut.p;
-    PgInteraction *dPi = device ? r.pi : (PgInteraction *)((char *)s->tOut.p + recBytes);
-    PgInteraction *dPo = !r.po ? nullptr : device ? r.po : (PgInteraction *)((char *)s->tOut.p + recBytes + isectBytes);
     TraceCounters *cn = (TraceCounters *)s->traceCn.p;
-    launch_closest(dsc, s->trace, q, (float4 *)s->tHit.p, (float *)s->tT.p, cn, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-    if (dPo) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, dPo, stream);
+    float4 *hits = (float4 *)s->tHit.p;
+    launch_closest(dsc, s->trace, q, hits, (float *)s->tT.p, cn, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
+    if (r.po) launch_interaction(dsc, q, hits, (const float *)s->tT.p, times, r.po, stream);
     HIP_TRY(hipMemsetAsync(st.qjob.counts, 0, QSTRIDE * sizeof(int), stream));
-    launch_sss_seed(dsc, vol, q, (const float4 *)s->tHit.p, times, u, r.n, st, chain, dOut, dPi, stream);
-    auto total = [&](const int *counts, uint64_t &t) -> int {
-        int blk[QSTRIDE];
-        HIP_TRY(hipMemcpyAsync(blk, counts, sizeof(blk), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        t = queueTotal(blk, 0);
-        return PG_OK;
-    };
+    launch_sss_seed(dsc, vol, q, hits, times, r.u, r.n, st, chain, r.out, r.pi, stream);
     uint64_t nJobs = 0, chainRays = 0, steps = 0;
-    if (int e = total(st.qjob.counts, nJobs)) return e;
-    for (int pass = 1; pass <= 2 && nJobs > 0; ++pass) {
-        RayQueue curQ = st.qjob;
-        uint64_t nRays = nJobs;
-        for (int step = 0; nRays > 0; ++step) {
-            if (step > 1000000) return setError(PG_ERR_DEVICE, "pg_subsurface_sample_at: a BSSRDF probe chain did not terminate");
-            RayQueue outQ = sq[1 + (step & 1)];
-            HIP_TRY(hipMemsetAsync(outQ.counts, 0, QSTRIDE * sizeof(int), stream));
-            launch_closest(dsc, s->trace, curQ, (float4 *)s->tHit.p, nullptr, pass == 1 ? cn : cn + 2, (int *)s->cursors.p, (int *)s->cullGuard.p, stream);
-            if (pass == 1) { chainRays += nRays; ++steps; launch_sss_tally(curQ, chain, stream); }
-            launch_sss_probe(dsc, st, pass, curQ, (const float4 *)s->tHit.p, outQ, stream, vol, vol && step == 0);
-            if (int e = total(outQ.counts, nRays)) return e;
-            curQ = outQ;
-        }
-    }
-    if (nJobs > 0) launch_sss_emit(dsc, vol, st, chain, times, dOut, dPi, stream);
+    if (int e = queueSize(stream, st.qjob.counts, nJobs)) return e;
+    if (int e = sssProbeChains("pg_subsurface_sample_at", s, dsc, st, sq + 1, hits, cn, nJobs, vol, stream,
+                               [&](const RayQueue &curQ, uint64_t nRays) { chainRays += nRays; ++steps; launch_sss_tally(curQ, chain, stream); })) return e;
+    if (nJobs > 0) launch_sss_emit(dsc, vol, st, chain, times, r.out, r.pi, stream);
     HIP_TRY(hipGetLastError());
-    if (!device) {
-        HIP_TRY(hipMemcpyAsync(r.out, dOut, recBytes, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(r.pi, dPi, isectBytes, hipMemcpyDeviceToHost, stream));
-        if (r.po) HIP_TRY(hipMemcpyAsync(r.po, dPo, isectBytes, hipMemcpyDeviceToHost, stream));
-    }
-    TraceCounters tc[2];
-    int guard = 0;
-    HIP_TRY(hipMemcpyAsync(tc, s->traceCn.p, sizeof(tc), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(&guard, s->cullGuard.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    PgCounters &c = s->counters;
-    c.closest_rays += n + chainRays; c.closest_launches += 1 + steps;
-    c.closest_node_visits = tc[0].node_visits; c.closest_tri_tests = tc[0].tri_tests;
-    c.node_visits = tc[0].node_visits + tc[1].node_visits;
-    c.tri_tests = tc[0].tri_tests + tc[1].tri_tests + c.light_tri_tests;
-    return cullGuardStatus(s, guard);
+    if (int e = stage.download()) return e;
+    return finishQuery(s, stream, false, n + chainRays, 1 + steps);
 }
 int pg_subsurface_sample_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *u, PgInteraction *po,
                             PgInteraction *pi, PgSubsurfaceSample *out, int mem, void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!o || !d || !tmax || !u || !pi || !out))) return setError(PG_ERR_INVALID, "pg_subsurface_sample_at: null argument");
+    if (int e = checkArgs("pg_subsurface_sample_at", s, n, {o, d, tmax, u, pi, out})) return e;
     if (n == 0) return PG_OK;
     const SubsurfaceQuery r = {n, o, d, tmax, time, u, po, pi, out, mem, streamPtr};
     return withExactFallback(s, [&]() { return subsurfaceQuery(s, r); });
@@ -1902,29 +1837,18 @@ int pg_subsurface_sample_at(PgScene *s, int32_t n, const float *o, const float *
 // The two exit-BSDF calls: stage, k_adapter, copy back, one wait.  Nothing is traced and no counter moves.
 static int adapterQuery(const char *name, PgScene *s, int32_t n, const PgInteraction *pi, const float *eta, const float *in, bool sample, int32_t flags,
                         PgScatter *out, int mem, void *streamPtr) {
-    if (!s || n < 0 || (n > 0 && (!pi || !eta || !in || !out))) return setError(PG_ERR_INVALID, "%s: null argument", name);
-    if (flags < 0 || flags > 31) return setError(PG_ERR_INVALID, "%s: flags %d is not a BxDFType mask (0 .. 31)", name, flags);
+    if (int e = checkArgs(name, s, n, {pi, eta, in, out}, flags)) return e;
     if (n == 0) return PG_OK;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)streamPtr;
-    const size_t nn = (size_t)n, inPer = sample ? 2 : 3;
-    const bool device = mem == PG_MEM_DEVICE;
-    PgScatter *dOut = out;
-    if (!device) {  // the records, eta and the per-record input, in this order (16-byte aligned records first)
-        HIP_TRY(reserve(s->tIn, nn * (sizeof(PgInteraction) + (inPer + 1) * sizeof(float))));
-        HIP_TRY(reserve(s->tOut, nn * sizeof(PgScatter)));
-        char *base = (char *)s->tIn.p;
-        HIP_TRY(hipMemcpyAsync(base, pi, nn * sizeof(PgInteraction), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(base + nn * sizeof(PgInteraction), eta, nn * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(base + nn * (sizeof(PgInteraction) + sizeof(float)), in, nn * inPer * sizeof(float), hipMemcpyHostToDevice, stream));
-        pi = (const PgInteraction *)base;
-        eta = (const float *)(base + nn * sizeof(PgInteraction));
-        in = eta + nn;
-        dOut = (PgScatter *)s->tOut.p;
-    }
-    launch_adapter(pi, eta, in, sample, flags, n, dOut, stream);
+    const size_t nn = (size_t)n;
+    Staging stage(s, mem, stream);
+    stage.in(pi, nn); stage.in(eta, nn); stage.in(in, (sample ? 2 : 3) * nn);
+    stage.out(out, nn);
+    if (int e = stage.upload()) return e;
+    launch_adapter(pi, eta, in, sample, flags, n, out, stream);
     HIP_TRY(hipGetLastError());
-    if (!device) HIP_TRY(hipMemcpyAsync(out, dOut, nn * sizeof(PgScatter), hipMemcpyDeviceToHost, stream));
+    if (int e = stage.download()) return e;
     HIP_TRY(hipStreamSynchronize(stream));
     return PG_OK;
 }
