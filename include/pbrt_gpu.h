@@ -763,7 +763,7 @@ int pg_intersect_p_at(PgScene *scene, int32_t n, const float *o, const float *d,
 
 /* The BSDF at one ray's closest hit, evaluated or sampled: 64 bytes, written by the device as four float4.  It is the BSDF PathIntegrator::Li holds
  * after isect.ComputeScatteringFunctions(ray, arena, true): TransportMode::Radiance, allowMultipleLobes = true, and a ray without differentials, so every
- * texture footprint is zero (ComputeDifferentials' early-out).  TransportMode::Importance is not built.  The BSDF of a subsurface material is
+ * texture footprint is zero (ComputeDifferentials' early-out).  TransportMode::Importance: pg_scatter_f_mode_at / pg_scatter_sample_mode_at below.  The BSDF of a subsurface material is
  * reported here; its BSSRDF is pg_subsurface_sample_at's below.  The BxDFType bits are the reference's (reflection.h:120-128): REFLECTION 1, TRANSMISSION 2, DIFFUSE 4, GLOSSY 8, SPECULAR 16. */
 typedef struct PgScatter {
     int32_t prim;          /* -1 = miss: every other field is 0.  Otherwise as pg_intersect_at reports it */
@@ -812,7 +812,7 @@ typedef struct PgLightSample {
  * per sample, the ray of p0.SpawnRayTo(p1) (interaction.h:73-78): origin[3], tMax = 1 - ShadowEpsilon, d[3], time -- zeros where visibility is -1 --,
  * with which a caller can march Tr itself or trace the ray again.  Occlusion is Scene::IntersectP's at ref.time, the scene seen as pg_intersect_p_at
  * sees it: a medium boundary occludes, as in Unoccluded; VisibilityTester::Tr of the same ray is pg_transmittance_at below.  Sample_Le / Pdf_Le are not
- * built, nor are light-selection distributions or TransportMode::Importance.  mem and stream as
+ * built, nor are light-selection distributions.  mem and stream as
  * pg_intersect_at takes them: with PG_MEM_DEVICE no input and no result visits the host; the call synchronises once.  PgCounters: shadow_rays += the
  * number of samples tested (light >= 0 and visibility >= 0), one shadow launch, the any-hit statistics as pg_intersect_p_at moves them; nothing else. */
 int pg_light_sample_at(PgScene *scene, int32_t n, const PgInteraction *ref, const int32_t *light, const float *u,
@@ -927,7 +927,7 @@ typedef struct PgSubsurfaceSample {
  *   as pg_intersect_at moves them, for those launches.  The device walks every chain a second time to stop at the chosen hit; that walk repeats
  *   queries the reference makes once and is not counted (the renderer's rule).
  * The arguments are checked before a device is touched; n == 0 returns PG_OK; a scene without BSSRDF materials is served (every hit: status 0).  The
- * call synchronises once per step of the chains.  BSSRDF::S itself, TransportMode::Importance and Sample_Le / Pdf_Le are not built. */
+ * call synchronises once per step of the chains.  BSSRDF::S itself, the adapter under TransportMode::Importance and Sample_Le / Pdf_Le are not built. */
 int pg_subsurface_sample_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
                             const float *u, PgInteraction *po, PgInteraction *pi, PgSubsurfaceSample *out, int mem, void *stream);
 /* Batched BSDF::f and BSDF::Pdf (reflection.cpp:680-693, :781-796) of the BSDF Sample_S installs at pi (bssrdf.cpp:243-248): one
@@ -971,7 +971,7 @@ typedef struct PgCameraRay {
  * fields the camera's, spp, the shutter and camera_medium are used.  mem and stream as pg_intersect_at: host arrays are staged once each way, PG_MEM_DEVICE
  * pointers are used as given (out 16-byte aligned), and the call synchronises once.  n == 0 returns PG_OK.
  * PgCounters: lens_rays_total / lens_rays_vignetted move as a frame's camera samples move them (the realistic camera's GenerateRay calls); nothing else moves --
- * camera_rays neither: no ray was traced.  Not built: Camera::We / Pdf_We / Sample_Wi. */
+ * camera_rays neither: no ray was traced.  Camera::We / Pdf_We / Sample_Wi: pg_camera_we_at / pg_camera_sample_wi_at below. */
 int pg_camera_rays_at(PgScene *scene, const PgRenderDesc *desc, int32_t n, const float *p_film, const float *p_lens, const float *u_time,
                       PgCameraRay *out, int mem, void *stream);
 
@@ -987,6 +987,77 @@ int pg_scatter_f_diff_at(PgScene *scene, int32_t n, const float *o, const float 
                          const float *wi, const float *diff, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
 int pg_scatter_sample_diff_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
                               const float *u, const float *diff, int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *stream);
+
+/* ---- Camera importance and TransportMode::Importance, for an integrator whose Li stays on the host and that traces light subpaths (bdpt, sppm, a light
+ * tracer): the camera end of a light subpath -- Camera::We / Pdf_We / Sample_Wi -- and the BSDF at a vertex of one. */
+
+/* What We, Pdf_We and Sample_Wi need of a PerspectiveCamera beside PgRenderDesc (whose size is pinned): the STORED inverses the reference keeps in
+ * Transform::mInv -- products of the factors' matrices, not numeric inversions -- and the image-plane area. */
+typedef struct PgCameraWeDesc {
+    float camera_to_raster[16];    /* Inverse(RasterToCamera).m = ScreenToRaster.m * CameraToScreen.m (camera.h:92-105) */
+    float world_to_camera[16];     /* Inverse(CameraToWorld at camera_time[0]).m: the CTM itself */
+    float world_to_camera_end[16]; /* ... at camera_time[1]; a still camera repeats world_to_camera */
+    float image_area;              /* A: the image plane's area at z = 1 (perspective.cpp:60-66), > 0 */
+} PgCameraWeDesc;
+
+/* PerspectiveCamera::We(ray, &pRaster) and ::Pdf_We(ray, &pdfPos, &pdfDir) for one ray (perspective.cpp:146-201): 32 bytes, written by the device as two
+ * float4.  The reference's spectrum is constant, so We is one float. */
+typedef struct PgCameraImportance {
+    int32_t status;      /* 0 = cosTheta <= 0 (the ray leaves the camera backwards or sideways): every other field 0;
+                            1 = pRaster outside the sample bounds (< pMin or >= pMax): p_raster and cos_theta reported, We and both pdfs 0;
+                            2 = inside */
+    float We;
+    float pdf_pos;       /* 1 / lensArea */
+    float pdf_dir;       /* 1 / (A cos^3) */
+    float p_raster[2];   /* what We returns through pRaster2 */
+    float cos_theta;     /* Dot(ray.d, c2w(0, 0, 1)) */
+    float reserved;      /* written as 0 */
+} PgCameraImportance;
+
+/* PerspectiveCamera::Sample_Wi(ref, u, &wi, &pdf, &pRaster, &vis) and vis.Unoccluded(scene) for one reference point (perspective.cpp:203-225): 64 bytes,
+ * written by the device as four float4.  `visibility` lies where PgLightSample has it. */
+typedef struct PgCameraSample {
+    int32_t status;      /* -1 = no sample drawn (ref.prim < 0): visibility -1, every other field 0; else the status of We on lensIntr.SpawnRay(-wi), as above */
+    int32_t visibility;  /* 1 = unoccluded, 0 = occluded, -1 = not tested (pdf == 0 or We == 0: bdpt tests neither, bdpt.cpp:470-481) */
+    float pdf;           /* dist^2 / (|n_lens . wi| lensArea), as computed: inf for a grazing direction */
+    float We;
+    float wi[3];         /* world, from ref towards the lens point */
+    float p_lens[3];     /* lensIntr.p */
+    float n_lens[3];     /* lensIntr.n = CameraToWorld(ref.time, (0, 0, 1)) */
+    float p_raster[2];
+    float reserved;      /* written as 0 */
+} PgCameraSample;
+
+/* Batched Camera::We and Camera::Pdf_We of the PerspectiveCamera `desc` and `we` describe (HostScene.camera_we_desc(); pbrt_host_camera_we_desc).  The
+ * reference implements them for that camera alone (the base class aborts): camera_type 1, 2 and 3 are refused with PG_ERR_UNSUPPORTED, on the host and
+ * before the device is touched.  o, d: three floats per ray, d used as given (not normalised); time: one float per ray (NULL: 0).  The camera matrix at the
+ * ray's time is AnimatedTransform::Interpolate's (transform.cpp:1144-1169): the start transform up to camera_time[0], the end transform from camera_time[1]
+ * on, in between m AND mInv interpolated as a moving instance's are.  desc is checked as pg_camera_rays_at checks it; `we` must be finite with
+ * image_area > 0 (PG_ERR_INVALID).  mem and stream as pg_camera_rays_at (PG_MEM_DEVICE: out 16-byte aligned); n == 0 returns PG_OK.  Nothing is traced
+ * and no counter of PgCounters moves; the call synchronises once.
+ * Not built: We for the other cameras (the reference has none), Sample_Le / Pdf_Le, light-selection distributions. */
+int pg_camera_we_at(PgScene *scene, const PgRenderDesc *desc, const PgCameraWeDesc *we, int32_t n, const float *o, const float *d, const float *time,
+                    PgCameraImportance *out, int mem, void *stream);
+/* Batched Camera::Sample_Wi followed by VisibilityTester::Unoccluded: bdpt's t = 1 connection and the camera end of a light tracer's splat.  ref exactly as
+ * pg_light_sample_at takes it (prim, p, p_error, n and time are read; prim >= 0 marks a valid point; n = 0: a medium vertex); u: two floats per sample,
+ * the lens sample.  We is evaluated on lensIntr.SpawnRay(-wi): the lens point carries no error bound, so the ray starts at p_lens.  A sample is tested for
+ * occlusion exactly when pdf > 0 and We != 0; its ray is ref.SpawnRayTo(lensIntr) at ref.time, traced as pg_light_sample_at traces its rays.  shadow may
+ * be NULL; otherwise eight floats per sample as pg_light_sample_at writes them (zeros where visibility is -1), for pg_transmittance_at -- the lens
+ * point's medium is desc->camera_medium.  desc, we, the refusals, mem and stream as pg_camera_we_at.  PgCounters: shadow_rays += the samples tested, one
+ * shadow launch, the any-hit statistics as pg_intersect_p_at moves them; nothing else. */
+int pg_camera_sample_wi_at(PgScene *scene, const PgRenderDesc *desc, const PgCameraWeDesc *we, int32_t n, const PgInteraction *ref, const float *u,
+                           PgCameraSample *out, float *shadow, int mem, void *stream);
+
+/* pg_scatter_f_diff_at / pg_scatter_sample_diff_at (diff may be NULL) under a TransportMode: mode 0 = Radiance -- the existing calls, byte for byte --,
+ * mode 1 = Importance, the BSDF ComputeScatteringFunctions(ray, arena, true, TransportMode::Importance) builds at a vertex of a light subpath; any other
+ * mode is PG_ERR_INVALID before the device is touched.  The mode changes f of the transmissive BxDFs alone: SpecularTransmission and FresnelSpecular drop
+ * the etaI^2 / etaT^2 factor (reflection.cpp:163-164, :514-516), MicrofacetTransmission's factor 1 / eta becomes 1 (:265).  pdf, wi, the component choice,
+ * eta, types and the shading normal do not depend on it.  Not built under Importance: the BSSRDF adapter (pg_subsurface_f_at: bdpt ignores BSSRDFs);
+ * CorrectShadingNormal (bdpt.cpp:55-65) is host arithmetic on PgInteraction.n and PgScatter.shading_n. */
+int pg_scatter_f_mode_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                         const float *wi, const float *diff, int32_t flags, int32_t mode, PgInteraction *isect, PgScatter *out, int mem, void *stream);
+int pg_scatter_sample_mode_at(PgScene *scene, int32_t n, const float *o, const float *d, const float *tmax, const float *time,
+                              const float *u, const float *diff, int32_t flags, int32_t mode, PgInteraction *isect, PgScatter *out, int mem, void *stream);
 
 int pg_counters(PgScene *scene, PgCounters *out);
 int pg_counters_reset(PgScene *scene);

@@ -29,6 +29,10 @@ void pbrt_host_render_desc(PbrtHostScene *s, PgRenderDesc *out);
 /* Integrator "directlighting": what pg_render_direct takes beside the render description (owned by the scene, valid until
  * pbrt_host_free); NULL for the path integrators, which render through pg_render. */
 const PgDirectLightingDesc *pbrt_host_direct_desc(PbrtHostScene *s);
+/* What pg_camera_we_at / pg_camera_sample_wi_at take beside the render description: the stored inverses of RasterToCamera and of the two ends of
+ * CameraToWorld, and the image-plane area A (perspective.cpp:60-66).  Returns 1 and fills *out for the perspective camera; 0 ("none": the reference
+ * implements We for no other camera) leaves *out zeroed. */
+int pbrt_host_camera_we_desc(PbrtHostScene *s, PgCameraWeDesc *out);
 
 /* Film: cropped image size; MergeFilmTile for one shard; final RGB image
  * (row-major, top row first, 3 floats per pixel) as Film::WriteImage computes it. */

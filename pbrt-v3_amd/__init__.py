@@ -62,6 +62,14 @@ SUBSURFACE_SAMPLE_DTYPE = np.dtype([("status", np.int32), ("prim", np.int32), ("
 CAMERA_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("time", np.float32), ("weight", np.float32), ("medium", np.int32),
                              ("has_differentials", np.int32), ("reserved", np.float32), ("differentials", np.float32, 12)])
 
+# one record of pg_camera_we_at: abi.PgCameraImportance field for field (32 bytes)
+CAMERA_IMPORTANCE_DTYPE = np.dtype([("status", np.int32), ("We", np.float32), ("pdf_pos", np.float32), ("pdf_dir", np.float32), ("p_raster", np.float32, 2),
+                                    ("cos_theta", np.float32), ("reserved", np.float32)])
+
+# one record of pg_camera_sample_wi_at: abi.PgCameraSample field for field (64 bytes; visibility where LIGHT_SAMPLE_DTYPE has it)
+CAMERA_SAMPLE_DTYPE = np.dtype([("status", np.int32), ("visibility", np.int32), ("pdf", np.float32), ("We", np.float32), ("wi", np.float32, 3),
+                                ("p_lens", np.float32, 3), ("n_lens", np.float32, 3), ("p_raster", np.float32, 2), ("reserved", np.float32)])
+
 _host = None
 _gpu = None
 
@@ -136,6 +144,12 @@ class HostScene:
         scene: keep the scene alive while the description is in use); None for the path integrators."""
         p = host_lib().pbrt_host_direct_desc(self._h)
         return p.contents if p else None
+
+    def camera_we_desc(self):
+        """The PgCameraWeDesc that goes with render_desc() into GpuScene.camera_we_at / camera_sample_wi_at: the stored inverses of RasterToCamera and of the
+        two ends of CameraToWorld, and the image-plane area; None for a camera that is not the perspective one (the reference implements We for no other)."""
+        we = abi.PgCameraWeDesc()
+        return we if host_lib().pbrt_host_camera_we_desc(self._h, C.byref(we)) else None
 
     @property
     def film_size(self):
@@ -349,7 +363,7 @@ class GpuScene:
         """pg_intersect_p_at on caller-owned device buffers: n bytes written at occluded_ptr."""
         _check(gpu_lib().pg_intersect_p_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, occluded_ptr, PG_MEM_DEVICE, stream), "pg_intersect_p_at")
 
-    def _scatter(self, name, o, d, tmax, extra, per, time, flags, with_interaction, diff=None):
+    def _scatter(self, name, o, d, tmax, extra, per, time, flags, with_interaction, diff=None, mode=None):
         o, d, tmax, time, n = self._rays(o, d, tmax, time)
         extra = np.ascontiguousarray(extra, np.float32)
         if extra.size != per * n:
@@ -363,22 +377,83 @@ class GpuScene:
                 raise ValueError("diff holds twelve floats per ray (PgCameraRay.differentials)")
             name = name.replace("_at", "_diff_at")
             args.append(diff.ctypes.data)
+        tail = [int(flags)]
+        if mode is not None:  # the _mode_ entry points: diff (may be NULL) behind wi / u, the TransportMode behind flags
+            name = name.replace("_diff_at", "_at").replace("_at", "_mode_at")
+            if diff is None:
+                args.append(None)
+            tail.append(int(mode))
         _check(getattr(gpu_lib(), name)(self._h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data, None if time is None else time.ctypes.data,
-                                        *args, int(flags), None if isect is None else isect.ctypes.data, out.ctypes.data, PG_MEM_HOST, None), name)
+                                        *args, *tail, None if isect is None else isect.ctypes.data, out.ctypes.data, PG_MEM_HOST, None), name)
         return (out, isect) if with_interaction else out
 
-    def scatter_f_at(self, o, d, tmax, wi, time=None, flags=31, with_interaction=False, diff=None):
+    def scatter_f_at(self, o, d, tmax, wi, time=None, flags=31, with_interaction=False, diff=None, mode=None):
         """Batched BSDF::f and BSDF::Pdf at the rays' closest hits (pg_scatter_f_at) on host arrays: the rays as intersect_at takes them, wi three floats per
         ray (world space, used as given), flags one BxDFType mask (0 .. 31) for all rays.  Returns the records as a structured array of SCATTER_DTYPE, or
         -- with_interaction -- (records, what intersect_at returns for the same rays) from the one trace.  diff: the rays' differentials, twelve floats
         per ray as camera_rays reports them (pg_scatter_f_diff_at: textures are filtered over the footprint ComputeDifferentials finds; twelve zeros =
-        a ray without); None: rays without differentials, the plain call."""
-        return self._scatter("pg_scatter_f_at", o, d, tmax, wi, 3, time, flags, with_interaction, diff)
+        a ray without); None: rays without differentials, the plain call.  mode: None = the calls above; abi.PG_MODE_RADIANCE (0) or
+        abi.PG_MODE_IMPORTANCE (1) = pg_scatter_f_mode_at, the BSDF under that TransportMode (1: at a vertex of a light subpath)."""
+        return self._scatter("pg_scatter_f_at", o, d, tmax, wi, 3, time, flags, with_interaction, diff, mode)
 
-    def scatter_sample_at(self, o, d, tmax, u, time=None, flags=31, with_interaction=False, diff=None):
+    def scatter_sample_at(self, o, d, tmax, u, time=None, flags=31, with_interaction=False, diff=None, mode=None):
         """Batched BSDF::Sample_f at the rays' closest hits (pg_scatter_sample_at, or -- diff -- pg_scatter_sample_diff_at): as scatter_f_at, with u two
         floats per ray (Sample_f's Point2f)."""
-        return self._scatter("pg_scatter_sample_at", o, d, tmax, u, 2, time, flags, with_interaction, diff)
+        return self._scatter("pg_scatter_sample_at", o, d, tmax, u, 2, time, flags, with_interaction, diff, mode)
+
+    def scatter_f_mode_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, diff_ptr, flags, mode, isect_ptr, out_ptr, stream=None):
+        """pg_scatter_f_mode_at on caller-owned device buffers: as scatter_f_diff_at_device, with the TransportMode (0 Radiance, 1 Importance) behind flags."""
+        _check(gpu_lib().pg_scatter_f_mode_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, diff_ptr, int(flags), int(mode), isect_ptr, out_ptr, PG_MEM_DEVICE,
+                                              stream), "pg_scatter_f_mode_at")
+
+    def scatter_sample_mode_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, diff_ptr, flags, mode, isect_ptr, out_ptr, stream=None):
+        """pg_scatter_sample_mode_at on caller-owned device buffers: as scatter_sample_diff_at_device, with the TransportMode behind flags."""
+        _check(gpu_lib().pg_scatter_sample_mode_at(self._h, n, o_ptr, d_ptr, tmax_ptr, time_ptr, u_ptr, diff_ptr, int(flags), int(mode), isect_ptr, out_ptr, PG_MEM_DEVICE,
+                                                   stream), "pg_scatter_sample_mode_at")
+
+    def camera_we_at(self, rd, we, o, d, time=None):
+        """Batched Camera::We and Camera::Pdf_We (pg_camera_we_at) on host arrays, for the perspective camera rd and we describe (HostScene.render_desc() and
+        camera_we_desc()): o and d three floats per ray (d used as given), time one (None: 0).  Returns a structured array of CAMERA_IMPORTANCE_DTYPE; traces
+        nothing and moves no counter.  Any other camera is refused (PG_ERR_UNSUPPORTED)."""
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        n = o.size // 3
+        if o.size != 3 * n or d.size != 3 * n:
+            raise ValueError("o and d hold three floats per ray")
+        if time is not None:
+            time = np.ascontiguousarray(time, np.float32)
+            if time.size != n:
+                raise ValueError("time holds one float per ray")
+        out = np.empty(n, CAMERA_IMPORTANCE_DTYPE)
+        _check(gpu_lib().pg_camera_we_at(self._h, C.byref(rd), C.byref(we), n, o.ctypes.data, d.ctypes.data, None if time is None else time.ctypes.data,
+                                         out.ctypes.data, PG_MEM_HOST, None), "pg_camera_we_at")
+        return out
+
+    def camera_sample_wi_at(self, rd, we, ref, u, with_shadow_rays=False):
+        """Batched Camera::Sample_Wi + VisibilityTester::Unoccluded (pg_camera_sample_wi_at) on host arrays: ref as light_sample_at takes it, u two floats per
+        reference point (the lens sample).  Returns a structured array of CAMERA_SAMPLE_DTYPE or -- with_shadow_rays -- (records, (n, 8) float32: origin,
+        tMax, direction, time of the tested samples' shadow rays, zeros elsewhere)."""
+        ref = np.ascontiguousarray(ref, INTERACTION_DTYPE)
+        u = np.ascontiguousarray(u, np.float32)
+        n = ref.size
+        if u.size != 2 * n:
+            raise ValueError("u holds two floats per reference point")
+        out = np.empty(n, CAMERA_SAMPLE_DTYPE)
+        shadow = np.empty((n, 8), np.float32) if with_shadow_rays else None
+        _check(gpu_lib().pg_camera_sample_wi_at(self._h, C.byref(rd), C.byref(we), n, ref.ctypes.data, u.ctypes.data, out.ctypes.data,
+                                                None if shadow is None else shadow.ctypes.data, PG_MEM_HOST, None), "pg_camera_sample_wi_at")
+        return (out, shadow) if with_shadow_rays else out
+
+    def camera_we_at_device(self, rd, we, n, o_ptr, d_ptr, time_ptr, out_ptr, stream=None):
+        """pg_camera_we_at on caller-owned device buffers (raw pointers): 3 n floats at o_ptr and d_ptr, n at time_ptr (None: 0); n records of
+        CAMERA_IMPORTANCE_DTYPE written at out_ptr (16-byte aligned).  Nothing visits the host."""
+        _check(gpu_lib().pg_camera_we_at(self._h, C.byref(rd), C.byref(we), n, o_ptr, d_ptr, time_ptr, out_ptr, PG_MEM_DEVICE, stream), "pg_camera_we_at")
+
+    def camera_sample_wi_at_device(self, rd, we, n, ref_ptr, u_ptr, out_ptr, shadow_ptr=None, stream=None):
+        """pg_camera_sample_wi_at on caller-owned device buffers: n records of INTERACTION_DTYPE at ref_ptr, 2 n floats at u_ptr; n records of
+        CAMERA_SAMPLE_DTYPE written at out_ptr (16-byte aligned) and, unless shadow_ptr is None, 8 n floats at shadow_ptr."""
+        _check(gpu_lib().pg_camera_sample_wi_at(self._h, C.byref(rd), C.byref(we), n, ref_ptr, u_ptr, out_ptr, shadow_ptr, PG_MEM_DEVICE, stream),
+               "pg_camera_sample_wi_at")
 
     def scatter_f_diff_at_device(self, n, o_ptr, d_ptr, tmax_ptr, time_ptr, wi_ptr, diff_ptr, flags, isect_ptr, out_ptr, stream=None):
         """pg_scatter_f_diff_at on caller-owned device buffers: as scatter_f_at_device, with 12 n floats at diff_ptr (16-byte aligned; None: no differentials)."""

@@ -10,6 +10,7 @@ PG_MAX_LENS_INTERFACES = 32
 PG_SAMPLER_HALTON, PG_SAMPLER_SOBOL, PG_SAMPLER_RANDOM, PG_SAMPLER_STRATIFIED, PG_SAMPLER_ZEROTWO, PG_SAMPLER_MAXMINDIST = range(6)
 PG_OK = 0
 PG_MEM_HOST, PG_MEM_DEVICE = 0, 1
+PG_MODE_RADIANCE, PG_MODE_IMPORTANCE = 0, 1  # TransportMode, as pg_scatter_*_mode_at take it
 PG_OPT_OVERLAP_SHADOW = 1
 PG_SHADING_MATERIAL_PREPASS, PG_SHADING_LISTS_DID_NOT_FIT = 0x100, 0x200
 PG_LIGHTS_UNIFORM, PG_LIGHTS_POWER, PG_LIGHTS_SPATIAL = 0, 1, 2
@@ -206,6 +207,20 @@ class PgCameraRay(C.Structure):
                 ("has_differentials", C.c_int32), ("reserved", C.c_float), ("differentials", C.c_float * 12)]
 
 
+class PgCameraWeDesc(C.Structure):
+    _fields_ = [("camera_to_raster", C.c_float * 16), ("world_to_camera", C.c_float * 16), ("world_to_camera_end", C.c_float * 16), ("image_area", C.c_float)]
+
+
+class PgCameraImportance(C.Structure):
+    _fields_ = [("status", C.c_int32), ("We", C.c_float), ("pdf_pos", C.c_float), ("pdf_dir", C.c_float), ("p_raster", C.c_float * 2),
+                ("cos_theta", C.c_float), ("reserved", C.c_float)]
+
+
+class PgCameraSample(C.Structure):
+    _fields_ = [("status", C.c_int32), ("visibility", C.c_int32), ("pdf", C.c_float), ("We", C.c_float), ("wi", C.c_float * 3),
+                ("p_lens", C.c_float * 3), ("n_lens", C.c_float * 3), ("p_raster", C.c_float * 2), ("reserved", C.c_float)]
+
+
 class PgCounters(C.Structure):
     _fields_ = [("camera_rays", C.c_uint64), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64), ("light_tri_tests", C.c_uint64),
@@ -270,6 +285,14 @@ GPU_SYMBOLS = {
                                        C.c_void_p, C.c_int, C.c_void_p]),
     "pg_scatter_sample_diff_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_camera_we_at": (C.c_int, [C.c_void_p, C.POINTER(PgRenderDesc), C.POINTER(PgCameraWeDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int, C.c_void_p]),
+    "pg_camera_sample_wi_at": (C.c_int, [C.c_void_p, C.POINTER(PgRenderDesc), C.POINTER(PgCameraWeDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p]),
+    "pg_scatter_f_mode_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pg_scatter_sample_mode_at": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pg_counters": (C.c_int, [C.c_void_p, C.POINTER(PgCounters)]),
     "pg_counters_reset": (C.c_int, [C.c_void_p]),
     "pg_scene_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -283,6 +306,7 @@ HOST_SYMBOLS = {
     "pbrt_host_scene_desc": (C.POINTER(PgSceneDesc), [C.c_void_p]),
     "pbrt_host_render_desc": (None, [C.c_void_p, C.POINTER(PgRenderDesc)]),
     "pbrt_host_direct_desc": (C.POINTER(PgDirectLightingDesc), [C.c_void_p]),
+    "pbrt_host_camera_we_desc": (C.c_int, [C.c_void_p, C.POINTER(PgCameraWeDesc)]),
     "pbrt_host_film_size": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pbrt_host_film_clear": (None, [C.c_void_p]),
     "pbrt_host_film_merge": (None, [C.c_void_p, C.POINTER(PgRenderDesc), C.c_void_p, C.c_void_p, C.c_int]),

@@ -1296,7 +1296,8 @@ int pg_render_sharded(PgScene *const *scenes, int32_t n, const PgRenderDesc *des
 // pg_intersect / pg_intersect_p (rays at time 0; primitive, t and barycentrics), pg_intersect_at / pg_intersect_p_at (Ray::time; the
 // SurfaceInteraction, pg_interaction.h), pg_scatter_f_at / pg_scatter_sample_at (the BSDF at the closest hit, pg_scatter.h) and pg_light_le_at (the
 // radiance the ray meets, pg_lightquery.h) are one device path, rayQuery: pack, trace, emit, account, one wait.  The other families have a driver each:
-// lightQuery (reference points instead of rays), mediumQuery, subsurfaceQuery with adapterQuery, and pg_camera_rays_at.  What the drivers share is
+// lightQuery (reference points instead of rays), mediumQuery, subsurfaceQuery with adapterQuery, pg_camera_rays_at, and pg_camera_we_at /
+// pg_camera_sample_wi_at.  What the drivers share is
 // stated once, in front of them:
 //   checkArgs    the entry points' refusals
 //   Staging      a call's host arrays <-> the scene's two staging arenas
@@ -1440,6 +1441,7 @@ struct RayQuery {
     int32_t flags = 0;
     float *le = nullptr;  // pg_light_le_at (at, not anyhit): three floats per ray
     const float *diff = nullptr;  // pg_scatter_*_diff_at: the rays' differentials, twelve floats per ray (nullptr: rays without)
+    bool importance = false;      // pg_scatter_*_mode_at with mode 1: the BSDF of TransportMode::Importance (pg_cameraimportance.h)
 };
 static int rayQuery(PgScene *s, RayQuery r) {
     HIP_TRY(hipSetDevice(s->device));
@@ -1489,7 +1491,8 @@ static int rayQuery(PgScene *s, RayQuery r) {
     HIP_TRY(hipEventRecord(b, stream));
     if (r.anyhit) launch_occluded_bytes((const int *)s->tOcc.p, r.occluded, r.n, stream);
     else if (r.at) {
-        if (r.scatter && stL) launch_scatter_diff(dsc, q, (const float4 *)s->tHit.p, r.scatterIn, r.sample, r.flags, stL, r.scatter, stream);
+        if (r.scatter && r.importance) launch_scatter_importance(dsc, q, (const float4 *)s->tHit.p, r.scatterIn, r.sample, r.flags, stL, r.scatter, stream);
+        else if (r.scatter && stL) launch_scatter_diff(dsc, q, (const float4 *)s->tHit.p, r.scatterIn, r.sample, r.flags, stL, r.scatter, stream);
         else if (r.scatter) launch_scatter(dsc, q, (const float4 *)s->tHit.p, r.scatterIn, r.sample, r.flags, r.scatter, stream);
         if (r.out) launch_interaction(dsc, q, (const float4 *)s->tHit.p, (const float *)s->tT.p, times, r.out, stream);
         if (r.le) launch_emitted(dsc, q, (const float4 *)s->tHit.p, r.le, stream);
@@ -1527,12 +1530,13 @@ int pg_intersect_p_at(PgScene *s, int32_t n, const float *o, const float *d, con
 }
 // The two scattering queries: pg_intersect_at's call with the BSDF's records beside (or instead of) the interactions
 static int scatterQuery(const char *name, PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *in, bool sample,
-                        int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr, const float *diff = nullptr) {
+                        int32_t flags, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr, const float *diff = nullptr, int32_t mode = 0) {
     if (int e = checkArgs(name, s, n, {o, d, tmax, in, out}, flags)) return e;
+    if (mode < 0 || mode > 1) return setError(PG_ERR_INVALID, "%s: mode %d is no TransportMode (0 = Radiance, 1 = Importance)", name, mode);
     if (diff && mem == PG_MEM_DEVICE && ((uintptr_t)diff & 15)) return setError(PG_ERR_INVALID, "%s: diff in device memory must be 16-byte aligned (it is read as float4)", name);
     if (n == 0) return PG_OK;
     RayQuery r = {n, o, d, tmax, time, false, true, nullptr, nullptr, nullptr, isect, nullptr, mem, streamPtr};
-    r.scatter = out; r.scatterIn = in; r.sample = sample; r.flags = flags; r.diff = diff;
+    r.scatter = out; r.scatterIn = in; r.sample = sample; r.flags = flags; r.diff = diff; r.importance = mode == 1;
     return withExactFallback(s, [&]() { return rayQuery(s, r); });
 }
 int pg_scatter_f_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *wi, int32_t flags,
@@ -1552,6 +1556,15 @@ int pg_scatter_sample_diff_at(PgScene *s, int32_t n, const float *o, const float
                               PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
     return scatterQuery("pg_scatter_sample_diff_at", s, n, o, d, tmax, time, u, true, flags, isect, out, mem, streamPtr, diff);
 }
+// ... and under a TransportMode: 0 = Radiance, the calls above; 1 = Importance, the same device path with launch_scatter_importance's kernel
+int pg_scatter_f_mode_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *wi, const float *diff, int32_t flags,
+                         int32_t mode, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    return scatterQuery("pg_scatter_f_mode_at", s, n, o, d, tmax, time, wi, false, flags, isect, out, mem, streamPtr, diff, mode);
+}
+int pg_scatter_sample_mode_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, const float *u, const float *diff, int32_t flags,
+                              int32_t mode, PgInteraction *isect, PgScatter *out, int mem, void *streamPtr) {
+    return scatterQuery("pg_scatter_sample_mode_at", s, n, o, d, tmax, time, u, true, flags, isect, out, mem, streamPtr, diff, mode);
+}
 int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const float *tmax, const float *time, PgInteraction *isect, float *Le, int mem,
                    void *streamPtr) {
     if (int e = checkArgs("pg_light_le_at", s, n, {o, d, tmax, Le})) return e;
@@ -1566,17 +1579,26 @@ int pg_light_le_at(PgScene *s, int32_t n, const float *o, const float *d, const 
 // itself, over facts that grant whatever it asks of a scene (the camera's kind and lens tables index the device's code and need no scene), then against this scene's.
 // The realistic camera's lens block and zeroed statistics go into the call's LensFrame, whose counts are added to the scene's counters as a frame's are
 // (camera_rays excepted: no ray is traced)
+static int checkCameraDescAlone(const PgRenderDesc *&rd, PgRenderDesc &current) {
+    rd = pgCurrentRenderDesc(rd, current);
+    std::string err;
+    RenderSceneFacts granted = {INT_MAX, true, true, true, INT_MAX};
+    if (int st = pg_check_render_desc(rd, granted, err)) return setError(st, "%s", err.c_str());
+    return PG_OK;
+}
+static int checkCameraDescOfScene(const PgScene *s, const PgRenderDesc *rd) {
+    std::string err;
+    const RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
+    if (int st = pg_check_render_desc(rd, facts, err)) return setError(st, "%s", err.c_str());
+    return PG_OK;
+}
 int pg_camera_rays_at(PgScene *s, const PgRenderDesc *rd, int32_t n, const float *pFilm, const float *pLens, const float *uTime, PgCameraRay *out, int mem,
                       void *streamPtr) {
     if (int e = checkArgs("pg_camera_rays_at", rd ? s : nullptr, n, {pFilm, out})) return e;  // (the description is required as the scene is, whatever n)
     if (n == 0) return PG_OK;
     PgRenderDesc current;
-    rd = pgCurrentRenderDesc(rd, current);
-    std::string err;
-    RenderSceneFacts granted = {INT_MAX, true, true, true, INT_MAX};
-    if (int st = pg_check_render_desc(rd, granted, err)) return setError(st, "%s", err.c_str());
-    const RenderSceneFacts facts = {s->nMedia, s->cmaxmin.p != nullptr, s->d.sobolMatrices != nullptr, s->d.perms != nullptr, s->d.nPermDims};
-    if (int st = pg_check_render_desc(rd, facts, err)) return setError(st, "%s", err.c_str());
+    if (int e = checkCameraDescAlone(rd, current)) return e;
+    if (int e = checkCameraDescOfScene(s, rd)) return e;
     if (mem == PG_MEM_DEVICE && ((uintptr_t)out & 15)) return setError(PG_ERR_INVALID, "pg_camera_rays_at: out in device memory must be 16-byte aligned (it is written as float4)");
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)streamPtr;
@@ -1664,6 +1686,77 @@ int pg_light_pdf_at(PgScene *s, int32_t n, const PgInteraction *ref, const int32
     if (int e = checkArgs("pg_light_pdf_at", s, n, {ref, light, wi, pdf})) return e;
     if (n == 0) return PG_OK;
     return lightQuery(s, {n, ref, light, wi, nullptr, nullptr, pdf, mem, streamPtr});
+}
+
+// ---- batched Camera::We / Pdf_We and Camera::Sample_Wi + VisibilityTester::Unoccluded (pg_cameraimportance.h) ----
+// The refusals of both calls, before the device is touched: arguments, a camera that is not the perspective one (the description is checked by itself first,
+// so that a camera without We answers PG_ERR_UNSUPPORTED on any scene), `we`, the description against the scene, a misaligned device output
+static int cameraWeArgs(const char *name, PgScene *s, const PgRenderDesc *&rd, PgRenderDesc &current, const PgCameraWeDesc *we, int32_t n,
+                        std::initializer_list<const void *> required, const void *out, int mem) {
+    if (int e = checkArgs(name, rd && we ? s : nullptr, n, required)) return e;  // (both descriptions are required as the scene is, whatever n)
+    if (n == 0) return PG_OK;
+    if (int e = checkCameraDescAlone(rd, current)) return e;
+    if (rd->camera_type != 0)
+        return setError(PG_ERR_UNSUPPORTED, "%s: camera_type %d -- Camera::We / Pdf_We / Sample_Wi exist for the perspective camera (0) alone", name, rd->camera_type);
+    bool finite = std::isfinite(we->image_area);
+    for (int k = 0; k < 16; ++k) finite = finite && std::isfinite(we->camera_to_raster[k]) && std::isfinite(we->world_to_camera[k]) && std::isfinite(we->world_to_camera_end[k]);
+    if (!finite || !(we->image_area > 0))
+        return setError(PG_ERR_INVALID, "%s: PgCameraWeDesc must hold finite matrices and image_area > 0 (image_area %g)", name, (double)we->image_area);
+    if (int e = checkCameraDescOfScene(s, rd)) return e;
+    if (mem == PG_MEM_DEVICE && ((uintptr_t)out & 15)) return setError(PG_ERR_INVALID, "%s: out in device memory must be 16-byte aligned (it is written as float4)", name);
+    return PG_OK;
+}
+// Check, stage, one launch, copy back, one wait.  Nothing is traced, no counter moves
+int pg_camera_we_at(PgScene *s, const PgRenderDesc *rd, const PgCameraWeDesc *we, int32_t n, const float *o, const float *d, const float *time,
+                    PgCameraImportance *out, int mem, void *streamPtr) {
+    PgRenderDesc current;
+    if (int e = cameraWeArgs("pg_camera_we_at", s, rd, current, we, n, {o, d, out}, out, mem)) return e;
+    if (n == 0) return PG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    const size_t N = (size_t)n;
+    Staging stage(s, mem, stream);
+    stage.in(o, 3 * N); stage.in(d, 3 * N); stage.in(time, N);
+    stage.out(out, N);
+    if (int e = stage.upload()) return e;
+    launch_camera_we(*rd, *we, o, d, time, n, out, stream);
+    HIP_TRY(hipGetLastError());
+    if (int e = stage.download()) return e;
+    HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
+    return PG_OK;
+}
+// lightQuery's sample path with the camera's kernel in the light's place: stage, sample (the kernel appends the rays of the samples bdpt would connect to the
+// test queue), trace, visibility, copy back, one wait
+int pg_camera_sample_wi_at(PgScene *s, const PgRenderDesc *rd, const PgCameraWeDesc *we, int32_t n, const PgInteraction *ref, const float *u,
+                           PgCameraSample *out, float *shadow, int mem, void *streamPtr) {
+    PgRenderDesc current;
+    if (int e = cameraWeArgs("pg_camera_sample_wi_at", s, rd, current, we, n, {ref, u, out}, out, mem)) return e;
+    if (n == 0) return PG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)streamPtr;
+    const size_t N = (size_t)n;
+    Staging stage(s, mem, stream);
+    stage.in(ref, N); stage.in(u, 2 * N);
+    stage.out(out, N); stage.out(shadow, 8 * N);
+    if (int e = stage.upload()) return e;
+    DScene dsc = s->d;
+    dsc.hitInst = nullptr; dsc.animXf = nullptr;
+    RayQueue q;
+    float *times = nullptr;
+    if (int e = testQueue(s, regionCapFor(n), q, times)) return e;
+    HIP_TRY(reserve(s->tOcc, sizeof(int) * (size_t)q.regionCap * PG_REGIONS));  // (answers by queue entry, as lightQuery's)
+    HIP_TRY(hipMemsetAsync(q.counts, 0, QSTRIDE * sizeof(int), stream));
+    launch_camera_sample_wi(*rd, *we, ref, u, n, q, times, out, shadow, stream);
+    TraceConfig cfg = s->trace;
+    cfg.anyhitFree = 0;
+    hipEvent_t a = getEvent(s, 0), b = getEvent(s, 1);
+    HIP_TRY(hipEventRecord(a, stream));
+    launch_anyhit(dsc, cfg, q, (int *)s->tOcc.p, (TraceCounters *)s->traceCn.p + 1, (int *)s->cursors.p, stream);
+    HIP_TRY(hipEventRecord(b, stream));
+    launch_light_visibility(q, (const int *)s->tOcc.p, reinterpret_cast<PgLightSample *>(out), stream);  // (`visibility` lies where PgLightSample has it)
+    HIP_TRY(hipGetLastError());
+    if (int e = stage.download()) return e;
+    return finishQuery(s, stream, true, 0, 1, a, b, q.counts);
 }
 
 // ---- batched VisibilityTester::Tr, Scene::IntersectTr and Medium::Sample ----

@@ -374,7 +374,11 @@ template <class LB> PG_DEV Spec lobe_fresnel(const LB &b, float cosI) {  // Fres
     return sp(1.f);
 }
 PG_DEV float pow5f(float v) { return (v * v) * (v * v) * v; }
-template <class LB> PG_DEV Spec lobe_f(const LB &b, int lobe, V3 wo, V3 wi) {  // BxDF::f of the wrapped BxDF (lobe = b.type), local frame
+// IMP (here and in the functions below that hand it down): TransportMode::Importance, for the BSDF at a vertex of a light subpath -- pg_scatter_*_mode_at's
+// kernel (pg_cameraimportance.h) alone instantiates it; every other caller leaves the default, TransportMode::Radiance.  The mode is read where
+// reflection.cpp reads it: SpecularTransmission::Sample_f (:164), MicrofacetTransmission::f (:265) and FresnelSpecular::Sample_f (:514).  (bsdf_sample_specular
+// above, the frames' specialised glass, is not reached by a query and stays Radiance.)
+template <bool IMP = false, class LB> PG_DEV Spec lobe_f(const LB &b, int lobe, V3 wo, V3 wi) {  // BxDF::f of the wrapped BxDF (lobe = b.type), local frame
     const float ax = b.alpha_x, ay = b.alpha_y;
     switch (lobe) {
     case PG_BXDF_LAMBERT_R: return sp_of(b.R) * PG_INVPI;  // reflection.cpp:178-180
@@ -403,7 +407,7 @@ template <class LB> PG_DEV Spec lobe_f(const LB &b, int lobe, V3 wo, V3 wi) {  /
         Spec F = lobe_fresnel(b, dot(wi, whf));
         return (((sp_of(b.R) * tr2_D(ax, ay, wh)) * tr2_G(ax, ay, wo, wi)) * F) / (4 * cosThetaI * cosThetaO);
     }
-    case PG_BXDF_MICROFACET_T: {  // :247-274, TransportMode::Radiance
+    case PG_BXDF_MICROFACET_T: {  // :247-274
         if (same_hemisphere(wo, wi)) return sp(0);
         float cosThetaO = wo.z, cosThetaI = wi.z;
         if (cosThetaI == 0 || cosThetaO == 0) return sp(0);
@@ -413,7 +417,7 @@ template <class LB> PG_DEV Spec lobe_f(const LB &b, int lobe, V3 wo, V3 wi) {  /
         if (dot(wo, wh) * dot(wi, wh) > 0) return sp(0);
         Spec F = sp(fr_dielectric(dot(wo, wh), b.eta_a, b.eta_b));
         float sqrtDenom = dot(wo, wh) + eta * dot(wi, wh);
-        float factor = 1 / eta;
+        float factor = IMP ? 1 : 1 / eta;  // (mode == TransportMode::Radiance) ? (1 / eta) : 1
         return ((sp(1.f) - F) * sp_of(b.T)) *
                fabsf(tr2_D(ax, ay, wh) * tr2_G(ax, ay, wo, wi) * eta * eta * absdot(wi, wh) * absdot(wo, wh) * factor * factor /
                      (cosThetaI * cosThetaO * sqrtDenom * sqrtDenom));
@@ -462,19 +466,19 @@ template <class LB> PG_DEV float lobe_pdf(const LB &b, int lobe, V3 wo, V3 wi) {
 // BxDF::Sample_f of the wrapped BxDF; pdf keeps the caller's 0 on the reference's early `return 0` paths.  wantF = false: the
 // value of a NON-specular BxDF is not computed (0 is returned) -- BSDF::Sample_f throws it away and sums f() over all matching
 // BxDFs instead (reflection.cpp:768-775); direction, pdf and the specular BxDFs' values are what they always are
-template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &wi, float u0, float u1, float &pdf, int &sampledType, bool wantF = true) {
+template <bool IMP = false, class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &wi, float u0, float u1, float &pdf, int &sampledType, bool wantF = true) {
     const float ax = b.alpha_x, ay = b.alpha_y;
     switch (lobe) {
     case PG_BXDF_LAMBERT_R: case PG_BXDF_OREN_NAYAR:  // BxDF::Sample_f, :383-390
         wi = cosine_sample_hemisphere(u0, u1);
         if (wo.z < 0) wi.z *= -1;
         pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
+        return wantF ? lobe_f<IMP>(b, lobe, wo, wi) : sp(0);
     case PG_BXDF_LAMBERT_T:  // :396-403
         wi = cosine_sample_hemisphere(u0, u1);
         if (wo.z > 0) wi.z *= -1;
         pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
+        return wantF ? lobe_f<IMP>(b, lobe, wo, wi) : sp(0);
     case PG_BXDF_SPECULAR_R:  // :136-143
         wi = mk(-wo.x, -wo.y, wo.z);
         pdf = 1;
@@ -486,7 +490,7 @@ template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &
         if (!refract_dir(wo, n, etaI / etaT, wi)) return sp(0);
         pdf = 1;
         Spec ft = sp_of(b.T) * (sp(1.f) - sp(fr_dielectric(wi.z, b.eta_a, b.eta_b)));
-        ft = ft * ((etaI * etaI) / (etaT * etaT));
+        if (!IMP) ft = ft * ((etaI * etaI) / (etaT * etaT));
         return ft / fabsf(wi.z);
     }
     case PG_BXDF_FRESNEL_SPECULAR: {  // :487-521
@@ -502,7 +506,7 @@ template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &
         const V3 n = (wo.z < 0.f) ? mk(0, 0, -1) : mk(0, 0, 1);
         if (!refract_dir(wo, n, etaI / etaT, wi)) return sp(0);
         Spec ft = sp_of(b.T) * (1 - F);
-        ft = ft * ((etaI * etaI) / (etaT * etaT));
+        if (!IMP) ft = ft * ((etaI * etaI) / (etaT * etaT));
         sampledType = PG_BSDF_SPECULAR | PG_BSDF_TRANSMISSION;
         pdf = 1 - F;
         return ft / fabsf(wi.z);
@@ -514,7 +518,7 @@ template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &
         wi = reflect_about(wo, wh);
         if (!same_hemisphere(wo, wi)) return sp(0);
         pdf = tr2_pdf(ax, ay, wo, wh) / (4 * dot(wo, wh));
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
+        return wantF ? lobe_f<IMP>(b, lobe, wo, wi) : sp(0);
     }
     case PG_BXDF_MICROFACET_T: {  // :431-442
         if (wo.z == 0) return sp(0);
@@ -523,7 +527,7 @@ template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &
         float eta = wo.z > 0 ? (b.eta_a / b.eta_b) : (b.eta_b / b.eta_a);
         if (!refract_dir(wo, wh, eta, wi)) return sp(0);
         pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
+        return wantF ? lobe_f<IMP>(b, lobe, wo, wi) : sp(0);
     }
     case PG_BXDF_FRESNEL_BLEND: {  // :460-478
         if ((double)u0 < .5) {
@@ -537,7 +541,7 @@ template <class LB> PG_DEV Spec lobe_sample_f(const LB &b, int lobe, V3 wo, V3 &
             if (!same_hemisphere(wo, wi)) return sp(0);
         }
         pdf = lobe_pdf(b, lobe, wo, wi);
-        return wantF ? lobe_f(b, lobe, wo, wi) : sp(0);
+        return wantF ? lobe_f<IMP>(b, lobe, wo, wi) : sp(0);
     }
     }
     return sp(0);
@@ -567,7 +571,7 @@ template <class LB> PG_DEV Spec lbsdf_scaled(const LobeBsdfT<LB> &b, int i, Spec
 // vertex asks for f AND pdf of the other matching BxDFs inside both of its BSDF::Sample_f calls.  For the light's direction BSDF::f and
 // BSDF::Pdf stay two walks: fused there as well the kernel gained nothing on microfacet scenes and lost 20 % on an all-Lambert one --
 // a matter of what the register allocator makes of it, profiles/r04l_*).
-template <class LB> PG_DEV void lobe_f_pdf(const LB &b, int lobe, V3 wo, V3 wi, bool wantF, bool wantPdf, Spec &f, float &pdf) {
+template <bool IMP = false, class LB> PG_DEV void lobe_f_pdf(const LB &b, int lobe, V3 wo, V3 wi, bool wantF, bool wantPdf, Spec &f, float &pdf) {
     const float ax = b.alpha_x, ay = b.alpha_y;
     f = sp(0); pdf = 0;
     switch (lobe) {
@@ -605,22 +609,22 @@ template <class LB> PG_DEV void lobe_f_pdf(const LB &b, int lobe, V3 wo, V3 wi, 
         return;
     }
     }
-    if (wantF) f = lobe_f(b, lobe, wo, wi);
+    if (wantF) f = lobe_f<IMP>(b, lobe, wo, wi);
     if (wantPdf) pdf = lobe_pdf(b, lobe, wo, wi);
 }
-template <class LB> PG_DEV Spec lbsdf_f_local(const LobeBsdfT<LB> &b, V3 wo, V3 wi, bool reflect, int flags) {
+template <bool IMP = false, class LB> PG_DEV Spec lbsdf_f_local(const LobeBsdfT<LB> &b, V3 wo, V3 wi, bool reflect, int flags) {
     Spec f = sp(0);
     for (int i = 0; i < b.n; ++i) {
         const int lobe = lbsdf_lobe(b, i), type = lobe_type(lobe);
         if ((type & flags) == type && ((reflect && (type & PG_BSDF_REFLECTION)) || (!reflect && (type & PG_BSDF_TRANSMISSION))))
-            { const auto &L = lobe_at(b, i); f = f + lbsdf_scaled(b, i, lobe_f(L, lobe, wo, wi)); }
+            { const auto &L = lobe_at(b, i); f = f + lbsdf_scaled(b, i, lobe_f<IMP>(L, lobe, wo, wi)); }
     }
     return f;
 }
-template <class LB> PG_DEV Spec lbsdf_f(const LobeBsdfT<LB> &b, V3 woW, V3 wiW, int flags) {  // reflection.cpp:680-693
+template <bool IMP = false, class LB> PG_DEV Spec lbsdf_f(const LobeBsdfT<LB> &b, V3 woW, V3 wiW, int flags) {  // reflection.cpp:680-693
     V3 wi = world_to_local(b, wiW), wo = world_to_local(b, woW);
     if (wo.z == 0) return sp(0);
-    return lbsdf_f_local(b, wo, wi, dot(wiW, b.ng) * dot(woW, b.ng) > 0, flags);
+    return lbsdf_f_local<IMP>(b, wo, wi, dot(wiW, b.ng) * dot(woW, b.ng) > 0, flags);
 }
 template <class LB> PG_DEV float lbsdf_pdf(const LobeBsdfT<LB> &b, V3 woW, V3 wiW, int flags) {  // reflection.cpp:781-796
     if (b.n == 0) return 0.f;
@@ -635,7 +639,7 @@ template <class LB> PG_DEV float lbsdf_pdf(const LobeBsdfT<LB> &b, V3 woW, V3 wi
     return matchingComps > 0 ? pdf / matchingComps : 0.f;
 }
 // BSDF::Sample_f, reflection.cpp:714-779: returns f, pdf = 0 when there is no sample
-template <class LB> PG_DEV Spec lbsdf_sample_f(const LobeBsdfT<LB> &b, V3 woWorld, V3 &wiWorld, float u0, float u1, float &pdf, int flags, int &sampledType) {
+template <bool IMP = false, class LB> PG_DEV Spec lbsdf_sample_f(const LobeBsdfT<LB> &b, V3 woWorld, V3 &wiWorld, float u0, float u1, float &pdf, int flags, int &sampledType) {
     const int matchingComps = lbsdf_num_components(b, flags);
     sampledType = 0;
     pdf = 0;
@@ -652,7 +656,7 @@ template <class LB> PG_DEV Spec lbsdf_sample_f(const LobeBsdfT<LB> &b, V3 woWorl
     if (wo.z == 0) return sp(0);
     sampledType = lobe_type(chosenLobe);
     const bool bxdfSpecular = (sampledType & PG_BSDF_SPECULAR) != 0;
-    Spec f = lbsdf_scaled(b, chosen, lobe_sample_f(bxdf, chosenLobe, wo, wi, uR0, u1, pdf, sampledType, bxdfSpecular));
+    Spec f = lbsdf_scaled(b, chosen, lobe_sample_f<IMP>(bxdf, chosenLobe, wo, wi, uR0, u1, pdf, sampledType, bxdfSpecular));
     if (pdf == 0) { sampledType = 0; return sp(0); }
     wiWorld = local_to_world(b, wi);
     if (!bxdfSpecular) {  // :760-775: the other matching BxDFs' pdfs, and f over all matching BxDFs of the hemisphere the pair is in
@@ -666,7 +670,7 @@ template <class LB> PG_DEV Spec lbsdf_sample_f(const LobeBsdfT<LB> &b, V3 woWorl
             if (!(wantPdf || wantF)) continue;
             Spec fi;
             float pi;
-            { const auto &L = lobe_at(b, i); lobe_f_pdf(L, lobe, wo, wi, wantF, wantPdf, fi, pi); }
+            { const auto &L = lobe_at(b, i); lobe_f_pdf<IMP>(L, lobe, wo, wi, wantF, wantPdf, fi, pi); }
             if (wantPdf) pdf += pi;
             if (wantF) f = f + lbsdf_scaled(b, i, fi);
         }

@@ -542,5 +542,13 @@ void launch_camera_rays(const PgRenderDesc &rd, LensFrame *lf, const float *pFil
 // launch_scatter for rays with differentials, in a scene with textured materials or nesting (the caller's test: no other scene reads a footprint): stL is such
 // that lens_frame(stL)->differentials holds three float4 per ray, by ray -- rxOrigin, rxDirection, ryOrigin, ryDirection; twelve zeros = a ray without
 void launch_scatter_diff(const DScene &sc, RayQueue q, const float4 *hits, const float *in, bool sample, int flags, const float4 *stL, PgScatter *out, hipStream_t s);
+// ---- camera importance and TransportMode::Importance (pg_cameraimportance.h)
+// out[i] = PerspectiveCamera::We and ::Pdf_We of ray i (o, d: three floats; time: one, or nullptr = 0) for the camera of rd and we
+void launch_camera_we(const PgRenderDesc &rd, const PgCameraWeDesc &we, const float *o, const float *d, const float *time, int n, PgCameraImportance *out, hipStream_t s);
+// out[i] = PerspectiveCamera::Sample_Wi at ref[i] with u[2i .. 2i+1]; q, times and shadow as launch_light_sample's.  launch_light_visibility fills `visibility`
+void launch_camera_sample_wi(const PgRenderDesc &rd, const PgCameraWeDesc &we, const PgInteraction *ref, const float *u, int n, RayQueue q, float *times, PgCameraSample *out,
+                             float *shadow, hipStream_t s);
+// launch_scatter / launch_scatter_diff under TransportMode::Importance; stL as launch_scatter_diff's, or nullptr: rays without differentials
+void launch_scatter_importance(const DScene &sc, RayQueue q, const float4 *hits, const float *in, bool sample, int flags, const float4 *stL, PgScatter *out, hipStream_t s);
 int pgSetError(int code, const char *msg);  // pg_abi.hip: sets pg_last_error()
 #endif

@@ -2013,3 +2013,4 @@ void launch_light_tables(const DScene &sc, float *table, int nDistributions, hip
 #include "pg_mediumquery.h"  // the kernels of the medium queries (pg_transmittance_at / pg_intersect_tr_at / pg_medium_sample_at)
 #include "pg_subsurfacequery.h"  // the kernels of the subsurface queries (pg_subsurface_sample_at / pg_subsurface_f_at / pg_subsurface_sample_f_at)
 #include "pg_cameraquery.h"  // the kernels of the camera queries (pg_camera_rays_at / pg_scatter_f_diff_at / pg_scatter_sample_diff_at)
+#include "pg_cameraimportance.h"  // camera importance and TransportMode::Importance (pg_camera_we_at / pg_camera_sample_wi_at / pg_scatter_*_mode_at)

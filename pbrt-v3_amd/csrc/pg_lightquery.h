@@ -5,7 +5,7 @@
 // The kernels are wiring: the sample is load_light_hot + light_sample_li_hot's (pg_light.h), the shadow ray shadow_ray_to's, Pdf_Li is mis_light_of +
 // mis_light_pdf's, an emitter's L area_light_le's (pg_hit.h) and an infinite light's env_le's -- the functions the shading kernels call.  EXT as in
 // light_sample_li: the plain instantiations serve scenes of triangles with area and delta lights.  One thread per sample, PG_SHADE_BLOCK threads per
-// block, no LDS.  Tr through media is pg_mediumquery.h; Sample_Le / Pdf_Le, light-selection distributions and TransportMode::Importance are not built.
+// block, no LDS.  Tr through media is pg_mediumquery.h; Sample_Le / Pdf_Le and light-selection distributions are not built.
 #ifndef PG_LIGHTQUERY_H
 #define PG_LIGHTQUERY_H
 

@@ -5,7 +5,7 @@
 //
 // The kernel is wiring: the interaction is hit_isect's, what textures read of it tex_hit_setup's, Material::Bump material_bump's, the BxDF list
 // MatEval's or the material's own, and BSDF::f / Pdf / Sample_f are lbsdf_f / lbsdf_pdf / lbsdf_sample_f -- the functions k_direct calls, in k_direct's
-// order.  A subsurface material's BSDF is reported here, its BSSRDF by pg_subsurfacequery.h; TransportMode::Importance is not built.
+// order.  A subsurface material's BSDF is reported here, its BSSRDF by pg_subsurfacequery.h; TransportMode::Importance is k_scatter_importance's (pg_cameraimportance.h).
 #ifndef PG_SCATTER_H
 #define PG_SCATTER_H
 

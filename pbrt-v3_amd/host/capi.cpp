@@ -52,6 +52,7 @@ PbrtHostScene *pbrt_host_load_string(const char *text, int quick, const float *c
 void pbrt_host_free(PbrtHostScene *s) { delete s; }
 const PgSceneDesc *pbrt_host_scene_desc(PbrtHostScene *s) { return &s->flat.desc; }
 void pbrt_host_render_desc(PbrtHostScene *s, PgRenderDesc *out) { s->loaded->integrator->FillRenderDesc(out); }
+int pbrt_host_camera_we_desc(PbrtHostScene *s, PgCameraWeDesc *out) { return s->loaded->integrator->FillCameraWeDesc(out) ? 1 : 0; }
 const PgDirectLightingDesc *pbrt_host_direct_desc(PbrtHostScene *s) { return s->loaded->integrator->directLighting ? &s->direct : nullptr; }
 void pbrt_host_film_size(PbrtHostScene *s, int *w, int *h) {
     const Film &f = *s->loaded->integrator->camera->film;

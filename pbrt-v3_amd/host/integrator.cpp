@@ -521,6 +521,25 @@ void GpuPathIntegrator::FillRenderDesc(PgRenderDesc *rd) const {
     rd->tile_pixels = rd->filter_general ? (16 + rd->tile_halo[0] + rd->tile_halo[2]) * (16 + rd->tile_halo[1] + rd->tile_halo[3]) : 256;
 }
 
+// What PerspectiveCamera::We / Pdf_We / Sample_Wi read beside FillRenderDesc's fields: Inverse(RasterToCamera) and Inverse(c2w) at the ends of the motion --
+// the inverses Transform keeps (products of the factors' matrices, camera.h:92-105; the CTMs), never a numeric inversion -- and A, perspective.cpp:60-66
+bool GpuPathIntegrator::FillCameraWeDesc(PgCameraWeDesc *we) const {
+    memset(we, 0, sizeof(*we));
+    if (camera->realistic || camera->environment || camera->orthographic) return false;
+    memcpy(we->camera_to_raster, camera->RasterToCamera.GetInverseMatrix().m, 16 * sizeof(float));
+    memcpy(we->world_to_camera, camera->CameraToWorld.GetInverseMatrix().m, 16 * sizeof(float));
+    memcpy(we->world_to_camera_end, (camera->animated ? camera->CameraToWorldEnd : camera->CameraToWorld).GetInverseMatrix().m, 16 * sizeof(float));
+    const Film &film = *camera->film;
+    Point3f pMin = camera->RasterToCamera.Pt(Point3f(0, 0, 0));
+    Point3f pMax = camera->RasterToCamera.Pt(Point3f(film.fullResolution[0], film.fullResolution[1], 0));
+    Float inv = (Float)1 / pMin.z;  // Point3::operator/=, geometry.h:381-387
+    pMin = Point3f(pMin.x * inv, pMin.y * inv, pMin.z * inv);
+    inv = (Float)1 / pMax.z;
+    pMax = Point3f(pMax.x * inv, pMax.y * inv, pMax.z * inv);
+    we->image_area = std::abs((pMax.x - pMin.x) * (pMax.y - pMin.y));
+    return true;
+}
+
 void GpuPathIntegrator::FillDirectDesc(PgDirectLightingDesc *dl) const {
     dl->strategy = directStrategy;
     dl->n_lights = (int)lightSamples.size();

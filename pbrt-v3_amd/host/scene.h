@@ -299,6 +299,7 @@ class GpuPathIntegrator : public Integrator {
     void Render(const Scene &scene) override;
     void Flatten(const Scene &scene, FlatScene *flat) const;
     void FillRenderDesc(PgRenderDesc *rd) const;
+    bool FillCameraWeDesc(PgCameraWeDesc *we) const;  // false: not the perspective camera (the only one with We / Pdf_We / Sample_Wi)
     bool volumetric = false;  // VolPathIntegrator (integrators/volpath.cpp) instead of PathIntegrator
     // DirectLightingIntegrator (integrators/directlighting.cpp) instead: maxDepth is its "maxdepth"; rrThreshold and lightSampleStrategy are unused.
     // Rendered through pg_render_direct with the description FillDirectDesc gives beside FillRenderDesc's (whose integrator field stays 0)
